@@ -30,9 +30,45 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BYTES = 64_000_000           # --dump-outputs: what DIR holds at most, all ranks together
+DUMP_SEED = 0x58524954
 
 
-def run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in, K, W, slices=None):
+def resident_bursts(torch, dev, want, burst_bytes, frac):
+    """How many bursts stay resident in HBM: `want`, or as many as `frac` of the device's memory holds.  Sized on the device's
+    total memory, not on what happens to be free, so that the stream's wrap-around (and with it every step's input) is the same
+    from run to run; the free memory only caps it when something else holds the device."""
+    free_b, total_b = torch.cuda.mem_get_info(dev)
+    fit = int(total_b * frac) // burst_bytes
+    if fit * burst_bytes > free_b * 0.9:
+        fit = int(free_b * frac) // burst_bytes
+    return min(want, fit)
+
+
+def dump_outputs(out_dir, arrays, budget):
+    """--dump-outputs: every (name, array) as out_dir/<name>.npy, float32 arrays as float32, everything else as float64.  An
+    array larger than what is left of `budget` is written as a fixed, seeded sample -- one position drawn in each of m equal
+    strata -- with the positions beside it as <name>_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget - 256 * len(arrays)          # (an .npy header is 128 bytes)
+    for name, a in sorted(arrays.items(), key=lambda kv: np.asarray(kv[1]).size):
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64).reshape(-1)
+        idx_path = os.path.join(out_dir, name + "_index.npy")
+        if os.path.exists(idx_path):
+            os.remove(idx_path)
+        if a.nbytes > left:
+            m = max(1, min(a.size, left // (a.itemsize + 8)))
+            pos = (np.arange(m, dtype=np.int64) * a.size) // m
+            pos += np.random.default_rng(DUMP_SEED).integers(0, max(1, a.size // m), m)
+            a = a[pos]
+            np.save(idx_path, pos.astype(np.float64))
+            left -= pos.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in, K, W, slices=None, dump=None):
     """ONE stream per step, cut in `world` time slices of n_burst samples (BASELINE config 4): the C++ group API
     (xrit_group_*: ncclSend / ncclRecv of the halo, of 256 boundary symbols and of the clock recovery's carried state, two
     ncclAllGather of (polarity, status) and (count, status)).  The handles persist across steps, the slices of every step are generated and resident before the
@@ -49,8 +85,7 @@ def run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst
     halo = grp.halo_samples
     rccl_ranks = grp.rccl_ranks
     if slices is None:
-        free_b, _ = torch.cuda.mem_get_info(dev)
-        nbuf = max(1, min(W + K, int(free_b * 0.6) // (n_burst * 8)))
+        nbuf = max(1, resident_bursts(torch, dev, W + K, n_burst * 8, 0.6))
         slices = torch.empty((nbuf, n_burst, 2), dtype=torch.float32, device=dev)
     nbuf = slices.shape[0]
     slices = slices[:, :n_burst]
@@ -72,12 +107,16 @@ def run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst
     barrier()
     t0 = time.perf_counter()
     for t in range(W, W + K):
-        k, _off, pol = grp.process_slice_device(slices[t % nbuf].data_ptr(), n_burst, soft.data_ptr(), cap,
-                                                stream=stream.cuda_stream)
+        k, off, pol = grp.process_slice_device(slices[t % nbuf].data_ptr(), n_burst, soft.data_ptr(), cap,
+                                               stream=stream.cuda_stream)
         nsym += k
         flips += 1 if pol < 0 else 0
     barrier()
     elapsed = time.perf_counter() - t0
+    if dump is not None:        # what the last timed call handed this rank
+        sfx = "_rank%d" % rank if world > 1 else ""
+        dump_outputs(dump, {"soft_symbols" + sfx: soft[:k].cpu().numpy(), "n_symbols" + sfx: [k],
+                            "symbol_offset" + sfx: [off], "polarity" + sfx: [pol]}, DUMP_BYTES // world)
     if world > 1:
         t = torch.tensor([elapsed, float(nsym), float(flips)], dtype=torch.float64, device=dev)
         tmax = t.clone()
@@ -101,7 +140,7 @@ def run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst
 def bench_contiguous(args, torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in):
     """--contiguous: the edge-exchange mode as the whole run (its own JSON line)."""
     K, W = args.steps, args.warmup
-    r = run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in, K, W)
+    r = run_contiguous(torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in, K, W, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps({
             "metric": "Msamples/s in -> soft-symbols/s out (LRIT 293 ksym/s chain); % HBM roofline",
@@ -275,6 +314,10 @@ def main():
                     help="add the `contiguous` leg (second timed region, same JSON line) also at N = 1, where the RCCL communicator "
                          "has one rank; with N > 1 over RCCL the leg is always run")
     ap.add_argument("--contiguous-timeout", type=int, default=240, help="seconds the contiguous leg may take before the line is printed without it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them returned -- its soft symbols (float32) and their "
+                         "count -- as DIR/<name>.npy, 64 MB at most in all (a larger output as a fixed, seeded sample, with its "
+                         "positions as <name>_index.npy); the inputs depend on the arguments only")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)          # (internal: run ONE alternative leg in this process)
     ap.add_argument("--leg-dir", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--legs-in-process", action="store_true",
@@ -288,6 +331,8 @@ def main():
                     help="N ranks demodulate ONE stream cut in N slices, with RCCL edge-sample exchange "
                          "(SURVEY.md 8(e); the default is N independent segments, no data-path collective)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.leg:
         return leg_child(args)
 
@@ -334,8 +379,7 @@ def main():
     # The warm-up and timed bursts are all resident before the clock starts; the bursts of the detail pass are
     # generated into the same buffers afterwards.  If --steps asks for more bursts than fit in HBM the buffers
     # wrap (the stream then jumps back once per lap: config.bursts_reused says so).
-    free_b, _total_b = torch.cuda.mem_get_info(dev)
-    nbuf = max(2, min(W + K, int(free_b * 0.7) // (n_burst * 8)))
+    nbuf = max(2, resident_bursts(torch, dev, W + K, n_burst * 8, 0.7))
     bursts = torch.empty((nbuf, n_burst, 2), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev)
 
@@ -426,10 +470,16 @@ def main():
     for b in range(W, W + K):
         if prefetch and b + depth < W + K:
             ahead(b + depth)
-        nsym_total += step(b)
+        ns = step(b)
+        nsym_total += ns
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs:
+        # (before the detail pass below reuses `soft`)
+        sfx = "_rank%d" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"soft_symbols" + sfx: soft[:ns].cpu().numpy(), "n_symbols" + sfx: [ns]},
+                     DUMP_BYTES // world)
     st = dem.stats()
     prof_timed = dem.profile_read() if not args.no_profile else []
     dem.profile(False)

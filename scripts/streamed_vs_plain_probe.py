@@ -2,7 +2,7 @@
 strict mode), the fast and quick configurations, HRIT without a decimator -- symbols word for word and per-call statistics equal."""
 import os, sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import xritdemod_amd as xa
 import os as _os, sys as _sys

@@ -3,10 +3,11 @@
 Not product code and not the oracle: a CPU sketch used to choose chain length,
 guess construction and the Newton hand-off before writing csrc/costas.hip.
 """
+import os
 import sys
 import numpy as np
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import oracle
 import os as _os, sys as _sys
 _sys.path.insert(0, _os.path.normpath(_os.path.join(_os.path.dirname(_os.path.abspath(__file__)), '..')))

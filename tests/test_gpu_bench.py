@@ -96,6 +96,72 @@ def test_circuit_rate_burst_walks_overlapping_blocks():
     assert d["value"] > 0 and d["config"]["decimation"] == 1
 
 
+def test_dump_outputs_writes_whole_arrays_or_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs), no GPU: an array that fits is written whole, float32 staying float32 and the rest
+    float64; a larger one as the same seeded sample in every run, its positions sorted and in range beside it, and the
+    directory within the budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.standard_normal(1000).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"soft_symbols": small, "n_symbols": [small.size]}, 64000)
+    got, n = np.load(tmp_path / "a" / "soft_symbols.npy"), np.load(tmp_path / "a" / "n_symbols.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    assert n.dtype == np.float64 and n.tolist() == [1000.0]
+    assert not (tmp_path / "a" / "soft_symbols_index.npy").exists()
+    big = rng.standard_normal(100000).astype(np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"soft_symbols": big, "n_symbols": [big.size]}, 64000)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64000
+    pos, vals = np.load(tmp_path / "b" / "soft_symbols_index.npy"), np.load(tmp_path / "b" / "soft_symbols.npy")
+    assert pos.dtype == np.float64 and vals.dtype == np.float32 and pos.size == vals.size > 64000 // 16
+    ip = pos.astype(np.int64)
+    assert np.array_equal(ip, pos) and ip[0] >= 0 and ip[-1] < big.size and (np.diff(ip) > 0).all()
+    assert np.array_equal(vals, big[ip])
+    for f in ("soft_symbols.npy", "soft_symbols_index.npy", "n_symbols.npy"):
+        assert (tmp_path / "b" / f).read_bytes() == (tmp_path / "c" / f).read_bytes(), f
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """--dump-outputs DIR: the soft symbols the last timed step returned and their count, the same words from two runs with the
+    same arguments, and the words plain consecutive calls of a fresh handle give on the same stream's burst (warm-up 2 + 3 timed
+    steps: burst 4)."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path / run)] + SMALL,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        _check_line(_last_json(r.stdout), 1)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 64_000_000
+        soft, n = np.load(tmp_path / run / "soft_symbols.npy"), np.load(tmp_path / run / "n_symbols.npy")
+        assert soft.dtype == np.float32 and n.dtype == np.float64 and soft.size == int(n[0])
+        assert abs(soft.size - (1 << 24) / 5 / (1.25e6 / 293883)) < 2000 and np.isfinite(soft).all()
+        dumps.append(soft)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
+    import torch
+    import xritdemod_amd as xa
+    from xritdemod_amd import _capi
+    n, D, fs = 1 << 24, 5, 6.25e6
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    sp = _capi.synth_params(fs_in=fs, symbol_rate=293883.0, alpha=0.5, seed=0x58524954)
+    buf = torch.empty((5, n, 2), dtype=torch.float32, device=dev)
+    for b in range(5):
+        _capi.synth_generate_device(sp, b * n, n, buf[b].data_ptr(), device=0, stream=st)
+    torch.cuda.synchronize(dev)
+    cap = int(n / (D * 4.2)) + 4096
+    soft = torch.empty(cap, dtype=torch.float32, device=dev)
+    dem = xa.Demodulator(xa.Demodulator.config("lrit", fs, D, device=0, costas_chain_len=0, clock_chain_syms=0, front_exact=0))
+    for b in range(5):
+        k = dem.process_device(buf[b].data_ptr(), n, soft.data_ptr(), cap, stream=st)
+    torch.cuda.synchronize(dev)
+    dem.close()
+    assert np.array_equal(soft[:k].cpu().numpy().view(np.uint32), dumps[0].view(np.uint32))
+
+
 @pytest.mark.gpu
 def test_bench_alternative_legs_run_in_processes_of_their_own():
     """Round 6: parity_mode (cfg.front_exact = 2), exact_mode, fast_mode, quick_mode are each a fresh process of bench.py (--leg):
