@@ -350,6 +350,54 @@ int xrit_sync_fix_frames(const int8_t *symbols, size_t n_symbols, const xrit_syn
                          uint32_t min_correlation, int8_t *frames, uint8_t *valid, int device);
 
 /* ------------------------------------------------------------------------
+ * Decoder: Viterbi27 + NRZ-M (HRIT) + DeRandomizer + 4 x RS(255,223), the
+ * per-frame FEC of decoder/src/newdecoder.cpp:272-348 on the frames that
+ * xrit_sync_fix_frames[_device] writes (16384 int8 symbols each, valid[nf]).
+ * Soft convention: symbol s votes for coded bit 0 with weight s, 0 = erasure
+ * (the reference's unsigned 128).  Exact integer contract: DESIGN.md
+ * "Frame decoder".
+ *  - window (:272-276, :298-300): the last 64 symbols of the most recent
+ *    earlier valid frame (across calls; zeros at start and after reset) +
+ *    the 16384 frame symbols; a valid = 0 frame neither decodes nor moves it.
+ *  - Viterbi (:281): maximum likelihood over the window's 8224 bits, register
+ *    taking new bits at its low end, polynomials 0x4F / 0x6D, start metrics
+ *    0, ties keep the predecessor ns >> 1, traceback from the first best end
+ *    state.  HRIT: NRZ-M over the whole window (:282-284).  Bits 32 .. 8223,
+ *    MSB first, are cadu[f][1024] (:297, vitdecData at :305).
+ *  - viterbi_errors: window symbols with s * (1 - 2c) < 0, c the re-encoded
+ *    decision path (Viterbi27::GetBER, :309).
+ *  - derandomise bytes 4 .. 1023 with the CCSDS PN sequence (:304-307), then
+ *    RS(255,223) errors-only per interleaved codeword, dual basis
+ *    (decode_ccsds, :313-318): block[f][1020] (rsCorrectedData), the VCDU is
+ *    block[f][0 .. 892) (:359).  rs_errors = corrected symbols or -1; a -1
+ *    codeword passes through.  ok = valid and not all four -1 (:321).
+ *  - scid / vcid / counter from block[f][0 .. 5) (:342-348).
+ * A valid = 0 frame: zero cadu and block bytes, zero info, rs_errors all -1.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_decoder xrit_decoder;   /* Viterbi27 + DeRandomizer + ReedSolomon state (newdecoder.cpp:80,125-131) */
+typedef struct xrit_frame_info {
+    uint32_t valid;
+    uint32_t ok;
+    uint32_t viterbi_errors;
+    int32_t  rs_errors[4];
+    uint32_t scid, vcid, counter;
+} xrit_frame_info;
+
+/* hrit = 0: LRIT, 1: HRIT (NRZ-M).  No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_decoder_create(xrit_decoder **d, int hrit, int device);
+int xrit_decoder_destroy(xrit_decoder *d);
+/* carry back to erasures (lastFrameEnd = 128 everywhere, :141); waits for the handle's last call */
+int xrit_decoder_reset(xrit_decoder *d);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation; the carry is updated on
+ * the device.  d_cadu: nf * 1024 bytes and d_block: nf * 1020 bytes, both 16-byte aligned; d_info: nf entries.
+ * Calls on one handle share its carry and scratch: the caller keeps them in order (one stream, or events). */
+int xrit_decoder_decode_device(xrit_decoder *d, const int8_t *d_frames, const uint8_t *d_valid, size_t nf,
+                               uint8_t *d_cadu, uint8_t *d_block, xrit_frame_info *d_info, void *stream);
+/* host buffers; returns when the outputs are written */
+int xrit_decoder_decode(xrit_decoder *d, const int8_t *frames, const uint8_t *valid, size_t nf,
+                        uint8_t *cadu, uint8_t *block, xrit_frame_info *info);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

@@ -14,4 +14,5 @@ from ._capi import (  # noqa: F401
     SAMPLE_FLOATIQ, SAMPLE_S16IQ, SAMPLE_S8IQ, SAMPLE_U8IQ,
     Filters, FirFilter, AGC, CostasLoop, ClockRecovery, RtlIngest, Demodulator, Group, LocalFabric, group_unique_id, DemodConfig, DemodStats,
     loop_sincosf, SynthParams as DeviceSynthParams, synth_generate_device, quantize_i8_device, sync_correlate, sync_correlate_device, sync_fix_frames, sync_fix_frames_device,
+    LRIT_UW0, LRIT_UW2, HRIT_UW0, HRIT_UW2, FrameDecoder, FRAME_INFO_DTYPE, CADU_SIZE, BLOCK_SIZE, VCDU_SIZE,
 )

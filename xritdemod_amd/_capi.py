@@ -89,6 +89,11 @@ _SIGNATURES = {
     "xrit_sync_correlate": (C.c_int, [_vp, _sz, _vp, C.c_int, C.c_uint32, _vp, C.c_int]),
     "xrit_sync_fix_frames_device": (C.c_int, [_vp, _sz, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int, _vp]),
     "xrit_sync_fix_frames": (C.c_int, [_vp, _sz, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int]),
+    "xrit_decoder_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
+    "xrit_decoder_destroy": (C.c_int, [_vp]),
+    "xrit_decoder_reset": (C.c_int, [_vp]),
+    "xrit_decoder_decode_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "xrit_decoder_decode": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -668,3 +673,51 @@ def sync_correlate_device(d_symbols_ptr, n, d_hits_ptr, words=(LRIT_UW0, LRIT_UW
     w = np.asarray(words, np.uint64)
     _check(lib().xrit_sync_correlate_device(C.c_void_p(d_symbols_ptr), n, _p(w), len(w), frame, C.c_void_p(d_hits_ptr),
                                             device, C.c_void_p(stream) if stream else None))
+
+
+# ---- decoder: Viterbi27 + NRZ-M + derandomiser + 4 x RS(255,223) (decoder/src/newdecoder.cpp:272-348) ------------
+CADU_SIZE, BLOCK_SIZE, VCDU_SIZE = 1024, 1020, 892
+
+# xrit_frame_info, one row per frame
+FRAME_INFO_DTYPE = np.dtype([("valid", np.uint32), ("ok", np.uint32), ("viterbi_errors", np.uint32),
+                             ("rs_errors", np.int32, (4,)), ("scid", np.uint32), ("vcid", np.uint32),
+                             ("counter", np.uint32)])
+
+
+class FrameDecoder(_Handle):
+    """The decoder's per-frame FEC on aligned, phase-fixed frames (what sync_fix_frames returns): the Viterbi window
+    (64 carried symbols + the frame), HRIT's NRZ-M, the derandomiser and four interleaved RS(255,223) codewords.  The
+    carry runs across calls until reset().  mode: "lrit" or "hrit"."""
+    _destroy = "xrit_decoder_destroy"
+
+    def __init__(self, mode="lrit", device=0):
+        super().__init__()
+        if mode not in ("lrit", "hrit"):
+            raise ValueError(f"mode {mode!r}: 'lrit' or 'hrit'")
+        self.mode = mode
+        _check(lib().xrit_decoder_create(C.byref(self._h), 1 if mode == "hrit" else 0, device))
+
+    def decode(self, frames, valid):
+        """frames (nf, 16384) int8, valid (nf,) -> (cadu (nf, 1024) uint8, block (nf, 1020) uint8, info (nf,)
+        FRAME_INFO_DTYPE).  The VCDU of frame f is block[f, :892]; it counts when info["ok"][f]."""
+        fr = np.ascontiguousarray(frames, np.int8).reshape(-1, CODED_FRAME_SIZE)
+        v = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+        if len(v) != len(fr):
+            raise ValueError(f"{len(fr)} frames but {len(v)} valid flags")
+        nf = len(fr)
+        cadu = np.zeros((nf, CADU_SIZE), np.uint8)
+        block = np.zeros((nf, BLOCK_SIZE), np.uint8)
+        info = np.zeros(nf, FRAME_INFO_DTYPE)
+        _check(lib().xrit_decoder_decode(self._h, _p(fr), _p(v), nf, _p(cadu), _p(block), _p(info)))
+        return cadu, block, info
+
+    def decode_device(self, d_frames_ptr, d_valid_ptr, nf, d_cadu_ptr, d_block_ptr, d_info_ptr, stream=None):
+        """Device pointers (cadu and block 16-byte aligned, info nf * FRAME_INFO_DTYPE.itemsize bytes), asynchronous on
+        stream."""
+        _check(lib().xrit_decoder_decode_device(self._h, C.c_void_p(d_frames_ptr), C.c_void_p(d_valid_ptr), nf,
+                                                C.c_void_p(d_cadu_ptr), C.c_void_p(d_block_ptr), C.c_void_p(d_info_ptr),
+                                                C.c_void_p(stream) if stream else None))
+
+    def reset(self):
+        """The carry back to erasures (the decoder's start state)."""
+        _check(lib().xrit_decoder_reset(self._h))

@@ -19,6 +19,8 @@ namespace xrit {
 
 void set_error(const char *fmt, ...);
 const char *get_error();
+// hipSetDevice after checking that the device exists (XRIT_E_NO_DEVICE: "... no CPU path")
+int select_device(int device);
 
 #define XR_HIP(expr)                                                                        \
     do {                                                                                    \

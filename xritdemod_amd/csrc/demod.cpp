@@ -24,7 +24,7 @@ void set_error(const char *fmt, ...)
 }
 const char *get_error() { return g_err; }
 
-static int select_device(int device)
+int select_device(int device)
 {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);

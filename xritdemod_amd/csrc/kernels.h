@@ -440,6 +440,12 @@ int launch_sync_correlate(const int8_t *data, size_t n, const unsigned long long
 int launch_sync_fix(const int8_t *data, size_t n, const xrit_sync_hit *hits, unsigned frame, unsigned min_corr,
                     int8_t *frames, unsigned char *valid, hipStream_t s);
 int launch_quantize_i8(const float *in, int8_t *out, size_t n, hipStream_t s);
+// decoder (viterbi.hip, rs.hip): decision words of one resident window; Viterbi + carry, then derandomiser + RS
+size_t viterbi_slot_bytes();
+int launch_viterbi(const int8_t *frames, const unsigned char *valid, size_t nf, int hrit, int8_t *carry, int *prev, int *last,
+                   unsigned long long *dec, unsigned slots, unsigned char *cadu, unsigned *verr, hipStream_t s);
+int launch_rs(const unsigned char *cadu, const unsigned char *valid, const unsigned *verr, size_t nf, unsigned char *block,
+              xrit_frame_info *info, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

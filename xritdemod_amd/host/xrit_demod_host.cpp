@@ -76,6 +76,7 @@ struct Options {
     size_t fifo_block = 65535;     // complex samples per source callback (CFileFrontend.cpp:12 BUFFERSIZE)
     int fifo_lag = 1;              // source blocks that arrive between two looks of the DSP loop
     int front_exact = 0;           // cfg.front_exact: 1 = the Costas loop's final pass warmed up; 2 = the front end bit for bit a CPU chain's
+    std::string decode;            // --decode PATH: the decoder's frame steps on the symbols, VCDUs of good frames to PATH
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -89,6 +90,8 @@ void usage()
                  "         [--diag udp://HOST:PORT] [--drop [--queue-symbols N]] [--sndbuf BYTES]\n"
                  "         [--gpus N]   (devices 0..N-1: each block of --block samples is cut in N time slices, RCCL edge exchange)\n"
                  "         [--fifo [--fifo-block SAMPLES] [--fifo-lag BLOCKS]]   (the reference's FIFO chunking, demodulator.cpp:108-119)\n"
+                 "         [--decode PATH]   (correlate, fix, Viterbi, derandomise, RS(255,223) on the GPU: the 892-byte VCDU of every\n"
+                 "                            good frame appended to PATH, counts on stderr at exit; --sink null for a decode-only run)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -119,6 +122,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--gpus") { if (!(v = need("--gpus"))) return false; o.gpus = std::atoi(v); }
         else if (a == "--fifo-block") { if (!(v = need("--fifo-block"))) return false; o.fifo_block = (size_t)std::atoll(v); }
         else if (a == "--fifo-lag") { if (!(v = need("--fifo-lag"))) return false; o.fifo_lag = std::atoi(v); }
+        else if (a == "--decode") { if (!(v = need("--decode"))) return false; o.decode = v; }
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -133,8 +137,96 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--fifo: --fifo-block 1..%zu, --fifo-lag >= 1, one GPU\n", FIFO_COMPLEX);
         return false;
     }
+    if (!o.decode.empty() && (o.drop || o.gpus > 1)) {
+        std::fprintf(stderr, "--decode: one GPU, without --drop\n");
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
+
+// ---- --decode: the decoder's steps per frame (decoder/src/newdecoder.cpp:218-359) on the quantised symbols -------------
+// Whole 16384-symbol windows go through the correlator, the frame fix (HRIT: word forced to 0, NRZ-M takes the phase) and
+// the frame decoder; the symbols from the first window whose frame is not complete yet wait for the next round.
+struct FrameDecode {
+    static constexpr size_t FRAME = 16384, VCDU = 892;
+    static constexpr uint32_t MIN_CORRELATION = 46;     // MINCORRELATIONBITS (parameters.h:31)
+    FILE *out = nullptr;
+    xrit_decoder *dec = nullptr;
+    bool hrit = false;
+    int device = 0;
+    std::vector<int8_t> pending;
+    std::vector<xrit_sync_hit> hits;
+    std::vector<int8_t> frames;
+    std::vector<uint8_t> valid, cadu, block;
+    std::vector<xrit_frame_info> info;
+    size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
+
+    bool open(const std::string &path, bool hrit_mode, int dev)
+    {
+        hrit = hrit_mode;
+        device = dev;
+        if (xrit_decoder_create(&dec, hrit ? 1 : 0, device) != XRIT_OK) {
+            std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+            return false;
+        }
+        out = std::fopen(path.c_str(), "wb");
+        if (!out) { std::perror("decode output"); return false; }
+        return true;
+    }
+    bool add(const int8_t *sym, size_t n)
+    {
+        pending.insert(pending.end(), sym, sym + n);
+        const size_t nw = pending.size() / FRAME;
+        if (nw == 0) return true;
+        // newdecoder.cpp:21-24
+        const uint64_t words[2] = {hrit ? 0xfc4ef4fd0cc2df89ull : 0xfca2b63db00d9794ull, hrit ? 0x25010b02f33d2076ull : 0x035d49c24ff2686bull};
+        hits.resize(nw);
+        frames.resize(nw * FRAME);
+        valid.resize(nw);
+        if (xrit_sync_correlate(pending.data(), nw * FRAME, words, 2, FRAME, hits.data(), device) != XRIT_OK) return fail("correlate");
+        size_t take = nw;           // windows decoded this round
+        for (size_t f = 0; f < nw; ++f) {
+            if (hrit) hits[f].word = 0;
+            if (hits[f].correlation >= MIN_CORRELATION && f * FRAME + hits[f].position + FRAME > pending.size()) { take = f; break; }
+        }
+        if (take == 0) return true;
+        if (xrit_sync_fix_frames(pending.data(), pending.size(), hits.data(), FRAME, MIN_CORRELATION, frames.data(), valid.data(),
+                                 device) != XRIT_OK)
+            return fail("fix frames");
+        cadu.resize(take * 1024);
+        block.resize(take * 1020);
+        info.resize(take);
+        if (xrit_decoder_decode(dec, frames.data(), valid.data(), take, cadu.data(), block.data(), info.data()) != XRIT_OK)
+            return fail("decode");
+        for (size_t f = 0; f < take; ++f) {
+            if (!info[f].valid) continue;
+            ++n_frames;
+            viterbi_errors += info[f].viterbi_errors;
+            if (!info[f].ok) { ++n_dropped; continue; }
+            ++n_ok;
+            for (int k = 0; k < 4; ++k) rs_corrections += info[f].rs_errors[k] > 0 ? (size_t)info[f].rs_errors[k] : 0;
+            if (std::fwrite(block.data() + f * 1020, 1, VCDU, out) != VCDU) { std::perror("decode output"); return false; }
+        }
+        pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)(take * FRAME));
+        return true;
+    }
+    bool fail(const char *what)
+    {
+        std::fprintf(stderr, "decode: %s: %s\n", what, xrit_last_error());
+        return false;
+    }
+    void close()
+    {
+        if (dec) {
+            std::fprintf(stderr, "decode: %zu frames, %zu ok, %zu dropped, %zu RS corrections, mean Viterbi errors %.2f\n", n_frames,
+                         n_ok, n_dropped, rs_corrections, n_frames ? (double)viterbi_errors / (double)n_frames : 0.0);
+            xrit_decoder_destroy(dec);
+            dec = nullptr;
+        }
+        if (out) std::fclose(out);
+        out = nullptr;
+    }
+};
 
 // ---- sink ------------------------------------------------------------------------------------------------
 struct Sink {
@@ -438,6 +530,11 @@ int main(int argc, char **argv)
 
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
+    FrameDecode decode;
+    if (!o.decode.empty() && !decode.open(o.decode, o.mode == "hrit", o.device)) {
+        decode.close(); std::fclose(in); xrit_demod_destroy(chain);
+        return 1;
+    }
     Sink sink;
     SymbolQueue queue;
     queue.cap = o.queue_symbols;
@@ -563,6 +660,7 @@ int main(int argc, char **argv)
             rc = xrit_quantize_i8(chain, soft.data(), q.data(), nsym);
             if (rc != XRIT_OK) { std::fprintf(stderr, "quantize: %s\n", xrit_last_error()); exit_code = 1; break; }
             if (!sink.send_all(q.data(), nsym)) { exit_code = 1; break; }
+            if (decode.dec && !decode.add(q.data(), nsym)) { exit_code = 1; break; }
         }
         if (diag.fd >= 0 && nsym > 0) {
             // the first symbols of the call, complex (stage 4); only what the tap can take is copied back
@@ -599,6 +697,7 @@ int main(int argc, char **argv)
                          queue.dropped_disconnected);
     }
     sink.close_all();
+    decode.close();
     std::fclose(in);
     xrit_demod_destroy(chain);
     return exit_code;
