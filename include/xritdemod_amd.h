@@ -398,6 +398,86 @@ int xrit_decoder_decode(xrit_decoder *d, const int8_t *frames, const uint8_t *va
                         uint8_t *cadu, uint8_t *block, xrit_frame_info *info);
 
 /* ------------------------------------------------------------------------
+ * Channel demultiplexer and packet accounting: the last stage of the
+ * reference decoder's data path (decoder/src/newdecoder.cpp:309-395), on the
+ * decoder's outputs.  Exact integer contract: DESIGN.md "Channel demux".
+ *  - per call, in frame order: the correlator's hit as it returned it (the
+ *    phase of a LRIT frame), the frame's cadu (syncWord = cadu[0 .. 4), :302),
+ *    its block and its xrit_frame_info.  A valid = 0 frame does not exist
+ *    for this stage (:244-247).
+ *  - a good frame (ok) adds its VCDU block[0 .. 892) to channel vcid
+ *    (ChannelWriter::writeChannel, :356-360; VCID 63 is not filtered) and
+ *    runs the lost-packet test of :363-371 on 24-bit counters with the
+ *    reference's C types: a counter wrap adds -2^24, a repeated counter -1.
+ *  - every valid frame leaves one Statistics_st (Statistics.h:14-36), the
+ *    record StatisticsDispatcher sends (:373-395); xrit_frame_stats is its
+ *    compact form, xrit_demux_expand writes the 4167-byte wire form.
+ * The counters carry across calls on one handle until reset.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_demux xrit_demux;
+/* the counters of newdecoder.cpp:44-53 after a call (the 256-wide arrays as Statistics_st holds them; entries
+ * 64 .. 255 stay at their start values, vcid has 6 bits) */
+typedef struct xrit_decoder_stats {
+    uint64_t total_packets;          /* frameCount: valid frames */
+    uint64_t dropped_packets;        /* droppedPackets: valid frames with all four RS codewords -1 */
+    uint64_t lost_packets;           /* lostPackets (uint64, wraps) */
+    uint64_t sum_viterbi_errors;     /* the averageVitCorrections accumulator */
+    uint64_t sum_rs_corrections;     /* the averageRSCorrections accumulator */
+    int64_t  received[256];          /* receivedPacketsPerFrame: -1 until a channel's first good frame */
+    int64_t  lost[256];              /* lostPacketsPerFrame */
+    int64_t  last_counter[256];      /* lastPacketCount: -1 until a channel's first good frame */
+    uint32_t start_time;             /* Statistics_st::startTime: the handle's creation, Unix seconds */
+    uint32_t reserved;
+} xrit_decoder_stats;
+/* Statistics_st after one frame, without the arrays: every scalar, plus the frame's VCID entries of the two arrays.
+ * A frame that is not good has scid = vcid = packet_number = signal_quality = phase_correction = 0, frame_lock = 0
+ * and received_vc = lost_vc = 0 (its record changes no array entry); a valid = 0 frame has an all-zero record. */
+typedef struct xrit_frame_stats {
+    uint64_t packet_number;          /* the 24-bit counter */
+    uint64_t lost_packets;
+    uint64_t dropped_packets;
+    uint64_t total_packets;
+    int64_t  received_vc;            /* receivedPacketsPerChannel[vcid] after the frame */
+    int64_t  lost_vc;                /* lostPacketsPerChannel[vcid] after the frame */
+    int32_t  rs_errors[4];
+    uint16_t vit_errors;             /* (uint16) viterbi_errors */
+    uint16_t frame_bits;             /* 8192 */
+    uint16_t average_vit_corrections;
+    uint8_t  scid, vcid;
+    uint8_t  signal_quality;         /* uint8(max(0, 100 - 10 * (100 * viterbi_errors / 8256))) in float32 */
+    uint8_t  sync_correlation;       /* (uint8) hit.correlation */
+    uint8_t  phase_correction;       /* hit.word ? 180 : 0 */
+    uint8_t  average_rs_corrections;
+    uint8_t  sync_word[4];
+    uint8_t  frame_lock;
+    uint8_t  valid;
+    uint8_t  reserved[6];
+} xrit_frame_stats;                  /* 88 bytes */
+#define XRIT_STATISTICS_WIRE_BYTES 4167   /* sizeof(Statistics_st), packed */
+
+int xrit_demux_create(xrit_demux **dm, int device);
+int xrit_demux_destroy(xrit_demux *dm);
+/* the start state of newdecoder.cpp:133-137 (startTime is kept); waits for the handle's last call */
+int xrit_demux_reset(xrit_demux *dm);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation; it may be queued directly
+ * behind xrit_decoder_decode_device.  nf <= 2^24.  d_hits, d_info, d_records: nf entries; d_cadu: nf * 1024 bytes;
+ * d_block: nf * 1020 bytes; d_vcdu: room for nf * 892 bytes (the good frames' VCDUs grouped by VCID in ascending
+ * order, frame order within a VCID; rows d_offsets[v] .. d_offsets[v + 1] are channel v's); d_offsets: 65 entries.
+ * d_cadu, d_block and d_vcdu 4-byte aligned.  Calls on one handle share its state and scratch: keep them in order. */
+int xrit_demux_process_device(xrit_demux *dm, const xrit_sync_hit *d_hits, const uint8_t *d_cadu, const uint8_t *d_block,
+                              const xrit_frame_info *d_info, size_t nf, uint8_t *d_vcdu, uint32_t *d_offsets,
+                              xrit_frame_stats *d_records, void *stream);
+/* host buffers (one upload, one download); returns when the outputs are written */
+int xrit_demux_process(xrit_demux *dm, const xrit_sync_hit *hits, const uint8_t *cadu, const uint8_t *block,
+                       const xrit_frame_info *info, size_t nf, uint8_t *vcdu, uint32_t *offsets, xrit_frame_stats *records);
+/* the full counters after the handle's last call (waits for it) */
+int xrit_demux_stats(xrit_demux *dm, xrit_decoder_stats *out);
+/* plain host code: from the counters before a call and that call's records, one XRIT_STATISTICS_WIRE_BYTES record per
+ * valid frame into out (packed, little-endian, Statistics.h's field order: what StatisticsDispatcher sends).
+ * Returns the number of records written, or a negative XRIT_E_* code. */
+int xrit_demux_expand(const xrit_decoder_stats *start, const xrit_frame_stats *records, size_t nf, uint8_t *out);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

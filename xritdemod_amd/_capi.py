@@ -94,6 +94,13 @@ _SIGNATURES = {
     "xrit_decoder_reset": (C.c_int, [_vp]),
     "xrit_decoder_decode_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "xrit_decoder_decode": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "xrit_demux_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_demux_destroy": (C.c_int, [_vp]),
+    "xrit_demux_reset": (C.c_int, [_vp]),
+    "xrit_demux_process_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "xrit_demux_process": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "xrit_demux_stats": (C.c_int, [_vp, _vp]),
+    "xrit_demux_expand": (C.c_int, [_vp, _vp, _sz, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -721,3 +728,103 @@ class FrameDecoder(_Handle):
     def reset(self):
         """The carry back to erasures (the decoder's start state)."""
         _check(lib().xrit_decoder_reset(self._h))
+
+
+# ---- channel demultiplexer and packet accounting (decoder/src/newdecoder.cpp:309-395) -------------------------------
+N_VCID = 64
+STATISTICS_WIRE_BYTES = 4167         # sizeof(Statistics_st), packed (decoder/src/Statistics.h:14-36)
+
+# xrit_frame_stats: Statistics_st after one frame, without the arrays (one row per frame)
+FRAME_STATS_DTYPE = np.dtype([
+    ("packet_number", np.uint64), ("lost_packets", np.uint64), ("dropped_packets", np.uint64),
+    ("total_packets", np.uint64), ("received_vc", np.int64), ("lost_vc", np.int64),
+    ("rs_errors", np.int32, (4,)),
+    ("vit_errors", np.uint16), ("frame_bits", np.uint16), ("average_vit_corrections", np.uint16),
+    ("scid", np.uint8), ("vcid", np.uint8), ("signal_quality", np.uint8), ("sync_correlation", np.uint8),
+    ("phase_correction", np.uint8), ("average_rs_corrections", np.uint8), ("sync_word", np.uint8, (4,)),
+    ("frame_lock", np.uint8), ("valid", np.uint8), ("reserved", np.uint8, (6,))])
+assert FRAME_STATS_DTYPE.itemsize == 88
+
+# xrit_decoder_stats: the counters of newdecoder.cpp:44-53 after a call
+DECODER_STATS_DTYPE = np.dtype([
+    ("total_packets", np.uint64), ("dropped_packets", np.uint64), ("lost_packets", np.uint64),
+    ("sum_viterbi_errors", np.uint64), ("sum_rs_corrections", np.uint64),
+    ("received", np.int64, (256,)), ("lost", np.int64, (256,)), ("last_counter", np.int64, (256,)),
+    ("start_time", np.uint32), ("reserved", np.uint32)])
+assert DECODER_STATS_DTYPE.itemsize == 6192
+
+
+def _hits16(hits, nf):
+    h = np.zeros((nf, 4), np.uint32)
+    if nf:
+        a = np.asarray(hits, np.uint32).reshape(nf, -1)
+        h[:, :min(4, a.shape[1])] = a[:, :4]
+    return h
+
+
+class ChannelDemux(_Handle):
+    """The reference decoder's last stage on the frame decoder's outputs: the good frames' VCDUs split by virtual
+    channel (ChannelWriter::writeChannel) and the Statistics_st record of every valid frame (newdecoder.cpp:309-395).
+    The counters run across calls until reset()."""
+    _destroy = "xrit_demux_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_demux_create(C.byref(self._h), device))
+
+    def process(self, hits, cadu, block, info):
+        """hits: rows (word, position, correlation[, reserved]) as the correlator returned them; cadu (nf, 1024),
+        block (nf, 1020), info (nf,) FRAME_INFO_DTYPE as FrameDecoder.decode returns them.  -> (vcdu (n_good, 892)
+        uint8 grouped by VCID in ascending order, frame order within a VCID; offsets (65,) uint32, channel v's rows
+        are offsets[v]:offsets[v + 1]; records (nf,) FRAME_STATS_DTYPE)."""
+        info = np.ascontiguousarray(info, FRAME_INFO_DTYPE).reshape(-1)
+        nf = len(info)
+        cadu = np.ascontiguousarray(cadu, np.uint8).reshape(nf, CADU_SIZE)
+        block = np.ascontiguousarray(block, np.uint8).reshape(nf, BLOCK_SIZE)
+        h = _hits16(hits, nf)
+        good = int(((info["valid"] != 0) & (info["ok"] != 0)).sum())
+        vcdu = np.zeros((good, VCDU_SIZE), np.uint8)
+        offsets = np.zeros(N_VCID + 1, np.uint32)
+        records = np.zeros(nf, FRAME_STATS_DTYPE)
+        _check(lib().xrit_demux_process(self._h, _p(h), _p(cadu), _p(block), _p(info), nf, _p(vcdu), _p(offsets),
+                                        _p(records)))
+        return vcdu, offsets, records
+
+    def channels(self, hits, cadu, block, info):
+        """process(), split: {vcid: (n, 892) uint8} for every VCID with good frames in this call."""
+        vcdu, off, _ = self.process(hits, cadu, block, info)
+        return {v: vcdu[off[v]:off[v + 1]] for v in range(N_VCID) if off[v + 1] > off[v]}
+
+    def process_device(self, d_hits_ptr, d_cadu_ptr, d_block_ptr, d_info_ptr, nf, d_vcdu_ptr, d_offsets_ptr,
+                       d_records_ptr, stream=None):
+        """Device pointers (hits nf x 16 bytes, cadu nf x 1024, block nf x 1020, info nf x 40, vcdu room for nf x 892,
+        offsets 65 x 4, records nf x 88), asynchronous on stream; may be queued behind FrameDecoder.decode_device."""
+        _check(lib().xrit_demux_process_device(self._h, C.c_void_p(d_hits_ptr), C.c_void_p(d_cadu_ptr),
+                                               C.c_void_p(d_block_ptr), C.c_void_p(d_info_ptr), nf,
+                                               C.c_void_p(d_vcdu_ptr), C.c_void_p(d_offsets_ptr),
+                                               C.c_void_p(d_records_ptr), C.c_void_p(stream) if stream else None))
+
+    def stats(self):
+        """The counters after the last call (a DECODER_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, DECODER_STATS_DTYPE)
+        _check(lib().xrit_demux_stats(self._h, _p(out)))
+        return out[0]
+
+    @staticmethod
+    def wire_records(start, records):
+        """The Statistics_st stream StatisticsDispatcher would send for one call: `start` is stats() taken before the
+        call, `records` the call's records; one 4167-byte record per valid frame, as bytes."""
+        st = np.zeros(1, DECODER_STATS_DTYPE)
+        st[0] = start
+        rec = np.ascontiguousarray(records, FRAME_STATS_DTYPE).reshape(-1)
+        n = int((rec["valid"] != 0).sum())
+        out = np.zeros(max(n, 1) * STATISTICS_WIRE_BYTES, np.uint8)
+        got = lib().xrit_demux_expand(_p(st), _p(rec), len(rec), _p(out))
+        if got < 0:
+            _check(got)
+        assert got == n
+        return out[:n * STATISTICS_WIRE_BYTES].tobytes()
+
+    def reset(self):
+        """The start state of newdecoder.cpp:133-137 (startTime is kept)."""
+        _check(lib().xrit_demux_reset(self._h))

@@ -446,6 +446,20 @@ int launch_viterbi(const int8_t *frames, const unsigned char *valid, size_t nf, 
                    unsigned long long *dec, unsigned slots, unsigned char *cadu, unsigned *verr, hipStream_t s);
 int launch_rs(const unsigned char *cadu, const unsigned char *valid, const unsigned *verr, size_t nf, unsigned char *block,
               xrit_frame_info *info, hipStream_t s);
+// demux (demux.hip): one tile of DEMUX_TILE frames per workgroup; the handle's state and the per-call scratch
+constexpr int DEMUX_TILE = 1024;
+struct DemuxState {                       // newdecoder.cpp:44-53, 133-137 (entries 64..255 are never touched)
+    long long last[64], received[64], lost[64];
+    unsigned long long frames, dropped, sum_vit, sum_rs, lost_total;
+};
+struct DemuxScratch {
+    unsigned *cnt; int *firstc, *lastc; unsigned *tsum;     // (a): [T][64] x 3, [T][4]
+    unsigned *base; int *P; unsigned long long *tin;         // (b): [T][64] x 2, [T][5]
+    long long *vcb;                                          // (b): [2][64]
+};
+int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,
+                 const xrit_frame_info *info, size_t nf, DemuxState *state, DemuxScratch &sc, unsigned char *vcdu,
+                 unsigned *offsets, xrit_frame_stats *records, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

@@ -37,12 +37,14 @@
 #include <netinet/in.h>
 #include <netinet/tcp.h>
 #include <sys/socket.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <atomic>
 #include <chrono>
 #include <deque>
 #include <mutex>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -77,6 +79,8 @@ struct Options {
     int fifo_lag = 1;              // source blocks that arrive between two looks of the DSP loop
     int front_exact = 0;           // cfg.front_exact: 1 = the Costas loop's final pass warmed up; 2 = the front end bit for bit a CPU chain's
     std::string decode;            // --decode PATH: the decoder's frame steps on the symbols, VCDUs of good frames to PATH
+    std::string channels;          // --channels DIR: the good frames' VCDUs split by VCID, DIR/channel_{vcid}.bin
+    std::string decoder_stats;     // --decoder-stats PATH: one Statistics_st (4167 bytes) per valid frame
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -92,6 +96,8 @@ void usage()
                  "         [--fifo [--fifo-block SAMPLES] [--fifo-lag BLOCKS]]   (the reference's FIFO chunking, demodulator.cpp:108-119)\n"
                  "         [--decode PATH]   (correlate, fix, Viterbi, derandomise, RS(255,223) on the GPU: the 892-byte VCDU of every\n"
                  "                            good frame appended to PATH, counts on stderr at exit; --sink null for a decode-only run)\n"
+                 "         [--channels DIR]   (the decoder's ChannelWriter: every good VCDU appended to DIR/channel_{vcid}.bin)\n"
+                 "         [--decoder-stats PATH]   (the decoder's Statistics_st, 4167 bytes per valid frame; lost packets on stderr at exit)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -123,6 +129,8 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--fifo-block") { if (!(v = need("--fifo-block"))) return false; o.fifo_block = (size_t)std::atoll(v); }
         else if (a == "--fifo-lag") { if (!(v = need("--fifo-lag"))) return false; o.fifo_lag = std::atoi(v); }
         else if (a == "--decode") { if (!(v = need("--decode"))) return false; o.decode = v; }
+        else if (a == "--channels") { if (!(v = need("--channels"))) return false; o.channels = v; }
+        else if (a == "--decoder-stats") { if (!(v = need("--decoder-stats"))) return false; o.decoder_stats = v; }
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -141,17 +149,30 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--decode: one GPU, without --drop\n");
         return false;
     }
+    if ((!o.channels.empty() || !o.decoder_stats.empty()) && (o.drop || o.gpus > 1)) {
+        std::fprintf(stderr, "--channels / --decoder-stats: one GPU, without --drop\n");
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
 
 // ---- --decode: the decoder's steps per frame (decoder/src/newdecoder.cpp:218-359) on the quantised symbols -------------
 // Whole 16384-symbol windows go through the correlator, the frame fix (HRIT: word forced to 0, NRZ-M takes the phase) and
 // the frame decoder; the symbols from the first window whose frame is not complete yet wait for the next round.
+// --channels / --decoder-stats add the channel demultiplexer behind the decoder (:309-395): ChannelWriter's files and
+// the Statistics_st stream, from the correlator's hits as it returned them.
 struct FrameDecode {
     static constexpr size_t FRAME = 16384, VCDU = 892;
     static constexpr uint32_t MIN_CORRELATION = 46;     // MINCORRELATIONBITS (parameters.h:31)
     FILE *out = nullptr;
+    FILE *stats_out = nullptr;
     xrit_decoder *dec = nullptr;
+    xrit_demux *dm = nullptr;
+    std::string channel_dir;
+    std::vector<xrit_sync_hit> raw_hits;
+    std::vector<uint8_t> vcdu, wire;
+    std::vector<xrit_frame_stats> records;
+    xrit_decoder_stats dm_stats{};
     bool hrit = false;
     int device = 0;
     std::vector<int8_t> pending;
@@ -161,7 +182,7 @@ struct FrameDecode {
     std::vector<xrit_frame_info> info;
     size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
 
-    bool open(const std::string &path, bool hrit_mode, int dev)
+    bool open(const std::string &path, const std::string &channels, const std::string &stats_path, bool hrit_mode, int dev)
     {
         hrit = hrit_mode;
         device = dev;
@@ -169,8 +190,23 @@ struct FrameDecode {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
         }
-        out = std::fopen(path.c_str(), "wb");
-        if (!out) { std::perror("decode output"); return false; }
+        if (!path.empty()) {
+            out = std::fopen(path.c_str(), "wb");
+            if (!out) { std::perror("decode output"); return false; }
+        }
+        if (channels.empty() && stats_path.empty()) return true;
+        if (xrit_demux_create(&dm, device) != XRIT_OK || xrit_demux_stats(dm, &dm_stats) != XRIT_OK) {
+            std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+            return false;
+        }
+        if (!channels.empty()) {
+            if (::mkdir(channels.c_str(), 0755) != 0 && errno != EEXIST) { std::perror("--channels"); return false; }
+            channel_dir = channels;
+        }
+        if (!stats_path.empty()) {
+            stats_out = std::fopen(stats_path.c_str(), "wb");
+            if (!stats_out) { std::perror("decoder statistics output"); return false; }
+        }
         return true;
     }
     bool add(const int8_t *sym, size_t n)
@@ -185,6 +221,7 @@ struct FrameDecode {
         valid.resize(nw);
         if (xrit_sync_correlate(pending.data(), nw * FRAME, words, 2, FRAME, hits.data(), device) != XRIT_OK) return fail("correlate");
         size_t take = nw;           // windows decoded this round
+        raw_hits.assign(hits.begin(), hits.end());     // the demux takes the phase as the correlator found it
         for (size_t f = 0; f < nw; ++f) {
             if (hrit) hits[f].word = 0;
             if (hits[f].correlation >= MIN_CORRELATION && f * FRAME + hits[f].position + FRAME > pending.size()) { take = f; break; }
@@ -205,9 +242,38 @@ struct FrameDecode {
             if (!info[f].ok) { ++n_dropped; continue; }
             ++n_ok;
             for (int k = 0; k < 4; ++k) rs_corrections += info[f].rs_errors[k] > 0 ? (size_t)info[f].rs_errors[k] : 0;
-            if (std::fwrite(block.data() + f * 1020, 1, VCDU, out) != VCDU) { std::perror("decode output"); return false; }
+            if (out && std::fwrite(block.data() + f * 1020, 1, VCDU, out) != VCDU) { std::perror("decode output"); return false; }
         }
+        if (dm && !demux(take)) return false;
         pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)(take * FRAME));
+        return true;
+    }
+    // ChannelWriter::writeChannel per good frame (newdecoder.cpp:356-360) and the statistics record of every valid frame
+    bool demux(size_t take)
+    {
+        uint32_t off[65];
+        vcdu.resize(take * VCDU);
+        records.resize(take);
+        const xrit_decoder_stats start = dm_stats;
+        if (xrit_demux_process(dm, raw_hits.data(), cadu.data(), block.data(), info.data(), take, vcdu.data(), off,
+                               records.data()) != XRIT_OK || xrit_demux_stats(dm, &dm_stats) != XRIT_OK)
+            return fail("demux");
+        for (int v = 0; !channel_dir.empty() && v < 64; ++v) {
+            if (off[v + 1] == off[v]) continue;
+            const std::string name = channel_dir + "/channel_" + std::to_string(v) + ".bin";
+            FILE *f = std::fopen(name.c_str(), "ab");
+            const size_t bytes = (size_t)(off[v + 1] - off[v]) * VCDU;
+            const bool ok = f && std::fwrite(vcdu.data() + (size_t)off[v] * VCDU, 1, bytes, f) == bytes;
+            if (f) std::fclose(f);
+            if (!ok) { std::perror(name.c_str()); return false; }
+        }
+        if (stats_out) {
+            wire.resize(take * XRIT_STATISTICS_WIRE_BYTES);
+            const int n = xrit_demux_expand(&start, records.data(), take, wire.data());
+            if (n < 0) return fail("statistics");
+            const size_t bytes = (size_t)n * XRIT_STATISTICS_WIRE_BYTES;
+            if (std::fwrite(wire.data(), 1, bytes, stats_out) != bytes) { std::perror("decoder statistics output"); return false; }
+        }
         return true;
     }
     bool fail(const char *what)
@@ -223,8 +289,22 @@ struct FrameDecode {
             xrit_decoder_destroy(dec);
             dec = nullptr;
         }
+        if (dm) {
+            std::fprintf(stderr, "demux: lost packets %lld (", (long long)dm_stats.lost_packets);
+            const char *sep = "";
+            for (int v = 0; v < 64; ++v) {
+                if (dm_stats.received[v] < 0) continue;
+                std::fprintf(stderr, "%svcid %d: %lld of %lld", sep, v, (long long)dm_stats.lost[v], (long long)dm_stats.received[v]);
+                sep = ", ";
+            }
+            std::fprintf(stderr, ")\n");
+            xrit_demux_destroy(dm);
+            dm = nullptr;
+        }
         if (out) std::fclose(out);
         out = nullptr;
+        if (stats_out) std::fclose(stats_out);
+        stats_out = nullptr;
     }
 };
 
@@ -531,7 +611,8 @@ int main(int argc, char **argv)
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
-    if (!o.decode.empty() && !decode.open(o.decode, o.mode == "hrit", o.device)) {
+    if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty()) &&
+        !decode.open(o.decode, o.channels, o.decoder_stats, o.mode == "hrit", o.device)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
