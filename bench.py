@@ -8,7 +8,14 @@ decimation 5 (151-tap Hamming low-pass) -> AGC -> 63-tap RRC (alpha 0.5) -> Cost
 already resident in HBM; consecutive steps are consecutive bursts of one
 continuous stream (loop and filter state carried from step to step, exactly as
 the reference's processSamples() carries it from chunk to chunk,
-/root/reference/demodulator/src/demodulator.cpp:100-168).
+demodulator/src/demodulator.cpp:100-168 of the reference).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what its headline needs and nothing else: it generates the
+bursts, warms up, times the K steps, writes --dump-outputs and prints the line -- `value`, `ms_per_step`, the chain's
+roofline fraction (arithmetic on `ms_per_step`), the loop statistics of the last step and the decimating FIR as the HIP
+events inside the timed region saw it.  Everything that takes runs of its own is behind --full: the per-kernel detail
+pass, the read-only bandwidth sweep, the alternative legs (LEGS) and BASELINE's other configurations in processes of their
+own, the CPU baseline and the parity comparisons against the oracle, the contiguous leg.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); every rank
 demodulates its own independent capture segment (distinct seed) -- the path
@@ -29,7 +36,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (vendor figure)
 DUMP_BYTES = 64_000_000           # --dump-outputs: what DIR holds at most, all ranks together
 DUMP_SEED = 0x58524954
 
@@ -284,6 +291,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--burst-log2", type=int, default=28, help="log2 of samples per burst (28 = 256 Mi)")
     ap.add_argument("--decimation", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else the benchmark measures and checks, each in a run of its own after "
+                         "the timed steps: the per-kernel detail pass and roofline, the read-only bandwidth sweep, the alternative "
+                         "legs, BASELINE's other single-GPU configurations, the CPU baseline, parity against the oracle and, with "
+                         "N > 1 or --contiguous-leg, the contiguous leg.  The --no-* options below take parts of it away again; "
+                         "without --full none of it runs")
     ap.add_argument("--cpu-sample-log2", type=int, default=27, help="log2 of samples timed on the CPU oracle")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
@@ -335,6 +348,9 @@ def main():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.leg:
         return leg_child(args)
+    full = args.full
+    if not full and (args.contiguous_leg or args.legs_in_process):
+        ap.error("--contiguous-leg and --legs-in-process are parts of a --full run")
 
     import torch
     import torch.distributed as dist
@@ -371,8 +387,8 @@ def main():
     K, W = args.steps, args.warmup
     if args.contiguous:
         return bench_contiguous(args, torch, dist, xa, _capi, world, rank, local_rank, dev, n_burst, D, fs_in)
-    detail = not args.no_profile        # a second, untimed set of K steps with every kernel bracketed
-    nb = K + W + (K if detail else 0)
+    detail = full and not args.no_profile        # a second, untimed set of K steps with every kernel bracketed
+    cpu = full and rank == 0 and world == 1 and not args.no_cpu        # the oracle on the host: baseline and parity
 
     # ---- synthetic stream: nb consecutive bursts of this rank's capture segment
     sp = _capi.synth_params(fs_in=fs_in, symbol_rate=sym_rate, alpha=alpha, seed=0x58524954 + 2 * rank)
@@ -392,7 +408,7 @@ def main():
     torch.cuda.synchronize(dev)
     host0 = None
     cpu_threads = args.cpu_threads if args.cpu_threads > 0 else (os.cpu_count() or 1)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if cpu:
         # the CPU baseline's samples, taken before the detail pass reuses the buffers
         n_cpu0 = min(n_burst, 1 << args.cpu_sample_log2)
         # (a whole number of decimation periods: the chain drops n mod D samples per call like the reference,
@@ -542,60 +558,61 @@ def main():
         # per symbol; the walkers read every sample 1 + history / range times)
         "clock_overlap": c8 + 4.0 / (D * sps),
     }
-    roofline = None
     kernels = {}
     alone = locals().get("alone", {})
     chain_gbs = b_alg * n_burst * K / elapsed / 1e9
-    if prof:
-        for name, ms, cnt in prof:
-            avg = ms / cnt
-            k = {"total_ms": round(ms, 4), "launches": cnt, "avg_launch_ms": round(avg, 4),
-                 "measured": ("timed region" + (", under the loops of the previous burst (second stream)" if prefetch else ""))
-                 if name == "fir_decim" else "detail pass"}
-            if name in dec_samples:
-                k["alone"] = dec_samples[name]       # detail pass: one burst at a time, every launch bracketed
-            if name == "fir_decim" and name in alone:
-                k["avg_launch_ms_alone"] = round(alone[name], 4)
-                if name in own_bytes:
-                    k["hbm_frac_alone"] = round(own_bytes[name] * n_burst / (alone[name] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    if not detail:
+        prof = prof_timed          # a plain run: what the events inside the timed region saw (the decimating FIR)
+    for name, ms, cnt in prof:
+        avg = ms / cnt
+        k = {"total_ms": round(ms, 4), "launches": cnt, "avg_launch_ms": round(avg, 4),
+             "measured": ("timed region" + (", under the loops of the previous burst (second stream)" if prefetch else ""))
+             if name == "fir_decim" else "detail pass"}
+        if name in dec_samples:
+            k["alone"] = dec_samples[name]       # detail pass: one burst at a time, every launch bracketed
+        if name == "fir_decim" and name in alone:
+            k["avg_launch_ms_alone"] = round(alone[name], 4)
             if name in own_bytes:
-                gbs = own_bytes[name] * n_burst / (avg * 1e-3) / 1e9
-                k["algorithmic_bytes_per_launch"] = own_bytes[name] * n_burst
-                k["achieved_gbs"] = round(gbs, 1)
-                k["hbm_frac"] = round(gbs / HBM_PEAK_GBS, 4)
-            kernels[name] = k
-        # roofline.achieved is the CHAIN's algorithmic traffic -- (8 + 4/(D*sps)) bytes per input
-        # sample x samples per step / step time -- against the HBM peak; that is the figure BASELINE.json's 0.40
-        # refers to.  The kernel that moves those bytes (the decimating FIR reads every input sample once; without a
-        # decimator the longest single launch) is listed beside it, priced with ITS OWN algorithmic bytes and timed
-        # with HIP events on the launch stream inside the timed region.
-        in_name = "fir_decim" if "fir_decim" in kernels else max(kernels, key=lambda n: kernels[n]["avg_launch_ms"])
-        dom_name = max(prof, key=lambda r: r[1])[0]          # the kernel the step spends most of its time in
-        fd = kernels[dom_name]
-        fi = kernels[in_name]
-        roofline = {"bound": "hbm", "achieved": round(chain_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(chain_gbs / HBM_PEAK_GBS, 4), "traffic": None,
-                    "what": "whole chain: algorithmic_bytes_per_sample x samples per step / ms_per_step",
-                    "algorithmic_bytes_per_step": b_alg * n_burst,
-                    "dominant_kernel": {"kernel": dom_name, "avg_launch_ms": fd["avg_launch_ms"],
-                                        "launches_per_step": fd["launches"] / K,
-                                        "algorithmic_bytes_per_launch": fd.get("algorithmic_bytes_per_launch"),
-                                        "achieved": fd.get("achieved_gbs"), "frac": fd.get("hbm_frac"),
-                                        "measured": fd.get("measured"),
-                                        "avg_launch_ms_alone": fd.get("avg_launch_ms_alone"),
-                                        "frac_alone": fd.get("hbm_frac_alone")},
-                    "dominant_kernel_frac": fd.get("hbm_frac"),
-                    # the kernel that moves the algorithmic bytes (reads every input sample once), priced on its own bytes
-                    "input_kernel": {"kernel": in_name, "avg_launch_ms": fi["avg_launch_ms"],
-                                     "algorithmic_bytes_per_launch": fi.get("algorithmic_bytes_per_launch"),
-                                     "achieved": fi.get("achieved_gbs"), "frac": fi.get("hbm_frac"),
-                                     "measured": fi.get("measured"), "avg_launch_ms_alone": fi.get("avg_launch_ms_alone"),
-                                     "frac_alone": fi.get("hbm_frac_alone")}}
+                k["hbm_frac_alone"] = round(own_bytes[name] * n_burst / (alone[name] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+        if name in own_bytes:
+            gbs = own_bytes[name] * n_burst / (avg * 1e-3) / 1e9
+            k["algorithmic_bytes_per_launch"] = own_bytes[name] * n_burst
+            k["achieved_gbs"] = round(gbs, 1)
+            k["hbm_frac"] = round(gbs / HBM_PEAK_GBS, 4)
+        kernels[name] = k
+
+    def priced(name):
+        """A kernel of `kernels` on its own algorithmic bytes, as the roofline quotes it."""
+        k = kernels[name]
+        return {"kernel": name, "avg_launch_ms": k["avg_launch_ms"],
+                "algorithmic_bytes_per_launch": k.get("algorithmic_bytes_per_launch"),
+                "achieved": k.get("achieved_gbs"), "frac": k.get("hbm_frac"), "measured": k.get("measured"),
+                "avg_launch_ms_alone": k.get("avg_launch_ms_alone"), "frac_alone": k.get("hbm_frac_alone")}
+
+    # SURVEY.md 8(d): roofline.achieved is the CHAIN's algorithmic traffic -- (8 + 4/(D*sps)) bytes per input
+    # sample x samples per step / step time -- against the HBM peak; that is the figure BASELINE.json's 0.40
+    # refers to: arithmetic on ms_per_step, so every run carries it.  The kernel that moves those bytes (the decimating
+    # FIR reads every input sample once; without a decimator the longest single launch, which only the detail pass knows)
+    # is listed beside it, priced with ITS OWN algorithmic bytes and timed with HIP events on the launch stream inside the
+    # timed region.
+    roofline = {"bound": "hbm", "achieved": round(chain_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(chain_gbs / HBM_PEAK_GBS, 4), "traffic": None,
+                "what": "whole chain: algorithmic_bytes_per_sample x samples per step / ms_per_step",
+                "algorithmic_bytes_per_step": b_alg * n_burst}
+    in_name = "fir_decim" if "fir_decim" in kernels else (max(kernels, key=lambda n: kernels[n]["avg_launch_ms"])
+                                                          if detail and kernels else None)
+    if in_name:
+        roofline["input_kernel"] = priced(in_name)
+    if detail and prof:
+        # --full: the kernel the step spends most of its time in, from the detail pass
         tot = max(prof, key=lambda r: r[1])
-        roofline["by_total_time"] = {"kernel": tot[0], "total_ms_per_step": round(tot[1] / K, 4),
-                                     "achieved": kernels[tot[0]].get("achieved_gbs"),
-                                     "frac": kernels[tot[0]].get("hbm_frac"),
-                                     "algorithmic_bytes_per_launch": kernels[tot[0]].get("algorithmic_bytes_per_launch")}
+        dom_name = tot[0]
+        roofline["dominant_kernel"] = {**priced(dom_name), "launches_per_step": kernels[dom_name]["launches"] / K}
+        roofline["dominant_kernel_frac"] = kernels[dom_name].get("hbm_frac")
+        roofline["by_total_time"] = {"kernel": dom_name, "total_ms_per_step": round(tot[1] / K, 4),
+                                     "achieved": kernels[dom_name].get("achieved_gbs"),
+                                     "frac": kernels[dom_name].get("hbm_frac"),
+                                     "algorithmic_bytes_per_launch": kernels[dom_name].get("algorithmic_bytes_per_launch")}
         tpath = os.path.join(HERE, "profiles", "hbm_traffic.json")
         if os.path.exists(tpath) and mode == "lrit" and D == 5:      # the committed PMC passes are C2's
             try:
@@ -615,11 +632,12 @@ def main():
     flops_per_sample = 4.0 * ((dem.decimator_ntaps if D > 1 else 0) + 63) / D + 30.0 / D
     fp32_tflops = flops_per_sample * n_burst * K / elapsed / 1e12
     read_bw = None
-    try:
-        read_bw = _capi.device_read_bandwidth(bursts[0].data_ptr(), n_burst * 8, reps=5, device=local_rank,
-                                              stream=stream.cuda_stream)
-    except Exception:
-        pass
+    if full:
+        try:
+            read_bw = _capi.device_read_bandwidth(bursts[0].data_ptr(), n_burst * 8, reps=5, device=local_rank,
+                                                  stream=stream.cuda_stream)
+        except Exception:
+            pass
 
     out = {
         "metric": "Msamples/s in -> soft-symbols/s out (LRIT 293 ksym/s chain); % HBM roofline",
@@ -651,8 +669,8 @@ def main():
                         "costas_unconverged": st.costas_unconverged, "clock_open_large": st.clock_open_large,
                         "clock_boundaries_at_the_floor": st.clock_unconverged},
     }
-    if roofline:
-        out["roofline"] = roofline
+    out["roofline"] = roofline
+    if kernels:
         out["kernels"] = kernels
 
     # ---- two other configurations beside it, the same stream from its first burst through a second handle each, timed over
@@ -660,7 +678,7 @@ def main():
     # trajectory) and -2 (hand-off passes only).  Not `value`: the headline is the default configuration (no hand-off
     # passes, three relay passes from the timing guess).
     soft0_alt, soft1_alt = {}, {}
-    if rank == 0 and world == 1 and not args.no_exact:
+    if full and rank == 0 and world == 1 and not args.no_exact:
         def cfg_of(**kw):
             return xa.Demodulator.config(mode, fs_in, D, device=local_rank, costas_chain_len=args.costas_chain,
                                          clock_chain_syms=args.clock_chain, **kw)
@@ -694,7 +712,7 @@ def main():
     # configuration -- C5 (configs[4], the "HBM-bound roofline point": 40 Msps, 963 taps, d = 32), C1's chain at burst size
     # (configs[0]'s chain, 2^28 samples at the circuit rate), C3 (configs[2], HRIT) -- the same timed region as `value` with
     # fewer steps; parity against the oracle on the first 2^25 samples of the cold-started burst.  Never `value`.
-    if (rank == 0 and world == 1 and not args.no_other_configs and (mode, D) == ("lrit", 5) and args.burst_log2 == 28
+    if (full and rank == 0 and world == 1 and not args.no_other_configs and (mode, D) == ("lrit", 5) and args.burst_log2 == 28
             and args.front_exact == 0):
         cfgs = {"C5": ["--decimation", "32", "--steps", "8", "--warmup", "4"],
                 "C1": ["--decimation", "1", "--steps", "5", "--warmup", "3"],
@@ -703,7 +721,7 @@ def main():
                 "C5, parity mode": ["--decimation", "32", "--steps", "5", "--warmup", "3", "--front-exact", "2"],
                 "C1, parity mode": ["--decimation", "1", "--steps", "4", "--warmup", "3", "--front-exact", "2"],
                 "C3, parity mode": ["--mode", "hrit", "--decimation", "1", "--steps", "4", "--warmup", "3", "--front-exact", "2"]}
-        common = ["--no-exact", "--no-other-configs", "--no-serial-floor", "--no-profile", "--cpu-sample-log2", "25", "--cpu-threads", "1"]
+        common = ["--full", "--no-exact", "--no-other-configs", "--no-serial-floor", "--no-profile", "--cpu-sample-log2", "25", "--cpu-threads", "1"]
         res = run_children([v + common for v in cfgs.values()], 240)
         out["other_configs"] = {}
         for key, (rc, so_, se_) in zip(cfgs, res):
@@ -725,7 +743,7 @@ def main():
 
     # ---- CPU baseline: the oracle (a CPU restatement; the reference binary cannot be built here) on a
     # bounded sample of the same workload, one thread like the reference's DSP thread.
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if cpu:
         import oracle
         n_cpu = len(host0)
         host = host0
@@ -829,7 +847,7 @@ def main():
     # slices through xrit_group_process_slice_device (a second timed region, LAST: `value` above is the independent-segments
     # figure and is complete by now).  A watchdog keeps a stuck collective from taking the headline with it: on expiry rank 0
     # prints the line it has, with the reason, and every rank leaves.
-    if (world > 1 and not share) or (args.contiguous_leg and world == 1):
+    if full and ((world > 1 and not share) or (args.contiguous_leg and world == 1)):
         import threading
 
         def give_up():
@@ -847,7 +865,7 @@ def main():
         except Exception as e:      # (a failure of one rank reaches every rank through the group's all-gathers)
             out["contiguous"] = {"error": "%s: %s" % (type(e).__name__, e)}
         dog.cancel()
-    elif world > 1:
+    elif full and world > 1:
         out["contiguous"] = {"skipped": "the ranks share a device and meet over gloo (XRIT_BENCH_SHARE_DEVICE): RCCL refuses two ranks on one GPU"}
     if rank == 0:
         print(json.dumps(out))

@@ -7,7 +7,7 @@ cp xritdemod_amd/lib/libxritdemod_amd.so /tmp/lib_orig.so
 for v in xritdemod_amd/lib/ab/*.so; do
   cp $v xritdemod_amd/lib/libxritdemod_amd.so
   for rep in 1 2; do
-  python bench.py --steps 20 --warmup 4 --no-cpu --no-serial-floor "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 4 --no-cpu --no-serial-floor "$@" 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['kernels']

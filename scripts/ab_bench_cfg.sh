@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 ARGS="$1"; shift
 for cfg in "$@"; do
-  env $cfg python bench.py $ARGS --steps 8 --warmup 3 --no-cpu --no-exact 2>/dev/null | python -c "
+  env $cfg python bench.py --full $ARGS --steps 8 --warmup 3 --no-cpu --no-exact 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']; p = d.get('parity_vs_oracle') or {}

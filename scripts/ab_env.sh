@@ -9,7 +9,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do vars+=("$1"); shift; done
 for rep in 1 2; do
   for v in "${vars[@]}"; do
     if [ "$v" = "-" ]; then e=(); else e=($v); fi
-    env "${e[@]}" python bench.py --steps 20 --warmup 4 --no-cpu --no-serial-floor "$@" 2>/dev/null | python -c "
+    env "${e[@]}" python bench.py --full --steps 20 --warmup 4 --no-cpu --no-serial-floor "$@" 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['kernels']

@@ -1,6 +1,6 @@
 #!/bin/bash
 # prints per-kernel ms/step from bench.py (dev aid)
-python bench.py --steps 3 --warmup 2 --no-cpu "$@" 2>&1 | tail -1 | python -c "
+python bench.py --full --steps 3 --warmup 2 --no-cpu "$@" 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('Msps',d['value'],'ms/step',d['ms_per_step'],d['loop_passes'],'chain_frac',d['roofline']['chain_frac'])

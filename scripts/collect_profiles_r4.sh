@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err      # (the driver's command)
-python bench.py --no-prefetch --no-cpu --no-exact > $OUT/bench_c2_noprefetch.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err      # (the standard command, with everything beside the headline)
+python bench.py --full --no-prefetch --no-cpu --no-exact > $OUT/bench_c2_noprefetch.json 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
 # kernel statistics over 20 streamed steps (beside), and one burst at a time (alone)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o c2 -- python $R/bench.py --steps 20 --warmup 4 --no-cpu --no-profile --no-exact > $OUT/stats.log 2>&1
@@ -23,7 +23,7 @@ cp gpurun_out/streamed_timeline.txt $OUT/timeline_streamed.txt
 python scripts/small_call_latency.py 2>&1 | grep "^D=" > $OUT/small_calls.txt
 for cfg in "c5:--decimation 32" "c3:--mode hrit --decimation 1" "c1:--decimation 1"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  python $R/bench.py $args > $OUT/bench_$name.json 2> /dev/null
+  python $R/bench.py --full $args > $OUT/bench_$name.json 2> /dev/null
 done
 # keep what the summariser reads, drop the raw traces (tens of MB)
 find $OUT -name "*_kernel_trace.csv" -delete

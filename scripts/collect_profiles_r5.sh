@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err      # (the driver's command)
-python bench.py --no-prefetch --no-cpu --no-exact > $OUT/bench_c2_noprefetch.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err      # (the standard command, with everything beside the headline)
+python bench.py --full --no-prefetch --no-cpu --no-exact > $OUT/bench_c2_noprefetch.json 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
 # kernel statistics over 20 streamed steps (beside), and one burst at a time (alone)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o c2 -- python $R/bench.py --steps 20 --warmup 5 --no-cpu --no-profile --no-exact > $OUT/stats.log 2>&1
@@ -24,7 +24,7 @@ python scripts/r5_step_times.py --steps 19 > $OUT/step_times_c2.json 2> /dev/nul
 python scripts/small_call_latency.py 2>&1 | grep "^D=" > $OUT/small_calls.txt
 for cfg in "c5:--decimation 32" "c3:--mode hrit --decimation 1" "c1:--decimation 1"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  python $R/bench.py --steps 20 --warmup 5 $args > $OUT/bench_$name.json 2> /dev/null
+  python $R/bench.py --full --steps 20 --warmup 5 $args > $OUT/bench_$name.json 2> /dev/null
   ( cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$name -o $name -- python $R/bench.py --steps 20 --warmup 5 --no-cpu --no-profile --no-exact --no-serial-floor $args > $OUT/stats_$name.log 2>&1 )
 done
 # keep what the summariser reads, drop the raw traces (tens of MB)

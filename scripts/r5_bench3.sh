@@ -2,7 +2,8 @@
 # bench.py at the BASELINE configurations (driver's command), short summaries.  Usage: scripts/r5_bench3.sh TAG [cases...] [-- extra bench args]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=$1; shift
-mkdir -p $R/gpurun_out/$TAG
+OUT=${OUT:-$R/bench_out}/$TAG
+mkdir -p $OUT
 CASES=""
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do CASES="$CASES $1"; shift; done
 [ "$1" == "--" ] && shift
@@ -14,13 +15,13 @@ for c in $CASES; do
     c1) A="--decimation 1";;
     c3) A="--decimation 1 --mode hrit";;
   esac
-  python $R/bench.py --steps 20 --warmup 5 --no-exact --no-cpu --no-serial-floor $A "$@" > $R/gpurun_out/$TAG/bench_$c.json 2> $R/gpurun_out/$TAG/bench_$c.err
+  python $R/bench.py --full --steps 20 --warmup 5 --no-exact --no-cpu --no-serial-floor $A "$@" > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   python - <<PY
 import json
 try:
-    d=json.loads(open("$R/gpurun_out/$TAG/bench_$c.json").read().strip().splitlines()[-1])
+    d=json.loads(open("$OUT/bench_$c.json").read().strip().splitlines()[-1])
     print("$c", d["value"], d["ms_per_step"], d["roofline"]["frac"], d["loop_passes"]["clock_relay_segments"], {k:v.get("avg_launch_ms") for k,v in d.get("kernels",{}).items() if k in ("fir_decim","fir_rrc","clock_overlap","clock_relay","costas_final","costas_pass")})
 except Exception as e:
-    print("$c failed", e); print(open("$R/gpurun_out/$TAG/bench_$c.err").read()[-1500:])
+    print("$c failed", e); print(open("$OUT/bench_$c.err").read()[-1500:])
 PY
 done

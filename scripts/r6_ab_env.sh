@@ -1,13 +1,14 @@
 #!/bin/bash
 # round 6: bench.py --front-exact 2 (C2 unless other flags are given) under a list of environment settings, 10 steps each;
 # prints ms per step and the exact kernels' times.   usage: scripts/r6_ab_env.sh "A=1" "B=2 C=3" ...  ("-" = no setting)
-mkdir -p gpurun_out/r6_ab
+OUT=${OUT:-bench_out}/r6_ab
+mkdir -p $OUT
 i=0
 for e in "$@"; do
   i=$((i+1))
   envs=""; [ "$e" != "-" ] && envs="$e"
-  env $envs timeout 600 python bench.py --front-exact 2 --no-exact --no-cpu --no-serial-floor --steps 10 --warmup 4 $BENCH_FLAGS > gpurun_out/r6_ab/b$i.json 2> gpurun_out/r6_ab/b$i.err || tail -3 gpurun_out/r6_ab/b$i.err
-  python - "$e" gpurun_out/r6_ab/b$i.json <<'PY'
+  env $envs timeout 600 python bench.py --full --front-exact 2 --no-exact --no-cpu --no-serial-floor --steps 10 --warmup 4 $BENCH_FLAGS > $OUT/b$i.json 2> $OUT/b$i.err || tail -3 $OUT/b$i.err
+  python - "$e" $OUT/b$i.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 # usage: scripts/r6_bench_modes.sh <front_exact> <outdir> [extra bench.py flags]
 FE=${1:-2}; OUT=gpurun_out/${2:-r6_fe}; shift; shift
 mkdir -p $OUT
-run() { name=$1; shift; timeout 900 python bench.py --front-exact $FE --no-exact "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || tail -5 $OUT/bench_$name.err; }
+run() { name=$1; shift; timeout 900 python bench.py --full --front-exact $FE --no-exact "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || tail -5 $OUT/bench_$name.err; }
 run c2 --decimation 5 --steps 10 --warmup 4 "$@"
 run c5 --decimation 32 --steps 10 --warmup 4 "$@"
 run c1 --decimation 1 --steps 6 --warmup 3 "$@"

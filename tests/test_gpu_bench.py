@@ -1,4 +1,5 @@
-"""GPU tier: bench.py's contract on the box -- the one-line JSON of a 1-rank run, and the driver's N > 1 launch
+"""GPU tier: bench.py's contract on the box -- the one-line JSON of a 1-rank run, plain (the headline and what it needs, nothing
+else) and with --full (everything else the benchmark measures, in runs of their own), and the N > 1 launch
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`) with two ranks that share the box's one device
 (XRIT_BENCH_SHARE_DEVICE=1: gloo for the barrier and the reductions, RCCL refuses two ranks on one device; every rank
 still demodulates its own capture segment on the GPU, the timing is the max over ranks, the value the sum)."""
@@ -12,6 +13,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--steps", "3", "--warmup", "2", "--burst-log2", "24", "--no-cpu", "--no-exact", "--no-serial-floor"]
+# what only a --full run measures: never in the line of a plain one
+FULL_ONLY = {"cpu_baseline", "parity_vs_oracle", "other_configs", "contiguous", "parity_mode", "warm_mode", "exact_mode", "fast_mode",
+             "quick_mode"}
 
 
 def _last_json(out):
@@ -38,19 +42,55 @@ def test_bench_line_of_one_rank():
     _check_line(_last_json(r.stdout), 1)
 
 
+def test_full_is_an_option_and_its_parts_need_it():
+    """No GPU: --full is there, and the options that only add to a --full run say so when given without it (the arguments are
+    checked before anything touches a device)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stdout + r.stderr
+    for opt in ("--contiguous-leg", "--legs-in-process"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, (opt, r.returncode, r.stderr[-500:])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean():
+    """The command every change is measured with, at the headline's own size (C2, 256 Mi samples per step), with none of the
+    --no-* options: its line carries the headline, the chain's roofline fraction and the decimating FIR as the timed region's
+    events saw it -- nothing that takes a run of its own -- and the whole process, start to exit, spends at most 30 s outside
+    its warm-up and timed steps."""
+    import time
+    K, W = 10, 4
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W)],
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == K and d["warmup"] == W and d["value"] > 0 and d["ms_per_step"] > 0
+    assert not FULL_ONLY & set(d), sorted(FULL_ONLY & set(d))
+    assert d["read_bw_measured_gbs"] is None
+    assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1
+    assert "dominant_kernel" not in d["roofline"] and "by_total_time" not in d["roofline"]
+    assert set(d["kernels"]) == {"fir_decim"} and d["kernels"]["fir_decim"]["measured"].startswith("timed region"), d["kernels"]
+    assert d["kernels"]["fir_decim"]["launches"] == K and d["roofline"]["input_kernel"]["kernel"] == "fir_decim"
+    outside = wall - (K + W) * d["ms_per_step"] * 1e-3
+    print("plain run: %.1f s from start to exit, %.1f s of them outside its %d steps" % (wall, outside, K + W))
+    assert outside <= 30.0, (wall, d["ms_per_step"])
+
+
 CONTIG_KEYS = {"value", "unit", "steps", "ms_per_step", "halo_samples", "halo_bytes_per_boundary", "rccl_ranks", "polarity_flips",
                "symbols_per_s", "samples_per_step_per_gpu"}
 
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_contiguous_leg_over_rccl():
-    """With N > 1 the driver's command times a second region through xrit_group_process_slice_device (ONE stream cut in N
+    """With N > 1 a --full run times a second region through xrit_group_process_slice_device (ONE stream cut in N
     slices, RCCL edge-sample exchange: BASELINE config 4) and reports it as `contiguous` in the same JSON line; `value` stays the
     independent-segments figure.  One GPU allows an RCCL communicator of ONE rank: --contiguous-leg runs that leg at N = 1, so the
     schema, ncclCommCount and the group path are covered here (two ranks on one device: the in-process fabric tests of
     test_gpu_parity.py)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--contiguous-leg"] + SMALL, capture_output=True, text=True,
-                       timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--contiguous-leg"] + SMALL, capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_line(d, 1)
@@ -70,7 +110,7 @@ def test_bench_two_ranks_launched_like_the_driver_does():
         port = s.getsockname()[1]
     env = dict(os.environ, XRIT_BENCH_SHARE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -164,11 +204,11 @@ def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_alternative_legs_run_in_processes_of_their_own():
-    """Round 6: parity_mode (cfg.front_exact = 2), exact_mode, fast_mode, quick_mode are each a fresh process of bench.py (--leg):
+    """Round 6, --full: parity_mode (cfg.front_exact = 2), exact_mode, fast_mode, quick_mode are each a fresh process of bench.py (--leg):
     what a handle's bursts take depends on the hardware queues HIP deals its streams onto, which depends on what the process
     created before.  The parent collects their results and their soft symbols for the parity comparison."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--burst-log2", "24",
-                        "--cpu-sample-log2", "22", "--cpu-threads", "1"], capture_output=True, text=True, timeout=900)
+                        "--cpu-sample-log2", "22", "--cpu-threads", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     _check_line(d, 1)
@@ -179,6 +219,9 @@ def test_bench_alternative_legs_run_in_processes_of_their_own():
     assert pv["parity_mode"]["sign_mismatches"] == 0 and pv["parity_mode"]["rms"] <= 1e-4, pv["parity_mode"]
     assert pv["exact_mode"]["words_differing_from_serial_gpu"] == 0
     assert "other_configs" not in d          # (only beside the headline workload: C2 at the full burst size)
+    # ... and the rest of what --full adds: the oracle on the host, the read-only sweep, the per-kernel pass
+    assert d["cpu_baseline"]["value"] > 0 and d["read_bw_measured_gbs"] > 0
+    assert "dominant_kernel" in d["roofline"] and len(d["kernels"]) > 1
 
 
 @pytest.mark.gpu

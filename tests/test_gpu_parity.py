@@ -1658,7 +1658,10 @@ def test_host_program_output_locks_in_the_decoder(xa, tmp_path):
 
 class _ThreadComm:
     """Two 'ranks' as two threads of this process sharing the one GPU: the send / recv / all_gather calls of
-    tests/dist_twin.py with queues in place of RCCL (a 1-GPU box cannot host two nccl ranks)."""
+    tests/dist_twin.py with queues in place of RCCL (a 1-GPU box cannot host two nccl ranks).  Every thread works on a
+    stream of its own, and a queue or a barrier orders the threads, not the streams: a tensor is complete on its sender's
+    stream before the other thread is handed it (_handed), or the receiver's copy -- on another stream -- may read the
+    block before the clone has filled it and take what an earlier test left there."""
 
     def __init__(self, world):
         import queue
@@ -1676,18 +1679,27 @@ class _ThreadComm:
         def wait(self):
             pass
 
+    @staticmethod
+    def _handed(t):
+        import torch
+        c = t.clone()
+        torch.cuda.current_stream(c.device).synchronize()
+        return c
+
     def isend(self, t, dst):
-        self.q[(self.local.rank, dst)].put(t.clone())
+        self.q[(self.local.rank, dst)].put(self._handed(t))
         return self._Done()
 
     def recv(self, t, src):
         t.copy_(self.q[(src, self.local.rank)].get(timeout=120))
 
     def all_gather(self, out, mine):
-        self.slots[self.local.rank] = mine.clone()
+        self.slots[self.local.rank] = self._handed(mine)
         self.bar.wait()
         for i in range(self.world):
             out[i].copy_(self.slots[i])
+        import torch
+        torch.cuda.current_stream(mine.device).synchronize()      # (the slots are overwritten by the next call)
         self.bar.wait()
 
 
@@ -1719,19 +1731,27 @@ def test_contiguous_split_on_device(xa, same_lock):
         res = [None, None]
 
         def work(rank):
-            comm.bind(rank)
-            torch.cuda.set_device(0)
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                out, off = xd.demodulate_contiguous_device(lambda: xa.Demodulator(cfg()), whole[rank * n:(rank + 1) * n], comm,
-                                                           rank, 2, halo, same_lock=same_lock, stream=s.cuda_stream)
-                res[rank] = (off, out.cpu().numpy())
+            try:
+                comm.bind(rank)
+                torch.cuda.set_device(0)
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
+                    out, off = xd.demodulate_contiguous_device(lambda: xa.Demodulator(cfg()), whole[rank * n:(rank + 1) * n], comm,
+                                                               rank, 2, halo, same_lock=same_lock, stream=s.cuda_stream)
+                    res[rank] = (off, out.cpu().numpy())
+            except BaseException as e:      # (said by the test, not lost with the thread; the other rank must not wait for this one)
+                res[rank] = e
+                comm.bar.abort()
 
         th = [threading.Thread(target=work, args=(r,)) for r in range(2)]
         for t in th:
             t.start()
         for t in th:
             t.join(timeout=300)
+        errs = [r for r in res if isinstance(r, BaseException)]
+        if errs:      # (the rank that failed first, not the one whose barrier it broke)
+            raise ([e for e in errs if not isinstance(e, threading.BrokenBarrierError)] or errs)[0]
+        assert None not in res, "a rank did not finish within 300 s: %s" % [r is not None for r in res]
         (o0, s0), (o1, s1) = res
         got = np.concatenate([s0, s1])
         if not (o0 == 0 and o1 == len(s0) and len(got) == len(ref)):
