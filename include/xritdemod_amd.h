@@ -478,6 +478,85 @@ int xrit_demux_stats(xrit_demux *dm, xrit_decoder_stats *out);
 int xrit_demux_expand(const xrit_decoder_stats *start, const xrit_frame_stats *records, size_t nf, uint8_t *out);
 
 /* ------------------------------------------------------------------------
+ * Packet assembler: CCSDS space packets (the LRIT/HRIT CP_PDUs) out of the
+ * demultiplexer's VCDU rows, with CRC.  The reference decoder ends at the VCDU,
+ * so there is no reference line to cite: the layout is taken from the CCSDS
+ * AOS space data link recommendation (CCSDS 732.0-B: the M_PDU, its first
+ * header pointer, 2047 = no header, 2046 = idle data), the space packet
+ * recommendation (CCSDS 133.0-B: the 6-byte primary header, APID 2047 = idle
+ * packet) and the LRIT/HRIT global specification (CGMS 03: the CP_PDU's
+ * CRC-16 over its data field).  Exact integer contract: DESIGN.md "Packet
+ * assembler"; tests/packet_spec.py is the serial statement of it.
+ *  - input: the demux's vcdu rows (892 bytes, grouped by VCID) and offsets[65].
+ *    Channel 63 (fill VCDUs) is ignored.  In a row r: counter = r[2..5) big
+ *    endian, fhp = (r[6] & 7) << 8 | r[7], packet zone = r[8..892).
+ *  - per channel, carried across calls until reset: the last row's counter and
+ *    the bytes of a packet that has begun and not ended.  A break in the
+ *    counters drops that partial packet; the first header pointer is
+ *    authoritative (what it contradicts is dropped, never re-interpreted).
+ *  - a finished packet of APID 2047 is counted and not emitted; every other one
+ *    is emitted whole (header included) with one xrit_packet descriptor.
+ *    crc_ok = 1 iff length >= 8 and the big-endian 16 bits in its last two
+ *    bytes are CRC-16/CCITT-FALSE (0x1021, initial value 0xFFFF, MSB first) of
+ *    packet[6 .. length - 2).  A packet that fails is still emitted.
+ *  - output order: VCID ascending, stream order within a VCID.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_packets xrit_packets;
+typedef struct xrit_packet {
+    uint64_t offset;                 /* of the packet's first byte in the call's byte buffer */
+    uint32_t length;                 /* 7 + the header's length field: primary header included (7 .. 65542) */
+    uint32_t first_counter;          /* VCDU counter of the row the packet began in */
+    uint16_t apid;                   /* (h[0] & 7) << 8 | h[1] */
+    uint16_t seq_count;              /* (h[2] & 0x3F) << 8 | h[3] */
+    uint16_t crc_computed;           /* 0 when length < 8 */
+    uint16_t crc_carried;            /* the last two bytes, big endian; 0 when length < 8 */
+    uint8_t  vcid;
+    uint8_t  seq_flags;              /* h[2] >> 6 */
+    uint8_t  crc_ok;
+    uint8_t  header_bits;            /* h[0] >> 3: version, type, secondary header flag, not interpreted */
+    uint8_t  reserved[4];
+} xrit_packet;                       /* 32 bytes */
+typedef struct xrit_packets_summary {
+    uint64_t packets, bytes;         /* emitted by this call: the true counts, whatever the capacities */
+    uint64_t total_packets, crc_failures, fill_packets, discarded, bad_fhp, rows;   /* the handle's counters after it */
+    uint32_t overflow;               /* 0; 1: max_packets or max_bytes too small; 2: d_offsets[64] > max_rows */
+    uint32_t reserved;
+} xrit_packets_summary;              /* 72 bytes */
+typedef struct xrit_packets_counters {
+    uint64_t packets, crc_failures, fill_packets, discarded, bad_fhp, rows;         /* all channels */
+    uint64_t vc_packets[64], vc_crc_failures[64], vc_fill_packets[64], vc_discarded[64], vc_bad_fhp[64], vc_rows[64];
+    int64_t  last_counter[64];       /* -1 until a channel's first row */
+    uint32_t pending_bytes[64];      /* bytes held of a packet that has begun and not ended (0 .. 65541) */
+    uint32_t pending_first_counter[64];
+} xrit_packets_counters;             /* 4144 bytes */
+/* the bytes of a call never exceed this */
+#define XRIT_PACKETS_MAX_BYTES(rows) ((size_t)884 * (rows) + (size_t)65541 * 64)
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_packets_create(xrit_packets **pa, int device);
+int xrit_packets_destroy(xrit_packets *pa);
+/* every channel back to its start (no last counter, nothing pending, counters zero); waits for the handle's last call */
+int xrit_packets_reset(xrit_packets *pa);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_demux_process_device, which hands it its row count in d_offsets[64] on the device.  max_rows (<= 2^24)
+ * is the host's bound on that count (the demux call's nf): launches and scratch are sized from it; a larger
+ * d_offsets[64] raises overflow = 2 in the summary and nothing else is written, the state unchanged.
+ * d_bytes: max_bytes; d_packets: max_packets descriptors, 8-byte aligned; d_pkt_offsets: 65 entries, the exclusive
+ * prefix of the per-channel packet counts; d_summary: 8-byte aligned.  Capacity: descriptor k is written iff
+ * k < max_packets, a packet's bytes iff offset + length <= max_bytes; the summary carries the true counts and
+ * overflow = 1, and the handle's state advances as if everything had fitted.
+ * Calls on one handle share its state and scratch: keep them in order. */
+int xrit_packets_process_device(xrit_packets *pa, const uint8_t *d_vcdu, const uint32_t *d_offsets, size_t max_rows,
+                                uint8_t *d_bytes, size_t max_bytes, xrit_packet *d_packets, size_t max_packets,
+                                uint32_t *d_pkt_offsets, xrit_packets_summary *d_summary, void *stream);
+/* host buffers (one upload, one download); the rows are offsets[64].  XRIT_E_CAPACITY when a capacity was too small:
+ * the prefix that fits is written, summary and pkt_offsets are the true ones, the state has advanced. */
+int xrit_packets_process(xrit_packets *pa, const uint8_t *vcdu, const uint32_t *offsets, uint8_t *bytes, size_t max_bytes,
+                         xrit_packet *packets, size_t max_packets, uint32_t *pkt_offsets, xrit_packets_summary *summary);
+/* the full counters after the handle's last call (waits for it) */
+int xrit_packets_stats(xrit_packets *pa, xrit_packets_counters *out);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

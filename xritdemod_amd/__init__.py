@@ -16,4 +16,5 @@ from ._capi import (  # noqa: F401
     loop_sincosf, SynthParams as DeviceSynthParams, synth_generate_device, quantize_i8_device, sync_correlate, sync_correlate_device, sync_fix_frames, sync_fix_frames_device,
     LRIT_UW0, LRIT_UW2, HRIT_UW0, HRIT_UW2, FrameDecoder, FRAME_INFO_DTYPE, CADU_SIZE, BLOCK_SIZE, VCDU_SIZE,
     ChannelDemux, FRAME_STATS_DTYPE, DECODER_STATS_DTYPE, STATISTICS_WIRE_BYTES, N_VCID,
+    PacketAssembler, PACKET_DTYPE, PACKETS_SUMMARY_DTYPE, PACKETS_STATS_DTYPE, packets_max_bytes,
 )

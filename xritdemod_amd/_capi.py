@@ -101,6 +101,12 @@ _SIGNATURES = {
     "xrit_demux_process": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "xrit_demux_stats": (C.c_int, [_vp, _vp]),
     "xrit_demux_expand": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "xrit_packets_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_packets_destroy": (C.c_int, [_vp]),
+    "xrit_packets_reset": (C.c_int, [_vp]),
+    "xrit_packets_process_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "xrit_packets_process": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "xrit_packets_stats": (C.c_int, [_vp, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -828,3 +834,111 @@ class ChannelDemux(_Handle):
     def reset(self):
         """The start state of newdecoder.cpp:133-137 (startTime is kept)."""
         _check(lib().xrit_demux_reset(self._h))
+
+
+# ---- packet assembler: CCSDS space packets out of the demultiplexed VCDUs, with CRC (DESIGN.md section 14) -----------
+# xrit_packet: one descriptor per emitted packet
+PACKET_DTYPE = np.dtype([
+    ("offset", np.uint64), ("length", np.uint32), ("first_counter", np.uint32),
+    ("apid", np.uint16), ("seq_count", np.uint16), ("crc_computed", np.uint16), ("crc_carried", np.uint16),
+    ("vcid", np.uint8), ("seq_flags", np.uint8), ("crc_ok", np.uint8), ("header_bits", np.uint8),
+    ("reserved", np.uint8, (4,))])
+assert PACKET_DTYPE.itemsize == 32
+
+# xrit_packets_summary: a call's true counts and the handle's counters after it
+PACKETS_SUMMARY_DTYPE = np.dtype([
+    ("packets", np.uint64), ("bytes", np.uint64),
+    ("total_packets", np.uint64), ("crc_failures", np.uint64), ("fill_packets", np.uint64), ("discarded", np.uint64),
+    ("bad_fhp", np.uint64), ("rows", np.uint64), ("overflow", np.uint32), ("reserved", np.uint32)])
+assert PACKETS_SUMMARY_DTYPE.itemsize == 72
+
+# xrit_packets_counters: the full counters, per channel included
+PACKETS_STATS_DTYPE = np.dtype([
+    ("packets", np.uint64), ("crc_failures", np.uint64), ("fill_packets", np.uint64), ("discarded", np.uint64),
+    ("bad_fhp", np.uint64), ("rows", np.uint64),
+    ("vc_packets", np.uint64, (64,)), ("vc_crc_failures", np.uint64, (64,)), ("vc_fill_packets", np.uint64, (64,)),
+    ("vc_discarded", np.uint64, (64,)), ("vc_bad_fhp", np.uint64, (64,)), ("vc_rows", np.uint64, (64,)),
+    ("last_counter", np.int64, (64,)), ("pending_bytes", np.uint32, (64,)), ("pending_first_counter", np.uint32, (64,))])
+assert PACKETS_STATS_DTYPE.itemsize == 4144
+
+PACKET_ZONE = 884                    # bytes of M_PDU packet zone in a VCDU
+PACKET_MAX = 65542                   # the longest space packet, primary header included
+
+
+def packets_max_bytes(rows):
+    """No call on `rows` rows emits more bytes than this (XRIT_PACKETS_MAX_BYTES)."""
+    return PACKET_ZONE * rows + (PACKET_MAX - 1) * N_VCID
+
+
+class PacketAssembler(_Handle):
+    """CCSDS space packets (the LRIT/HRIT CP_PDUs) out of ChannelDemux's rows: per channel the M_PDU first header
+    pointer is followed, a packet under which a VCDU was lost is dropped, every other one is emitted whole with its
+    CRC-16 checked.  What has begun and not ended is carried across calls until reset()."""
+    _destroy = "xrit_packets_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_packets_create(C.byref(self._h), device))
+
+    def process(self, vcdu, offsets, max_packets=None, max_bytes=None):
+        """vcdu (n, 892) uint8 and offsets (65,) uint32 as ChannelDemux.process returns them.  -> (bytes uint8: the
+        emitted packets back to back, VCID ascending, stream order within a VCID; packets (n_packets,) PACKET_DTYPE;
+        pkt_offsets (65,) uint32: channel v's packets are pkt_offsets[v]:pkt_offsets[v + 1]; summary, a
+        PACKETS_SUMMARY_DTYPE record).  With capacities that turn out too small XritError -5 is raised; its `partial`
+        holds the same four with the prefix that fitted (the handle's state has advanced all the same)."""
+        offsets = np.ascontiguousarray(offsets, np.uint32).reshape(N_VCID + 1)
+        rows = int(offsets[N_VCID])
+        vcdu = np.ascontiguousarray(vcdu, np.uint8).reshape(-1, VCDU_SIZE)
+        if len(vcdu) < rows:
+            raise ValueError("offsets[64] counts more rows than vcdu holds")
+        cap_b = packets_max_bytes(rows) if max_bytes is None else int(max_bytes)
+        cap_p = 127 * rows + N_VCID if max_packets is None else int(max_packets)
+        buf = np.empty(max(cap_b, 1), np.uint8)              # (untouched pages cost nothing)
+        desc = np.empty(max(cap_p, 1), PACKET_DTYPE)
+        pkt_offsets = np.zeros(N_VCID + 1, np.uint32)
+        summary = np.zeros(1, PACKETS_SUMMARY_DTYPE)
+        rc = lib().xrit_packets_process(self._h, _p(vcdu), _p(offsets), _p(buf), cap_b, _p(desc), cap_p, _p(pkt_offsets),
+                                        _p(summary))
+        if rc not in (0, -5):
+            _check(rc)
+        n = min(int(summary[0]["packets"]), cap_p)
+        desc = desc[:n].copy()
+        if int(summary[0]["bytes"]) <= cap_b:
+            nb = int(summary[0]["bytes"])
+        else:                                                # whole packets only: up to the end of the last one that fits
+            ends = desc["offset"] + desc["length"]
+            ends = ends[ends <= cap_b]
+            nb = int(ends[-1]) if len(ends) else 0
+        out = (buf[:nb].copy(), desc, pkt_offsets, summary[0])
+        if rc != 0:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            err.partial = out
+            raise err
+        return out
+
+    def process_device(self, d_vcdu_ptr, d_offsets_ptr, max_rows, d_bytes_ptr, max_bytes, d_packets_ptr, max_packets,
+                       d_pkt_offsets_ptr, d_summary_ptr, stream=None):
+        """Device pointers (vcdu rows of 892 bytes and offsets 65 x 4 as ChannelDemux.process_device wrote them, bytes
+        max_bytes, packets max_packets x 32, pkt_offsets 65 x 4, summary 72 bytes), asynchronous on stream; may be
+        queued behind ChannelDemux.process_device: the row count is read from offsets[64] on the device, max_rows is
+        the host's bound on it (that call's nf)."""
+        _check(lib().xrit_packets_process_device(self._h, C.c_void_p(d_vcdu_ptr), C.c_void_p(d_offsets_ptr), max_rows,
+                                                 C.c_void_p(d_bytes_ptr), max_bytes, C.c_void_p(d_packets_ptr),
+                                                 max_packets, C.c_void_p(d_pkt_offsets_ptr), C.c_void_p(d_summary_ptr),
+                                                 C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def split(data, packets):
+        """The packets of one call as a list of bytes objects, in order."""
+        raw = np.asarray(data, np.uint8).tobytes()
+        return [raw[int(o):int(o) + int(n)] for o, n in zip(packets["offset"], packets["length"])]
+
+    def stats(self):
+        """The counters after the last call (a PACKETS_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, PACKETS_STATS_DTYPE)
+        _check(lib().xrit_packets_stats(self._h, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Every channel back to its start: no last counter, nothing pending, counters zero."""
+        _check(lib().xrit_packets_reset(self._h))

@@ -460,6 +460,31 @@ struct DemuxScratch {
 int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,
                  const xrit_frame_info *info, size_t nf, DemuxState *state, DemuxScratch &sc, unsigned char *vcdu,
                  unsigned *offsets, xrit_frame_stats *records, hipStream_t s);
+// packet assembler (packets.hip): the handle's state, the per-call scratch (R = max(max_rows, 1) rows)
+constexpr unsigned PACKETS_PEND_MAX = 65541;        // a pending packet is shorter than the longest packet (65542)
+constexpr unsigned PACKETS_TILE = 1024;             // rows per tile of the scan
+constexpr unsigned PACKETS_PEND_STRIDE = 65544;     // bytes of pending buffer per channel
+struct PacketsState {
+    unsigned long long packets[64], crc_failures[64], fill_packets[64], discarded[64], bad_fhp[64], rows[64];
+    int last[64];                                   // the last row's counter, -1 at start
+    unsigned pend_len[64], first_counter[64];       // the bytes held in the channel's pending buffer, where they began
+};
+struct PacketsScratch {
+    unsigned *rowA;                 // [R] per row, by its own lane: packets inside | fill << 8 | bytes << 16 | discarded << 28 | bad << 29
+    uint2 *spanB;                   // [R] per row, by the lane of the tail that ends here: (origin, length | fill << 31)
+    uint2 *newp;                    // [64] per channel: (origin, bytes) of what is pending after the call
+    unsigned *state_disc;           // [64] the pending state the call began with was discarded
+    unsigned *plocal, *blocal;      // [R] descriptor index and byte offset of the row's first packet inside its tile
+    uint2 *tsum;                    // [T] packets and bytes of a tile of PACKETS_TILE rows
+    unsigned *tbase_c;              // [T] descriptor index of the tile's first packet
+    unsigned long long *tbase_b;    // [T] ... and its byte offset
+    unsigned *crcfail;              // [R] emitted packets of the row whose CRC does not match
+};
+size_t packets_scratch_bytes(size_t max_rows);
+void packets_scratch_carve(void *p, size_t max_rows, PacketsScratch &sc);
+int launch_packets(const unsigned char *vcdu, const unsigned *offsets, size_t max_rows, PacketsState *state,
+                   unsigned char *pend, PacketsScratch &sc, unsigned char *bytes, size_t max_bytes, xrit_packet *packets,
+                   size_t max_packets, unsigned *pkt_offsets, xrit_packets_summary *summary, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

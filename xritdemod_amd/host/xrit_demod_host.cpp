@@ -43,6 +43,8 @@
 #include <atomic>
 #include <chrono>
 #include <deque>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <cerrno>
 #include <cstdint>
@@ -81,6 +83,7 @@ struct Options {
     std::string decode;            // --decode PATH: the decoder's frame steps on the symbols, VCDUs of good frames to PATH
     std::string channels;          // --channels DIR: the good frames' VCDUs split by VCID, DIR/channel_{vcid}.bin
     std::string decoder_stats;     // --decoder-stats PATH: one Statistics_st (4167 bytes) per valid frame
+    std::string packets;           // --packets DIR: the CRC-checked space packets, DIR/vc{vcid}_apid{apid}.bin
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -98,6 +101,8 @@ void usage()
                  "                            good frame appended to PATH, counts on stderr at exit; --sink null for a decode-only run)\n"
                  "         [--channels DIR]   (the decoder's ChannelWriter: every good VCDU appended to DIR/channel_{vcid}.bin)\n"
                  "         [--decoder-stats PATH]   (the decoder's Statistics_st, 4167 bytes per valid frame; lost packets on stderr at exit)\n"
+                 "         [--packets DIR]   (CCSDS space packets out of the channels' VCDUs: every packet whose CRC-16 matches appended whole,\n"
+                 "                            header included, to DIR/vc{vcid}_apid{apid}.bin; counts on stderr at exit)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -131,6 +136,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--decode") { if (!(v = need("--decode"))) return false; o.decode = v; }
         else if (a == "--channels") { if (!(v = need("--channels"))) return false; o.channels = v; }
         else if (a == "--decoder-stats") { if (!(v = need("--decoder-stats"))) return false; o.decoder_stats = v; }
+        else if (a == "--packets") { if (!(v = need("--packets"))) return false; o.packets = v; }
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -153,6 +159,10 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--channels / --decoder-stats: one GPU, without --drop\n");
         return false;
     }
+    if (!o.packets.empty() && (o.drop || o.gpus > 1)) {
+        std::fprintf(stderr, "--packets: one GPU, without --drop\n");
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
 
@@ -160,7 +170,8 @@ bool parse(int argc, char **argv, Options &o)
 // Whole 16384-symbol windows go through the correlator, the frame fix (HRIT: word forced to 0, NRZ-M takes the phase) and
 // the frame decoder; the symbols from the first window whose frame is not complete yet wait for the next round.
 // --channels / --decoder-stats add the channel demultiplexer behind the decoder (:309-395): ChannelWriter's files and
-// the Statistics_st stream, from the correlator's hits as it returned them.
+// the Statistics_st stream, from the correlator's hits as it returned them.  --packets adds the packet assembler behind
+// the demultiplexer: the channels' rows go back to the device and come out as CRC-checked space packets.
 struct FrameDecode {
     static constexpr size_t FRAME = 16384, VCDU = 892;
     static constexpr uint32_t MIN_CORRELATION = 46;     // MINCORRELATIONBITS (parameters.h:31)
@@ -168,7 +179,13 @@ struct FrameDecode {
     FILE *stats_out = nullptr;
     xrit_decoder *dec = nullptr;
     xrit_demux *dm = nullptr;
-    std::string channel_dir;
+    xrit_packets *pk = nullptr;
+    std::string channel_dir, packet_dir;
+    std::unique_ptr<uint8_t[]> pk_bytes;
+    std::unique_ptr<xrit_packet[]> pk_desc;
+    size_t pk_bytes_cap = 0, pk_desc_cap = 0;
+    std::map<std::pair<int, int>, FILE *> pk_files;
+    xrit_packets_summary pk_summary{};
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
     std::vector<xrit_frame_stats> records;
@@ -182,7 +199,8 @@ struct FrameDecode {
     std::vector<xrit_frame_info> info;
     size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
 
-    bool open(const std::string &path, const std::string &channels, const std::string &stats_path, bool hrit_mode, int dev)
+    bool open(const std::string &path, const std::string &channels, const std::string &stats_path, const std::string &packets,
+              bool hrit_mode, int dev)
     {
         hrit = hrit_mode;
         device = dev;
@@ -194,7 +212,7 @@ struct FrameDecode {
             out = std::fopen(path.c_str(), "wb");
             if (!out) { std::perror("decode output"); return false; }
         }
-        if (channels.empty() && stats_path.empty()) return true;
+        if (channels.empty() && stats_path.empty() && packets.empty()) return true;
         if (xrit_demux_create(&dm, device) != XRIT_OK || xrit_demux_stats(dm, &dm_stats) != XRIT_OK) {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
@@ -206,6 +224,14 @@ struct FrameDecode {
         if (!stats_path.empty()) {
             stats_out = std::fopen(stats_path.c_str(), "wb");
             if (!stats_out) { std::perror("decoder statistics output"); return false; }
+        }
+        if (!packets.empty()) {
+            if (xrit_packets_create(&pk, device) != XRIT_OK) {
+                std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                return false;
+            }
+            if (::mkdir(packets.c_str(), 0755) != 0 && errno != EEXIST) { std::perror("--packets"); return false; }
+            packet_dir = packets;
         }
         return true;
     }
@@ -274,7 +300,35 @@ struct FrameDecode {
             const size_t bytes = (size_t)n * XRIT_STATISTICS_WIRE_BYTES;
             if (std::fwrite(wire.data(), 1, bytes, stats_out) != bytes) { std::perror("decoder statistics output"); return false; }
         }
+        return pk ? assemble(off) : true;
+    }
+    // the space packets of this round's rows; what has begun and not ended waits on the device for the next round
+    bool assemble(const uint32_t *off)
+    {
+        const size_t rows = off[64], need_bytes = XRIT_PACKETS_MAX_BYTES(rows), need_desc = 127 * rows + 64;
+        if (need_bytes > pk_bytes_cap) { pk_bytes.reset(new uint8_t[need_bytes]); pk_bytes_cap = need_bytes; }
+        if (need_desc > pk_desc_cap) { pk_desc.reset(new xrit_packet[need_desc]); pk_desc_cap = need_desc; }
+        uint32_t pkt_off[65];
+        if (xrit_packets_process(pk, vcdu.data(), off, pk_bytes.get(), pk_bytes_cap, pk_desc.get(), pk_desc_cap, pkt_off,
+                                 &pk_summary) != XRIT_OK)
+            return fail("packets");
+        for (size_t i = 0; i < pk_summary.packets; ++i) {
+            const xrit_packet &d = pk_desc[i];
+            if (!d.crc_ok) continue;
+            const std::pair<int, int> key{d.vcid, d.apid};
+            if (pk_files.size() >= 64 && !pk_files.count(key)) close_packet_files();     // (a bound on the open files)
+            FILE *&f = pk_files[key];
+            const std::string name = packet_dir + "/vc" + std::to_string(d.vcid) + "_apid" + std::to_string(d.apid) + ".bin";
+            if (!f) f = std::fopen(name.c_str(), "ab");
+            if (!f || std::fwrite(pk_bytes.get() + d.offset, 1, d.length, f) != d.length) { std::perror(name.c_str()); return false; }
+        }
         return true;
+    }
+    void close_packet_files()
+    {
+        for (auto &kv : pk_files)
+            if (kv.second) std::fclose(kv.second);
+        pk_files.clear();
     }
     bool fail(const char *what)
     {
@@ -300,6 +354,14 @@ struct FrameDecode {
             std::fprintf(stderr, ")\n");
             xrit_demux_destroy(dm);
             dm = nullptr;
+        }
+        if (pk) {
+            std::fprintf(stderr, "packets: %llu emitted, %llu CRC failures, %llu discarded, %llu fill\n",
+                         (unsigned long long)pk_summary.total_packets, (unsigned long long)pk_summary.crc_failures,
+                         (unsigned long long)pk_summary.discarded, (unsigned long long)pk_summary.fill_packets);
+            close_packet_files();
+            xrit_packets_destroy(pk);
+            pk = nullptr;
         }
         if (out) std::fclose(out);
         out = nullptr;
@@ -611,8 +673,8 @@ int main(int argc, char **argv)
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
-    if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty()) &&
-        !decode.open(o.decode, o.channels, o.decoder_stats, o.mode == "hrit", o.device)) {
+    if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty()) &&
+        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.mode == "hrit", o.device)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
