@@ -557,6 +557,143 @@ int xrit_packets_process(xrit_packets *pa, const uint8_t *vcdu, const uint32_t *
 int xrit_packets_stats(xrit_packets *pa, xrit_packets_counters *out);
 
 /* ------------------------------------------------------------------------
+ * File assembler and Rice decoder: LRIT/HRIT files out of the packet
+ * assembler's space packets, and the Rice-coded scan lines inside GOES image
+ * files.  The reference decoder ends at the VCDU, so there is no reference line
+ * to cite: the layouts are taken from the space packet recommendation (CCSDS
+ * 133.0-B: sequence flags 1 first, 0 continuation, 2 last, 3 unsegmented; the
+ * 14-bit sequence count), the LRIT/HRIT global specification (CGMS 03: the
+ * transport file's 10-byte header -- file counter, length in bits --, the
+ * primary header record, the image structure record, type 1), the GOES
+ * mission specific Rice compression record (type 131) and the lossless data
+ * compression recommendation (CCSDS 121.0-B: the adaptive entropy coder and
+ * the unit-delay predictor).  No libaec and no recorded downlink was at hand:
+ * DESIGN.md sections 15 and 16 list what is unverified.  Exact integer
+ * contracts there; tests/file_spec.py and tests/rice_spec.py are the serial
+ * statements.
+ *
+ * Files.  Input: one packets call's bytes, descriptors and pkt_offsets[65].
+ *  - key = (vcid, apid); per key, carried across calls until reset: whether a
+ *    file is open, the next sequence count, the file's serial on its key, its
+ *    bytes and pieces so far, the transport header and the parsed header fields.
+ *    File bytes are not kept: a call emits the pieces it saw.
+ *  - a packet is bad iff crc_ok == 0, length < 8 or it lies outside the input
+ *    bytes; a bad packet, a break in the sequence counts or a new first packet
+ *    aborts the open file (its record carries ABORTED; nothing emitted is taken
+ *    back).  Pieces outside a file are counted (orphans) and not emitted.
+ *  - outputs ordered by (vcid, apid, stream order): the pieces' payloads back to
+ *    back, one xrit_file_piece each, one xrit_file_record per file touched.
+ * ------------------------------------------------------------------------ */
+#define XRIT_E_ARG XRIT_E_INVALID   /* the argument-error code under the name the file / Rice stages' documents use */
+typedef struct xrit_files xrit_files;
+typedef struct xrit_file_piece {
+    uint64_t offset;                 /* of the payload's first byte in the call's byte buffer */
+    uint32_t length;                 /* payload bytes (0 .. 65528) */
+    uint32_t index_in_file;          /* 0 for the piece that began the file */
+    uint32_t file;                   /* index into the call's records */
+    uint16_t seq_count, apid;
+    uint8_t  vcid, seq_flags;
+    uint8_t  reserved[6];
+} xrit_file_piece;                   /* 32 bytes; begins like xrit_packet: either serves as a Rice line descriptor */
+#define XRIT_FILE_BEGINS       1     /* the file's first piece is in this call */
+#define XRIT_FILE_ENDS         2     /* ... its last */
+#define XRIT_FILE_ABORTED      4     /* the host discards the file */
+#define XRIT_FILE_LENGTH_MATCH 8     /* on ENDS: 8 * (file_offset + length) == declared_bits */
+typedef struct xrit_file_record {
+    uint64_t offset, length;         /* the file's bytes of this call: contiguous in the call's byte buffer */
+    uint64_t file_offset;            /* bytes of the file emitted by earlier calls */
+    uint64_t declared_bits;          /* transport header: BE64(u[2..10)); reported, never used to cut */
+    uint64_t data_bits;              /* primary header */
+    uint32_t header_length;          /* primary header: total header length */
+    uint32_t first_piece, n_pieces;  /* this call's pieces of the file */
+    uint32_t key_serial;             /* files begun on this key before this one */
+    uint16_t file_counter;           /* transport header: BE16(u[0..2)) */
+    uint16_t apid;
+    uint16_t columns, lines;         /* image structure record (type 1, length 9) */
+    uint16_t rice_flags;             /* Rice record (type 131, length 7) */
+    uint8_t  vcid, flags;
+    uint8_t  file_type;              /* primary header */
+    uint8_t  header_state;           /* 0: no primary header in the first piece; 1: headers incomplete or malformed; 2: walked to their end */
+    uint8_t  bits_per_pixel, compression;
+    uint8_t  pixels_per_block, lines_per_packet;
+    uint8_t  reserved[6];
+} xrit_file_record;                  /* 80 bytes */
+typedef struct xrit_files_counters {
+    uint64_t files_begun, files_completed, files_aborted, bad_packets, seq_gaps, short_first, orphans;
+    uint64_t total_pieces, total_bytes;
+    uint64_t open_files;             /* keys with a file open */
+} xrit_files_counters;               /* 80 bytes */
+typedef struct xrit_files_summary {
+    uint64_t pieces, bytes, files;   /* of this call: the true counts, whatever the capacities */
+    uint64_t files_begun, files_completed, files_aborted, bad_packets, seq_gaps, short_first, orphans;   /* the handle's */
+    uint64_t total_pieces, total_bytes;                                                                  /* counters after it */
+    uint32_t overflow;               /* 0; 1: a capacity too small; 2: d_pkt_offsets[64] > max_packets_in */
+    uint32_t reserved;
+} xrit_files_summary;                /* 104 bytes */
+/* what one key carries (xrit_files_key) */
+typedef struct xrit_file_key {
+    uint64_t file_bytes, declared_bits, data_bits;
+    uint32_t header_length, n_pieces, key_serial;
+    uint16_t next_seq, file_counter, columns, lines, rice_flags;
+    uint8_t  open, file_type, header_state, bits_per_pixel, compression, pixels_per_block, lines_per_packet;
+    uint8_t  reserved[3];
+} xrit_file_key;                     /* 56 bytes */
+#define XRIT_FILES_MAX_PACKETS ((size_t)1 << 24)            /* packets per call */
+/* a call on n packets of b bytes emits at most n pieces, b bytes and 2 n records (in fact n + one per key) */
+#define XRIT_FILES_MAX_PIECES(n) ((size_t)(n))
+#define XRIT_FILES_MAX_BYTES(b)  ((size_t)(b))
+#define XRIT_FILES_MAX_FILES(n)  ((size_t)2 * (n))
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_files_create(xrit_files **fa, int device);
+int xrit_files_destroy(xrit_files *fa);
+/* every key back to its start, counters zero; waits for the handle's last call */
+int xrit_files_reset(xrit_files *fa);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_packets_process_device, which hands it its packet count in d_pkt_offsets[64] on the device.
+ * max_packets_in (<= XRIT_FILES_MAX_PACKETS) is the host's bound on that count (the descriptors the packets call could
+ * write: its max_packets), in_bytes the size of d_in_bytes (its max_bytes): a larger d_pkt_offsets[64] raises
+ * overflow = 2 and nothing else is written, the state unchanged; a packet that lies outside in_bytes is a bad packet.
+ * d_pieces, d_files, d_summary 8-byte aligned.  Capacity: piece k is written iff k < max_pieces, its bytes iff offset +
+ * length <= max_bytes, record k iff k < max_files; the summary carries the true counts and overflow = 1, and the
+ * handle's state advances as if everything had fitted.  Calls on one handle share its state and scratch: keep them in
+ * order. */
+int xrit_files_process_device(xrit_files *fa, const uint8_t *d_in_bytes, size_t in_bytes, const xrit_packet *d_packets,
+                              const uint32_t *d_pkt_offsets, size_t max_packets_in, uint8_t *d_bytes, size_t max_bytes,
+                              xrit_file_piece *d_pieces, size_t max_pieces, xrit_file_record *d_files, size_t max_files,
+                              xrit_files_summary *d_summary, void *stream);
+/* host buffers (one upload, one download); the packets are pkt_offsets[64].  XRIT_E_CAPACITY when a capacity was too
+ * small: the prefix that fits is written, the summary is the true one, the state has advanced. */
+int xrit_files_process(xrit_files *fa, const uint8_t *in_bytes, size_t n_in_bytes, const xrit_packet *packets,
+                       const uint32_t *pkt_offsets, uint8_t *bytes, size_t max_bytes, xrit_file_piece *pieces,
+                       size_t max_pieces, xrit_file_record *files, size_t max_files, xrit_files_summary *summary);
+/* the counters after the handle's last call (waits for it) */
+int xrit_files_stats(xrit_files *fa, xrit_files_counters *out);
+/* what key (vcid < 64, apid < 2048) carries after the handle's last call (waits for it) */
+int xrit_files_key(xrit_files *fa, unsigned vcid, unsigned apid, xrit_file_key *out);
+
+/* Rice.  A batch of coded lines, each decoded on its own: n_lines descriptors `stride` bytes apart (stride >= 16, a
+ * multiple of 8), each beginning {uint64 offset; uint32 length} into d_bytes -- xrit_packet and xrit_file_piece both
+ * fit.  bits_per_sample 1 .. 16, block 8 / 16 / 32 / 64, samples 1 .. 65535 per line: anything else XRIT_E_ARG.
+ * d_out: n_lines * samples of uint8 (bits_per_sample <= 8) or little-endian uint16; d_status[n_lines]: 0, 1 (a fault:
+ * the blocks decoded in front of it are kept, the rest 0) or 2 (the descriptor points outside the n_bytes of d_bytes
+ * or is longer than 2^20 bytes: nothing read, all 0).  Stateless: no handle, no scratch.  Asynchronous on `stream`, no
+ * host synchronisation. */
+int xrit_rice_decode_device(const uint8_t *d_bytes, size_t n_bytes, const void *d_desc, size_t stride, size_t n_lines,
+                            int bits_per_sample, int block, int samples, void *d_out, uint8_t *d_status, int device,
+                            void *stream);
+/* Which kernel the decode calls launch, process wide: the default is the wave form (DESIGN.md section 16 has
+ * what was measured); the other stays selectable so that tests and the benchmark hold both to the specification.  LANE: one lane per
+ * line; WAVE: one wave per line.  Anything else: XRIT_E_ARG. */
+#define XRIT_RICE_FORM_DEFAULT 0
+#define XRIT_RICE_FORM_LANE    1
+#define XRIT_RICE_FORM_WAVE    2
+int xrit_rice_form(int form);
+/* host buffers (one upload, one download; staged through grow-only device buffers that the calling thread keeps) */
+int xrit_rice_decode(const uint8_t *bytes, size_t n_bytes, const void *desc, size_t stride, size_t n_lines,
+                     int bits_per_sample, int block, int samples, void *out, uint8_t *status, int device);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

@@ -107,6 +107,16 @@ _SIGNATURES = {
     "xrit_packets_process_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "xrit_packets_process": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "xrit_packets_stats": (C.c_int, [_vp, _vp]),
+    "xrit_files_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_files_destroy": (C.c_int, [_vp]),
+    "xrit_files_reset": (C.c_int, [_vp]),
+    "xrit_files_process_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "xrit_files_process": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "xrit_files_stats": (C.c_int, [_vp, _vp]),
+    "xrit_files_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
+    "xrit_rice_decode_device": (C.c_int, [_vp, _sz, _vp, _sz, _sz, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "xrit_rice_form": (C.c_int, [C.c_int]),
+    "xrit_rice_decode": (C.c_int, [_vp, _sz, _vp, _sz, _sz, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -942,3 +952,173 @@ class PacketAssembler(_Handle):
     def reset(self):
         """Every channel back to its start: no last counter, nothing pending, counters zero."""
         _check(lib().xrit_packets_reset(self._h))
+
+
+# ---- file assembler and Rice decoder (DESIGN.md sections 15 and 16) ---------------------------------------------------
+# xrit_file_piece: one descriptor per emitted piece (offset and length lie as in xrit_packet)
+FILE_PIECE_DTYPE = np.dtype([
+    ("offset", np.uint64), ("length", np.uint32), ("index_in_file", np.uint32), ("file", np.uint32),
+    ("seq_count", np.uint16), ("apid", np.uint16), ("vcid", np.uint8), ("seq_flags", np.uint8), ("reserved", np.uint8, (6,))])
+assert FILE_PIECE_DTYPE.itemsize == 32
+
+# xrit_file_record: one per file touched in a call
+FILE_RECORD_DTYPE = np.dtype([
+    ("offset", np.uint64), ("length", np.uint64), ("file_offset", np.uint64), ("declared_bits", np.uint64),
+    ("data_bits", np.uint64),
+    ("header_length", np.uint32), ("first_piece", np.uint32), ("n_pieces", np.uint32), ("key_serial", np.uint32),
+    ("file_counter", np.uint16), ("apid", np.uint16), ("columns", np.uint16), ("lines", np.uint16), ("rice_flags", np.uint16),
+    ("vcid", np.uint8), ("flags", np.uint8), ("file_type", np.uint8), ("header_state", np.uint8),
+    ("bits_per_pixel", np.uint8), ("compression", np.uint8), ("pixels_per_block", np.uint8), ("lines_per_packet", np.uint8),
+    ("reserved", np.uint8, (6,))])
+assert FILE_RECORD_DTYPE.itemsize == 80
+FILE_BEGINS, FILE_ENDS, FILE_ABORTED, FILE_LENGTH_MATCH = 1, 2, 4, 8
+
+_FILES_COUNTERS = [(k, np.uint64) for k in ("files_begun", "files_completed", "files_aborted", "bad_packets", "seq_gaps",
+                                            "short_first", "orphans", "total_pieces", "total_bytes")]
+# xrit_files_summary: a call's true counts and the handle's counters after it
+FILES_SUMMARY_DTYPE = np.dtype([("pieces", np.uint64), ("bytes", np.uint64), ("files", np.uint64)] + _FILES_COUNTERS +
+                               [("overflow", np.uint32), ("reserved", np.uint32)])
+assert FILES_SUMMARY_DTYPE.itemsize == 104
+# xrit_files_counters
+FILES_STATS_DTYPE = np.dtype(_FILES_COUNTERS + [("open_files", np.uint64)])
+assert FILES_STATS_DTYPE.itemsize == 80
+# xrit_file_key: what one (vcid, apid) carries
+FILE_KEY_DTYPE = np.dtype([
+    ("file_bytes", np.uint64), ("declared_bits", np.uint64), ("data_bits", np.uint64),
+    ("header_length", np.uint32), ("n_pieces", np.uint32), ("key_serial", np.uint32),
+    ("next_seq", np.uint16), ("file_counter", np.uint16), ("columns", np.uint16), ("lines", np.uint16), ("rice_flags", np.uint16),
+    ("open", np.uint8), ("file_type", np.uint8), ("header_state", np.uint8), ("bits_per_pixel", np.uint8),
+    ("compression", np.uint8), ("pixels_per_block", np.uint8), ("lines_per_packet", np.uint8), ("reserved", np.uint8, (3,))])
+assert FILE_KEY_DTYPE.itemsize == 56
+
+
+class FileAssembler(_Handle):
+    """LRIT/HRIT files out of PacketAssembler's packets: per (vcid, apid) the sequence flags and counts are followed and
+    the transport header and the header records of a file's first packet parsed; a call emits the pieces it saw and one
+    record per file touched, and the host appends.  What is open is carried across calls until reset()."""
+    _destroy = "xrit_files_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_files_create(C.byref(self._h), device))
+
+    def process(self, data, packets, pkt_offsets, max_bytes=None, max_pieces=None, max_files=None):
+        """data uint8, packets PACKET_DTYPE and pkt_offsets (65,) uint32 as PacketAssembler.process returns them.  ->
+        (bytes uint8: the emitted payloads back to back; pieces FILE_PIECE_DTYPE; files FILE_RECORD_DTYPE; summary, a
+        FILES_SUMMARY_DTYPE record), all ordered by (vcid, apid, stream order).  With capacities that turn out too small
+        XritError -5 is raised; its `partial` holds the same four with the prefix that fitted (the handle's state has
+        advanced all the same)."""
+        pkt_offsets = np.ascontiguousarray(pkt_offsets, np.uint32).reshape(N_VCID + 1)
+        n = int(pkt_offsets[N_VCID])
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        packets = np.ascontiguousarray(packets, PACKET_DTYPE).reshape(-1)
+        if len(packets) < n:
+            raise ValueError("pkt_offsets[64] counts more packets than there are descriptors")
+        cap_b = len(data) if max_bytes is None else int(max_bytes)
+        cap_p = n if max_pieces is None else int(max_pieces)
+        cap_f = 2 * n if max_files is None else int(max_files)
+        buf = np.empty(max(cap_b, 1), np.uint8)
+        pieces = np.empty(max(cap_p, 1), FILE_PIECE_DTYPE)
+        files = np.empty(max(cap_f, 1), FILE_RECORD_DTYPE)
+        summary = np.zeros(1, FILES_SUMMARY_DTYPE)
+        rc = lib().xrit_files_process(self._h, _p(data), len(data), _p(packets), _p(pkt_offsets), _p(buf), cap_b, _p(pieces),
+                                      cap_p, _p(files), cap_f, _p(summary))
+        if rc not in (0, -5):
+            _check(rc)
+        pieces = pieces[:min(int(summary[0]["pieces"]), cap_p)].copy()
+        files = files[:min(int(summary[0]["files"]), cap_f)].copy()
+        if int(summary[0]["bytes"]) <= cap_b:
+            nb = int(summary[0]["bytes"])
+        else:                                                # whole pieces only: up to the end of the last one that fits
+            ends = pieces["offset"] + pieces["length"]
+            ends = ends[ends <= cap_b]
+            nb = int(ends[-1]) if len(ends) else 0
+        out = (buf[:nb].copy(), pieces, files, summary[0])
+        if rc != 0:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            err.partial = out
+            raise err
+        return out
+
+    def process_device(self, d_in_bytes_ptr, in_bytes, d_packets_ptr, d_pkt_offsets_ptr, max_packets_in, d_bytes_ptr, max_bytes,
+                       d_pieces_ptr, max_pieces, d_files_ptr, max_files, d_summary_ptr, stream=None):
+        """Device pointers (bytes of in_bytes, packets max_packets_in x 32 and pkt_offsets 65 x 4 as
+        PacketAssembler.process_device wrote them; bytes max_bytes, pieces max_pieces x 32, files max_files x 80,
+        summary 104 bytes), asynchronous on stream; may be queued behind PacketAssembler.process_device: the packet
+        count is read from pkt_offsets[64] on the device, max_packets_in is the host's bound on it."""
+        _check(lib().xrit_files_process_device(self._h, C.c_void_p(d_in_bytes_ptr), in_bytes, C.c_void_p(d_packets_ptr),
+                                               C.c_void_p(d_pkt_offsets_ptr), max_packets_in, C.c_void_p(d_bytes_ptr), max_bytes,
+                                               C.c_void_p(d_pieces_ptr), max_pieces, C.c_void_p(d_files_ptr), max_files,
+                                               C.c_void_p(d_summary_ptr), C.c_void_p(stream) if stream else None))
+
+    def stats(self):
+        """The counters after the last call (a FILES_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, FILES_STATS_DTYPE)
+        _check(lib().xrit_files_stats(self._h, _p(out)))
+        return out[0]
+
+    def key(self, vcid, apid):
+        """What (vcid, apid) carries after the last call (a FILE_KEY_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, FILE_KEY_DTYPE)
+        _check(lib().xrit_files_key(self._h, vcid, apid, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Every key back to its start: nothing open, serials and counters zero."""
+        _check(lib().xrit_files_reset(self._h))
+
+
+RICE_FORMS = {"default": 0, "lane": 1, "wave": 2}
+
+
+def rice_form(form="default"):
+    """Which kernel RiceDecoder launches from now on, process wide: "default" (the wave form), "lane" (one lane per
+    line) or "wave" (one wave per line).  Both are held to the same specification."""
+    _check(lib().xrit_rice_form(RICE_FORMS[form]))
+
+
+class RiceDecoder:
+    """The Rice decoder (CCSDS 121.0-B) on batches of coded lines: bits per sample 1 .. 16, block 8 / 16 / 32 / 64,
+    samples per line 1 .. 65535.  Stateless."""
+
+    def __init__(self, bits_per_sample, block, samples, device=0):
+        self.n, self.J, self.S, self.device = int(bits_per_sample), int(block), int(samples), device
+        # an empty batch: the parameters and the device are checked here, not at the first line
+        _check(lib().xrit_rice_decode(None, 0, None, 16, 0, self.n, self.J, self.S, None, None, device))
+
+    def decode(self, data, desc):
+        """data uint8; desc a structured array whose records begin {offset u64, length u32} (PACKET_DTYPE,
+        FILE_PIECE_DTYPE or tests' 16-byte form), one line each.  -> (samples (n_lines, S) uint8 or uint16,
+        status (n_lines,) uint8: 0, 1 a fault -- whole blocks kept, the rest 0 --, 2 descriptor outside data)."""
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        desc = np.ascontiguousarray(desc).reshape(-1)
+        out = np.zeros((len(desc), self.S), np.uint8 if self.n <= 8 else np.uint16)
+        status = np.zeros(len(desc), np.uint8)
+        _check(lib().xrit_rice_decode(_p(data), len(data), _p(desc), desc.dtype.itemsize, len(desc), self.n, self.J, self.S,
+                                      _p(out), _p(status), self.device))
+        return out, status
+
+    def decode_device(self, d_bytes_ptr, n_bytes, d_desc_ptr, stride, n_lines, d_out_ptr, d_status_ptr, stream=None):
+        """Device pointers, asynchronous on stream."""
+        _check(lib().xrit_rice_decode_device(C.c_void_p(d_bytes_ptr), n_bytes, C.c_void_p(d_desc_ptr), stride, n_lines, self.n,
+                                             self.J, self.S, C.c_void_p(d_out_ptr), C.c_void_p(d_status_ptr), self.device,
+                                             C.c_void_p(stream) if stream else None))
+
+
+def is_rice_coded(record, first_piece_length):
+    """The link between the two stages (this project's convention): the record's file is an image
+    whose first piece carries the headers alone and whose pieces 1, 2, ... are one Rice-coded line each."""
+    return (int(record["header_state"]) == 2 and int(record["file_type"]) == 0 and int(record["compression"]) == 1 and
+            1 <= int(record["bits_per_pixel"]) <= 16 and int(record["columns"]) >= 1 and
+            int(record["pixels_per_block"]) in (8, 16, 32, 64) and int(record["header_length"]) == int(first_piece_length))
+
+
+def decode_file_lines(record, pieces, data, device=0):
+    """The scan lines of a rice-coded file whose pieces all lie in one call: record, a FILE_RECORD_DTYPE with BEGINS;
+    pieces and data, that call's.  -> (samples (n_pieces - 1, columns), status) or None when the link rule says the file
+    is not rice-coded."""
+    mine = pieces[int(record["first_piece"]):int(record["first_piece"]) + int(record["n_pieces"])]
+    if not (int(record["flags"]) & FILE_BEGINS) or len(mine) < 1 or not is_rice_coded(record, mine[0]["length"]):
+        return None
+    dec = RiceDecoder(int(record["bits_per_pixel"]), int(record["pixels_per_block"]), int(record["columns"]), device)
+    return dec.decode(data, mine[1:])

@@ -485,6 +485,30 @@ void packets_scratch_carve(void *p, size_t max_rows, PacketsScratch &sc);
 int launch_packets(const unsigned char *vcdu, const unsigned *offsets, size_t max_rows, PacketsState *state,
                    unsigned char *pend, PacketsScratch &sc, unsigned char *bytes, size_t max_bytes, xrit_packet *packets,
                    size_t max_packets, unsigned *pkt_offsets, xrit_packets_summary *summary, hipStream_t s);
+// file assembler (files.hip): the handle's state is FILES_KEYS xrit_file_key records and one xrit_files_counters
+constexpr unsigned FILES_KEYS = 64 * 2048;          // (vcid, apid), directly indexed
+constexpr unsigned FILES_TILE = 2048;               // keys per tile of the scan
+constexpr unsigned FILES_TSUM = 10;                 // words of a tile's sums: pieces, records, bytes, seven counter increments
+struct FilesScratch {
+    unsigned *order;                // [N] packet indices, per VCID stably sorted by APID
+    unsigned *kstart, *kcount;      // [FILES_KEYS] a key's run in `order`
+    unsigned *kpieces, *krecs;      // [FILES_KEYS] pieces and records the key's walk emits; after the scan: their exclusive prefix inside the tile
+    unsigned long long *kbytes;     // [FILES_KEYS] ... and bytes
+    unsigned long long *tsum, *tbase;   // [64][FILES_TSUM] a tile's sums; [64][3] its first piece index, record index, byte offset
+    unsigned *kcnt;                 // [FILES_KEYS][7] the walk's counter increments: begun, completed, aborted, bad, gaps, short, orphans
+    unsigned long long *psrc, *pdst;// [N] per piece: where its payload lies in the input, where it goes
+    unsigned *plen;                 // [N]
+};
+size_t files_scratch_bytes(size_t max_in);
+void files_scratch_carve(void *p, size_t max_in, FilesScratch &sc);
+int launch_files(const unsigned char *in_bytes, size_t n_in_bytes, const xrit_packet *packets, const unsigned *pkt_offsets,
+                 size_t max_in, xrit_file_key *keys, xrit_files_counters *counters, FilesScratch &sc, unsigned char *bytes,
+                 size_t max_bytes, xrit_file_piece *pieces, size_t max_pieces, xrit_file_record *files, size_t max_files,
+                 xrit_files_summary *summary, hipStream_t s);
+// Rice decoder (rice.hip)
+constexpr int RICE_FORM_LANE = 1, RICE_FORM_WAVE = 2;
+int launch_rice(const unsigned char *bytes, size_t n_bytes, const void *desc, size_t stride, size_t n_lines, int n, int J, int S,
+                void *out, unsigned char *status, int form, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

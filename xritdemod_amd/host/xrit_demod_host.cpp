@@ -84,6 +84,8 @@ struct Options {
     std::string channels;          // --channels DIR: the good frames' VCDUs split by VCID, DIR/channel_{vcid}.bin
     std::string decoder_stats;     // --decoder-stats PATH: one Statistics_st (4167 bytes) per valid frame
     std::string packets;           // --packets DIR: the CRC-checked space packets, DIR/vc{vcid}_apid{apid}.bin
+    std::string files;             // --files DIR: the LRIT/HRIT files, DIR/vc{vcid}_apid{apid}_{serial}.lrit
+    bool files_decompress = false; // --files-decompress: the scan lines of rice-coded image files, ..._{serial}.img
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -103,6 +105,12 @@ void usage()
                  "         [--decoder-stats PATH]   (the decoder's Statistics_st, 4167 bytes per valid frame; lost packets on stderr at exit)\n"
                  "         [--packets DIR]   (CCSDS space packets out of the channels' VCDUs: every packet whose CRC-16 matches appended whole,\n"
                  "                            header included, to DIR/vc{vcid}_apid{apid}.bin; counts on stderr at exit)\n"
+                 "         [--files DIR]   (LRIT/HRIT files out of the space packets: every file appended to DIR/vc{vcid}_apid{apid}_{serial}.lrit.part,\n"
+                 "                          renamed to .lrit at its last packet, deleted when it is aborted (a lost or damaged packet); a file that\n"
+                 "                          is open at exit stays .part; counts on stderr at exit)\n"
+                 "         [--files-decompress]   (with --files: image files whose headers say Rice compression -- one coded line per packet behind a\n"
+                 "                                 header-only first packet -- are also decoded on the GPU to ..._{serial}.img: lines x columns raw\n"
+                 "                                 samples, uint8 or little-endian uint16; a line that faults is written as decoded and counted)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -137,6 +145,8 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--channels") { if (!(v = need("--channels"))) return false; o.channels = v; }
         else if (a == "--decoder-stats") { if (!(v = need("--decoder-stats"))) return false; o.decoder_stats = v; }
         else if (a == "--packets") { if (!(v = need("--packets"))) return false; o.packets = v; }
+        else if (a == "--files") { if (!(v = need("--files"))) return false; o.files = v; }
+        else if (a == "--files-decompress") o.files_decompress = true;
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -163,6 +173,14 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--packets: one GPU, without --drop\n");
         return false;
     }
+    if (!o.files.empty() && (o.drop || o.gpus > 1)) {
+        std::fprintf(stderr, "--files: one GPU, without --drop\n");
+        return false;
+    }
+    if (o.files_decompress && o.files.empty()) {
+        std::fprintf(stderr, "--files-decompress needs --files DIR\n");
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
 
@@ -171,7 +189,8 @@ bool parse(int argc, char **argv, Options &o)
 // the frame decoder; the symbols from the first window whose frame is not complete yet wait for the next round.
 // --channels / --decoder-stats add the channel demultiplexer behind the decoder (:309-395): ChannelWriter's files and
 // the Statistics_st stream, from the correlator's hits as it returned them.  --packets adds the packet assembler behind
-// the demultiplexer: the channels' rows go back to the device and come out as CRC-checked space packets.
+// the demultiplexer: the channels' rows go back to the device and come out as CRC-checked space packets.  --files adds
+// the file assembler behind that (and, with --files-decompress, the Rice decoder on the lines of rice-coded image files).
 struct FrameDecode {
     static constexpr size_t FRAME = 16384, VCDU = 892;
     static constexpr uint32_t MIN_CORRELATION = 46;     // MINCORRELATIONBITS (parameters.h:31)
@@ -186,6 +205,16 @@ struct FrameDecode {
     size_t pk_bytes_cap = 0, pk_desc_cap = 0;
     std::map<std::pair<int, int>, FILE *> pk_files;
     xrit_packets_summary pk_summary{};
+    xrit_files *fa = nullptr;
+    std::string file_dir;
+    bool decompress = false;
+    std::vector<uint8_t> f_bytes, img;
+    std::vector<xrit_file_piece> f_pieces;
+    std::vector<xrit_file_record> f_recs;
+    std::vector<uint8_t> line_status;
+    xrit_files_summary f_summary{};
+    std::map<std::string, bool> rice_files;       // the open files that are rice-coded, by their path stem
+    size_t rice_lines = 0, rice_faults = 0;
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
     std::vector<xrit_frame_stats> records;
@@ -200,7 +229,7 @@ struct FrameDecode {
     size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
 
     bool open(const std::string &path, const std::string &channels, const std::string &stats_path, const std::string &packets,
-              bool hrit_mode, int dev)
+              const std::string &files, bool files_decompress, bool hrit_mode, int dev)
     {
         hrit = hrit_mode;
         device = dev;
@@ -212,7 +241,7 @@ struct FrameDecode {
             out = std::fopen(path.c_str(), "wb");
             if (!out) { std::perror("decode output"); return false; }
         }
-        if (channels.empty() && stats_path.empty() && packets.empty()) return true;
+        if (channels.empty() && stats_path.empty() && packets.empty() && files.empty()) return true;
         if (xrit_demux_create(&dm, device) != XRIT_OK || xrit_demux_stats(dm, &dm_stats) != XRIT_OK) {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
@@ -225,13 +254,24 @@ struct FrameDecode {
             stats_out = std::fopen(stats_path.c_str(), "wb");
             if (!stats_out) { std::perror("decoder statistics output"); return false; }
         }
-        if (!packets.empty()) {
+        if (!packets.empty() || !files.empty()) {
             if (xrit_packets_create(&pk, device) != XRIT_OK) {
                 std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
                 return false;
             }
+        }
+        if (!packets.empty()) {
             if (::mkdir(packets.c_str(), 0755) != 0 && errno != EEXIST) { std::perror("--packets"); return false; }
             packet_dir = packets;
+        }
+        if (!files.empty()) {
+            if (xrit_files_create(&fa, device) != XRIT_OK) {
+                std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                return false;
+            }
+            if (::mkdir(files.c_str(), 0755) != 0 && errno != EEXIST) { std::perror("--files"); return false; }
+            file_dir = files;
+            decompress = files_decompress;
         }
         return true;
     }
@@ -312,7 +352,7 @@ struct FrameDecode {
         if (xrit_packets_process(pk, vcdu.data(), off, pk_bytes.get(), pk_bytes_cap, pk_desc.get(), pk_desc_cap, pkt_off,
                                  &pk_summary) != XRIT_OK)
             return fail("packets");
-        for (size_t i = 0; i < pk_summary.packets; ++i) {
+        for (size_t i = 0; !packet_dir.empty() && i < pk_summary.packets; ++i) {
             const xrit_packet &d = pk_desc[i];
             if (!d.crc_ok) continue;
             const std::pair<int, int> key{d.vcid, d.apid};
@@ -321,6 +361,70 @@ struct FrameDecode {
             const std::string name = packet_dir + "/vc" + std::to_string(d.vcid) + "_apid" + std::to_string(d.apid) + ".bin";
             if (!f) f = std::fopen(name.c_str(), "ab");
             if (!f || std::fwrite(pk_bytes.get() + d.offset, 1, d.length, f) != d.length) { std::perror(name.c_str()); return false; }
+        }
+        return fa ? assemble_files(pkt_off) : true;
+    }
+    // the files of this round's packets: every record's bytes appended to its file, which is renamed at its end and
+    // deleted when it is aborted; what is open waits (on the device: the key's state; here: the .part file)
+    bool assemble_files(const uint32_t *pkt_off)
+    {
+        const size_t n = pkt_off[64];
+        f_bytes.resize(XRIT_FILES_MAX_BYTES(pk_summary.bytes) + 1);
+        f_pieces.resize(XRIT_FILES_MAX_PIECES(n) + 1);
+        f_recs.resize(XRIT_FILES_MAX_FILES(n) + 1);
+        if (xrit_files_process(fa, pk_bytes.get(), pk_summary.bytes, pk_desc.get(), pkt_off, f_bytes.data(), f_bytes.size(), f_pieces.data(),
+                               f_pieces.size(), f_recs.data(), f_recs.size(), &f_summary) != XRIT_OK)
+            return fail("files");
+        for (size_t i = 0; i < f_summary.files; ++i) {
+            const xrit_file_record &r = f_recs[i];
+            const std::string stem = file_dir + "/vc" + std::to_string(r.vcid) + "_apid" + std::to_string(r.apid) + "_" +
+                                     std::to_string(r.key_serial);
+            const std::string part = stem + ".lrit.part", img_part = stem + ".img.part";
+            const bool begins = r.flags & XRIT_FILE_BEGINS;
+            if (r.n_pieces) {
+                FILE *f = std::fopen(part.c_str(), begins ? "wb" : "ab");
+                const bool ok = f && std::fwrite(f_bytes.data() + r.offset, 1, r.length, f) == r.length;
+                if (f) std::fclose(f);
+                if (!ok) { std::perror(part.c_str()); return false; }
+            }
+            // the link rule: an image file, Rice compression, the first packet the headers alone
+            if (decompress && begins) {
+                const bool rice = r.header_state == 2 && r.file_type == 0 && r.compression == 1 && r.bits_per_pixel >= 1 &&
+                                  r.bits_per_pixel <= 16 && r.columns >= 1 &&
+                                  (r.pixels_per_block == 8 || r.pixels_per_block == 16 || r.pixels_per_block == 32 || r.pixels_per_block == 64) &&
+                                  r.header_length == f_pieces[r.first_piece].length;
+                if (rice) {
+                    rice_files[stem] = true;
+                    FILE *f = std::fopen(img_part.c_str(), "wb");
+                    if (!f) { std::perror(img_part.c_str()); return false; }
+                    std::fclose(f);
+                }
+            }
+            const bool rice = decompress && rice_files.count(stem);
+            const size_t first = r.first_piece + (begins ? 1 : 0), lines = r.n_pieces - (begins ? 1 : 0);
+            if (rice && r.n_pieces && lines) {
+                const size_t width = r.bits_per_pixel <= 8 ? 1 : 2;
+                img.resize(lines * r.columns * width);
+                line_status.resize(lines);
+                if (xrit_rice_decode(f_bytes.data(), f_summary.bytes, &f_pieces[first], sizeof(xrit_file_piece), lines, r.bits_per_pixel,
+                                     r.pixels_per_block, r.columns, img.data(), line_status.data(), device) != XRIT_OK)
+                    return fail("rice");
+                rice_lines += lines;
+                for (size_t k = 0; k < lines; ++k) rice_faults += line_status[k] != 0;
+                FILE *f = std::fopen(img_part.c_str(), "ab");
+                const bool ok = f && std::fwrite(img.data(), 1, img.size(), f) == img.size();
+                if (f) std::fclose(f);
+                if (!ok) { std::perror(img_part.c_str()); return false; }
+            }
+            if (r.flags & XRIT_FILE_ABORTED) {
+                std::remove(part.c_str());
+                if (rice) std::remove(img_part.c_str());
+                rice_files.erase(stem);
+            } else if (r.flags & XRIT_FILE_ENDS) {
+                if (std::rename(part.c_str(), (stem + ".lrit").c_str()) != 0) { std::perror(part.c_str()); return false; }
+                if (rice && std::rename(img_part.c_str(), (stem + ".img").c_str()) != 0) { std::perror(img_part.c_str()); return false; }
+                rice_files.erase(stem);
+            }
         }
         return true;
     }
@@ -354,6 +458,16 @@ struct FrameDecode {
             std::fprintf(stderr, ")\n");
             xrit_demux_destroy(dm);
             dm = nullptr;
+        }
+        if (fa) {
+            std::fprintf(stderr, "files: %llu begun, %llu completed, %llu aborted, %llu pieces, %llu bad packets, %llu gaps, %llu orphans\n",
+                         (unsigned long long)f_summary.files_begun, (unsigned long long)f_summary.files_completed,
+                         (unsigned long long)f_summary.files_aborted, (unsigned long long)f_summary.total_pieces,
+                         (unsigned long long)f_summary.bad_packets, (unsigned long long)f_summary.seq_gaps,
+                         (unsigned long long)f_summary.orphans);
+            if (decompress) std::fprintf(stderr, "rice: %zu lines decoded, %zu faulted\n", rice_lines, rice_faults);
+            xrit_files_destroy(fa);
+            fa = nullptr;
         }
         if (pk) {
             std::fprintf(stderr, "packets: %llu emitted, %llu CRC failures, %llu discarded, %llu fill\n",
@@ -673,8 +787,8 @@ int main(int argc, char **argv)
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
-    if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty()) &&
-        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.mode == "hrit", o.device)) {
+    if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
+        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
