@@ -1,0 +1,323 @@
+"""The stages behind the demodulator on device-resident data, timed with torch events after a warm-up; one JSON line per
+case, medians.  (Equality with the specifications is tests/test_gpu_{decode,demux,packets,files,rice}.py.)
+
+decode   xrit_decoder_decode_device (Viterbi27 + derandomiser + 4 x RS(255,223)): 65536 valid frames per call, clean
+         coded CADUs and the same at Es/N0 4 dB; and the test side's NumPy Viterbi (tests/ccsds.py) on a few frames on
+         one host core -- the specification, not the reference decoder (--no-cpu leaves it out).
+demux    xrit_demux_process_device on the decoder's outputs: a skewed VCID mix (about 90 % on one channel, the rest on
+         20 others, fill included), about 3 % corrupted frames -- the demux alone, and decode + demux on one stream.
+packets  xrit_packets_process_device behind the two: the same mix with packet zones that carry LRIT-like space packets
+         (most between 100 and 8198 bytes; a tile of 512 distinct CADUs repeated, so every channel's counters break once
+         per tile) -- the packet stage next to the demux on the same rows, and the chain with and without it.
+files    xrit_files_process_device on that case's packets (random bytes: nearly every one is a one-piece file with a
+         garbage header, over some 2000 APIDs per channel) -- the file stage alone, and the chain with and without it.
+rice     xrit_rice_decode_device: --lines x --samples 8-bit lines, J = 16, on both kernel forms and then on the default
+         (512 distinct lines tiled, a fifth of each of the specification's five generators, so every option occurs), as
+         Msamples/s and as a fraction of the device read rate measured in the same run on bytes in plus bytes out.
+all      the five, in this order.
+
+    python scripts/bench_backend.py {decode,demux,packets,files,rice,all} [--frames N] [--reps R] [--warmup W]
+                                    [--lines L] [--samples S] [--no-cpu]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+import xritdemod_amd as xa
+import ccsds
+import packet_spec as ps
+import rice_spec as rs
+
+ap = argparse.ArgumentParser()
+ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "all"])
+ap.add_argument("--frames", type=int, default=1 << 16)
+ap.add_argument("--reps", type=int, default=None, help="timed calls per case (decode: 5, the others: 20)")
+ap.add_argument("--warmup", type=int, default=None, help="calls before them (decode: 2, the others: 3)")
+ap.add_argument("--lines", type=int, default=8192)
+ap.add_argument("--samples", type=int, default=2048)
+ap.add_argument("--no-cpu", action="store_true")
+args = ap.parse_args()
+
+FR = ccsds.FRAME_SYMBOLS
+nf = args.frames
+dev = torch.device("cuda:0")
+st = torch.cuda.current_stream(dev).cuda_stream
+OTHERS = [0, 1, 2, 3, 4, 6, 7, 9, 13, 20, 21, 30, 31, 32, 40, 41, 50, 60, 62, 63]
+
+
+def emit(**row):
+    print(json.dumps(row), flush=True)
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times)), min(times)
+
+
+def u8(n):
+    return torch.empty(n, dtype=torch.uint8, device=dev)
+
+
+def tiled(cadus, dtype):
+    """The CADUs coded as one stream, tiled to nf frames (one seam per tile)."""
+    base = torch.from_numpy(ccsds.coded_symbols(cadus, amplitude=40).reshape(len(cadus), FR).astype(dtype)).to(dev)
+    return base.repeat((nf + len(cadus) - 1) // len(cadus), 1)[:nf].contiguous()
+
+
+def skewed_vcids(rng, n):
+    return [5 if rng.random() < 0.9 else OTHERS[rng.integers(0, len(OTHERS))] for _ in range(n)]
+
+
+def lrit_like_rows(rng, vcids):
+    """One 892-byte row per entry of vcids; every channel's rows are one generator stream of LRIT-like packets."""
+    def lrit_like(n_rows):
+        out, have = [], 0
+        while have < (n_rows + 2) * ps.ZONE:
+            u = rng.random()
+            total = int(rng.integers(100, 8199)) if u < 0.85 else int(rng.integers(7, 100)) if u < 0.95 else int(rng.integers(8199, 30000))
+            out.append(ps.make_packet(int(rng.integers(0, 2047)), len(out) & 0x3FFF, total, rng))
+            have += total
+        return out
+
+    rows = {}
+    for v in sorted(set(vcids)):
+        n = vcids.count(v)
+        if v == 63:
+            z = rng.integers(0, 256, (n, 892), dtype=np.uint8)
+            z[:, :6] = [ccsds.vcdu_header(0x8C, 63, i) for i in range(n)]
+            rows[v] = [bytes(r) for r in z]
+        else:
+            rows[v] = [bytes(r) for r in ps.build_stream(v, lrit_like(n), rng, start_counter=1000 * v).rows][:n]
+    nxt = {v: 0 for v in rows}
+    sent = []
+    for v in vcids:
+        sent.append(rows[v][nxt[v]])
+        nxt[v] += 1
+    return sent
+
+
+class Chain:
+    """The skewed mix with about 3 % corrupted frames, every stage's buffers and handle, and the stages as closures that
+    queue on the current stream.  zones: "random" (256 distinct CADUs, random phase words in the hits) or "packets" (512)."""
+
+    def __init__(self, zones):
+        rng = np.random.default_rng(1)
+        base_n = min(256 if zones == "random" else 512, nf)
+        vcids = skewed_vcids(rng, base_n)
+        if zones == "random":
+            blocks = [ccsds.make_block(0x8C, v, i, rng) for i, v in enumerate(vcids)]
+        else:
+            blocks = [ps.block_of(r) for r in lrit_like_rows(rng, vcids)]
+        self.frames = tiled(np.stack([ccsds.cadu_from_block(b) for b in blocks]), np.int8)
+        bad = torch.from_numpy(np.nonzero(rng.random(nf) < 0.03)[0]).to(dev)
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        self.frames[bad] = torch.randint(-128, 128, (len(bad), FR), dtype=torch.int8, device=dev, generator=g)
+        self.valid = torch.ones(nf, dtype=torch.uint8, device=dev)
+        self.hits = torch.zeros((nf, 4), dtype=torch.int32, device=dev)
+        if zones == "random":
+            self.hits[:, 0] = torch.randint(0, 2, (nf,), dtype=torch.int32, device=dev, generator=g)
+        self.hits[:, 2] = 60
+        self.cadu, self.block, self.info = u8(nf * 1024), u8(nf * 1020), u8(nf * xa.FRAME_INFO_DTYPE.itemsize)
+        self.vcdu, self.records = u8(nf * 892), u8(nf * xa.FRAME_STATS_DTYPE.itemsize)
+        self.offsets, self.pkt_offsets = (torch.empty(65, dtype=torch.int32, device=dev) for _ in range(2))
+        self.max_bytes, self.max_packets = xa.packets_max_bytes(nf), 16 * nf + 64
+        self.handles = []
+        if zones == "packets":
+            self.out_bytes, self.out_desc = u8(self.max_bytes), u8(self.max_packets * xa.PACKET_DTYPE.itemsize)
+            self.summary = u8(xa.PACKETS_SUMMARY_DTYPE.itemsize)
+            # the file stage: no call emits more pieces than packets, more bytes than it was given, more records than 2 x packets
+            self.f_bytes, self.f_pieces = u8(self.max_bytes), u8(self.max_packets * xa.FILE_PIECE_DTYPE.itemsize)
+            self.f_recs, self.f_summary = u8(2 * self.max_packets * xa.FILE_RECORD_DTYPE.itemsize), u8(xa.FILES_SUMMARY_DTYPE.itemsize)
+
+    def fresh_handles(self):
+        for h in self.handles:
+            h.close()
+        self.dec, self.dm, self.pa, self.fa = self.handles = [xa.FrameDecoder("lrit"), xa.ChannelDemux(), xa.PacketAssembler(),
+                                                               xa.FileAssembler()]
+
+    def decode(self):
+        self.dec.decode_device(self.frames.data_ptr(), self.valid.data_ptr(), nf, self.cadu.data_ptr(), self.block.data_ptr(),
+                               self.info.data_ptr(), stream=st)
+
+    def demux(self):
+        self.dm.process_device(self.hits.data_ptr(), self.cadu.data_ptr(), self.block.data_ptr(), self.info.data_ptr(), nf,
+                               self.vcdu.data_ptr(), self.offsets.data_ptr(), self.records.data_ptr(), stream=st)
+
+    def packets(self):
+        self.pa.process_device(self.vcdu.data_ptr(), self.offsets.data_ptr(), nf, self.out_bytes.data_ptr(), self.max_bytes,
+                               self.out_desc.data_ptr(), self.max_packets, self.pkt_offsets.data_ptr(), self.summary.data_ptr(), stream=st)
+
+    def files(self):
+        self.fa.process_device(self.out_bytes.data_ptr(), self.max_bytes, self.out_desc.data_ptr(), self.pkt_offsets.data_ptr(),
+                               self.max_packets, self.f_bytes.data_ptr(), self.max_bytes, self.f_pieces.data_ptr(), self.max_packets,
+                               self.f_recs.data_ptr(), 2 * self.max_packets, self.f_summary.data_ptr(), stream=st)
+
+    def chain(self, *stages):
+        def run():
+            for s in stages:
+                s()
+        return run
+
+    def run_cases(self, first, cases):
+        """On fresh handles first() once, then every (name, fn, many) timed: args.reps calls after args.warmup, or a fifth
+        of them after 2."""
+        self.fresh_handles()
+        first()
+        torch.cuda.synchronize()
+        reps, warm = args.reps or 20, 3 if args.warmup is None else args.warmup
+        res = {}
+        for name, fn, many in cases:
+            res[name] = timed(fn, reps if many else max(3, reps // 5), warm if many else 2)
+        return res
+
+
+def bench_decode():
+    rng = np.random.default_rng(1)
+    base_n = min(256, nf)
+    blocks = [ccsds.make_block(0x8C, i % 64, i, rng) for i in range(base_n)]
+    clean16 = tiled(np.stack([ccsds.cadu_from_block(b) for b in blocks]), np.int16)
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    sigma = 40 / np.sqrt(2.0 * 10 ** (4.0 / 10))               # BPSK, Es/N0 = 4 dB
+    noisy = (clean16.float() + sigma * torch.randn(clean16.shape, device=dev, generator=g)).round().clamp(-128, 127).to(torch.int8)
+    clean = clean16.to(torch.int8)
+    del clean16
+    valid = torch.ones(nf, dtype=torch.uint8, device=dev)
+    cadu, block, info = u8(nf * 1024), u8(nf * 1020), u8(nf * xa.FRAME_INFO_DTYPE.itemsize)
+    for name, frames in (("clean", clean), ("esn0_4dB", noisy)):
+        dec = xa.FrameDecoder("lrit")
+        ms, mn = timed(lambda: dec.decode_device(frames.data_ptr(), valid.data_ptr(), nf, cadu.data_ptr(), block.data_ptr(),
+                                                 info.data_ptr(), stream=st), args.reps or 5, 2 if args.warmup is None else args.warmup)
+        inf = info.cpu().numpy().view(xa.FRAME_INFO_DTYPE)
+        emit(case=name, frames=nf, ms_median=round(ms, 3), ms_min=round(mn, 3), frames_per_ms=round(nf / ms, 1),
+             decoded_Mbit_per_s=round(nf * 8192 / ms / 1e3, 1), ok_frac=round(float(inf["ok"].mean()), 5),
+             mean_viterbi_errors=round(float(inf["viterbi_errors"].mean()), 2),
+             rs_corrections=int(np.where(inf["rs_errors"] > 0, inf["rs_errors"], 0).sum()))
+        dec.close()
+    if not args.no_cpu:
+        k = 4
+        w, _, _ = ccsds.windows(noisy[:k].cpu().numpy(), np.ones(k, np.uint8))
+        t = time.perf_counter()
+        ccsds.viterbi_batch(w)
+        s = time.perf_counter() - t
+        emit(case="numpy_viterbi_spec_one_core", frames=k, s=round(s, 3), frames_per_ms=round(k / s / 1e3, 5))
+
+
+def bench_demux():
+    c = Chain("random")
+    seen = {}
+
+    def first():
+        c.decode()
+        seen["info"] = c.info.cpu().numpy().view(xa.FRAME_INFO_DTYPE)
+
+    res = c.run_cases(first, (("demux", c.demux, True), ("decode+demux", c.chain(c.decode, c.demux), False)))
+    inf = seen["info"]
+    good = int(inf["ok"].sum())
+    moved = nf * (16 + 4 + 40 + 88) + good * (892 + 892)          # bytes read + written, the VCDUs twice
+    for name, (ms, mn) in res.items():
+        row = dict(case=name, frames=nf, good=good, channels=int((np.bincount(inf["vcid"][inf["ok"] == 1], minlength=64) > 0).sum()),
+                   ms_median=round(ms, 4), ms_min=round(mn, 4))
+        if name == "demux":
+            row.update(bound_ms=0.5, within_bound=ms <= 0.5, GB_per_s=round(moved / ms / 1e6, 1))
+        emit(**row)
+    emit(case="check", vcdu_rows=int(c.offsets.cpu().numpy()[64]), good=good, dropped=int(nf - good))
+
+
+def emit_times(res):
+    for name, (ms, mn) in res.items():
+        emit(case=name, frames=nf, ms_median=round(ms, 4), ms_min=round(mn, 4))
+    return {k: v[0] for k, v in res.items()}
+
+
+def bench_packets(c):
+    two, three = c.chain(c.decode, c.demux), c.chain(c.decode, c.demux, c.packets)
+    res = emit_times(c.run_cases(two, (("demux", c.demux, True), ("packets", c.packets, True), ("decode", c.decode, False),
+                                       ("decode+demux", two, False), ("decode+demux+packets", three, False))))
+    c.pa.reset()
+    c.packets()
+    torch.cuda.synchronize()
+    s = c.summary.cpu().numpy().view(xa.PACKETS_SUMMARY_DTYPE)[0]
+    moved = int(c.offsets.cpu().numpy()[64]) * 892 + int(s["bytes"]) + int(s["packets"]) * 32
+    emit(case="check", rows=int(s["rows"]), packets=int(s["packets"]), bytes=int(s["bytes"]), crc_failures=int(s["crc_failures"]),
+         discarded=int(s["discarded"]), fill_packets=int(s["fill_packets"]), overflow=int(s["overflow"]),
+         packets_GB_per_s=round(moved / res["packets"] / 1e6, 1), packets_share_of_decode_percent=round(100 * res["packets"] / res["decode"], 3),
+         chain_difference_ms=round(res["decode+demux+packets"] - res["decode+demux"], 4))
+
+
+def bench_files(c):
+    three = c.chain(c.decode, c.demux, c.packets)
+    res = emit_times(c.run_cases(three, (("packets", c.packets, True), ("files", c.files, True), ("decode+demux+packets", three, False),
+                                         ("decode+demux+packets+files", c.chain(three, c.files), False),
+                                         ("decode+demux+packets again", three, False))))
+    c.fa.reset()
+    c.pa.reset()
+    c.packets()
+    c.files()
+    torch.cuda.synchronize()
+    s = c.f_summary.cpu().numpy().view(xa.FILES_SUMMARY_DTYPE)[0]
+    p = c.summary.cpu().numpy().view(xa.PACKETS_SUMMARY_DTYPE)[0]
+    moved = int(p["bytes"]) + int(p["packets"]) * 32 + int(s["bytes"]) + int(s["pieces"]) * 32 + int(s["files"]) * 80
+    emit(case="files check", packets_in=int(p["packets"]), bytes_in=int(p["bytes"]), pieces=int(s["pieces"]), bytes=int(s["bytes"]),
+         records=int(s["files"]), files_begun=int(s["files_begun"]), files_completed=int(s["files_completed"]),
+         bad_packets=int(s["bad_packets"]), short_first=int(s["short_first"]), orphans=int(s["orphans"]), overflow=int(s["overflow"]),
+         files_GB_per_s=round(moved / res["files"] / 1e6, 1),
+         chain_difference_ms=round(res["decode+demux+packets+files"] - res["decode+demux+packets"], 4))
+
+
+def bench_rice():
+    n, J, S, L = 8, 16, args.samples, args.lines
+    rng = np.random.default_rng(2)
+    stats = {}
+    distinct = [rs.random_line(rng, n, J, S, kind=rs.KINDS[i % len(rs.KINDS)], stats=stats)[1] for i in range(min(512, L))]
+    data, desc = rs.pack([distinct[i % len(distinct)] for i in range(L)])
+    d_data = torch.from_numpy(data.copy()).to(dev)
+    d_desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    d_out = torch.empty(L * S, dtype=torch.uint8, device=dev)
+    d_status = torch.empty(L, dtype=torch.uint8, device=dev)
+    rd = xa.RiceDecoder(n, J, S)
+    want = rs.decode_batch(distinct[:8], n, J, S)[0]
+    probe = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
+    hbm = xa._capi.device_read_bandwidth(probe.data_ptr(), probe.numel(), reps=10, stream=st)
+    moved = len(data) + L * S + L * 17
+    for form in ("lane", "wave", "default"):
+        xa.rice_form(form)
+        d_out.zero_()
+        ms, mn = timed(lambda: rd.decode_device(d_data.data_ptr(), len(data), d_desc.data_ptr(), 16, L, d_out.data_ptr(), d_status.data_ptr(),
+                                                stream=st), args.reps or 20, 3 if args.warmup is None else args.warmup)
+        assert np.array_equal(d_out.cpu().numpy().reshape(L, S)[:8], want) and not d_status.cpu().numpy().any()
+        emit(case="rice", form=form, bits=n, block=J, samples=S, lines=L, bytes_in=len(data),
+             options={str(k): v for k, v in sorted(stats.items(), key=str)}, ms_median=round(ms, 4), ms_min=round(mn, 4),
+             Msamples_per_s=round(L * S / ms / 1e3, 1), GB_per_s_in_plus_out=round(moved / ms / 1e6, 2),
+             device_read_GB_per_s=round(hbm, 1), fraction_of_read_rate=round(moved / ms / 1e6 / hbm, 5))
+
+
+shared = []                                     # the packets and the files cases run on one stream of frames
+
+
+def packet_chain():
+    if not shared:
+        shared.append(Chain("packets"))
+    return shared[0]
+
+
+for what in ["decode", "demux", "packets", "files", "rice"] if args.what == "all" else [args.what]:
+    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "packets": lambda: bench_packets(packet_chain()),
+     "files": lambda: bench_files(packet_chain())}[what]()

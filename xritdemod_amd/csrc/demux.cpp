@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "stage_handle.h"
 
 using namespace xrit;
 
@@ -17,12 +18,6 @@ static_assert(sizeof(xrit_decoder_stats) == 5 * 8 + 3 * 256 * 8 + 8, "xrit_decod
 static_assert(sizeof(xrit_sync_hit) == 16 && sizeof(xrit_frame_info) == 40, "decoder record layouts");
 
 namespace {
-constexpr size_t DM_CADU = 1024, DM_BLOCK = 1020, DM_VCDU = 892;
-constexpr size_t DM_MAX_FRAMES = (size_t)1 << 24;   // the decoder's DEC_MAX_FRAMES
-constexpr int NVC = 64;
-
-size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
-
 DemuxState start_state()
 {
     DemuxState s{};
@@ -35,70 +30,29 @@ DemuxState start_state()
 }
 }  // namespace
 
-struct xrit_demux {
-    int device = 0;
+struct xrit_demux : StageHandle {
     uint32_t start_time = 0;
-    hipStream_t stream = nullptr;                   // the host-buffer path's
-    void *last_stream = nullptr;                    // the stream of the most recent call (reset and stats wait for it)
     DevBuf state, scratch;
     DevBuf h_hits, h_cadu, h_block, h_info, h_vcdu, h_offsets, h_records;
+    void close_all() { close({&state, &scratch, &h_hits, &h_cadu, &h_block, &h_info, &h_vcdu, &h_offsets, &h_records}); }
 };
-
-static int upload_start_state(xrit_demux *dm)
-{
-    static const DemuxState s0 = start_state();
-    XR_HIP(hipMemcpyAsync(dm->state.p, &s0, sizeof s0, hipMemcpyHostToDevice, dm->stream));
-    XR_HIP(hipStreamSynchronize(dm->stream));
-    dm->last_stream = dm->stream;
-    return XRIT_OK;
-}
 
 int xrit_demux_create(xrit_demux **out, int device)
 {
-    if (!out) { set_error("null argument"); return XRIT_E_INVALID; }
-    *out = nullptr;
-    XR_TRY(select_device(device));
-    xrit_demux *dm = new (std::nothrow) xrit_demux;
-    if (!dm) { set_error("out of host memory"); return XRIT_E_NOMEM; }
-    dm->device = device;
-    dm->start_time = (uint32_t)std::time(nullptr);   // Statistics::Statistics(), Statistics.cpp: getTimestamp()
-    int rc = dm->state.reserve(sizeof(DemuxState));
-    if (rc == XRIT_OK && hipStreamCreateWithFlags(&dm->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipStreamCreate failed");
-        dm->stream = nullptr;
-        rc = XRIT_E_HIP;
-    }
-    if (rc == XRIT_OK) rc = upload_start_state(dm);
-    if (rc != XRIT_OK) {
-        xrit_demux_destroy(dm);
-        return rc;
-    }
-    *out = dm;
-    return XRIT_OK;
+    return stage_create(out, device, [](xrit_demux &dm) {
+        dm.start_time = (uint32_t)std::time(nullptr);   // Statistics::Statistics(), Statistics.cpp: getTimestamp()
+        XR_TRY(dm.state.reserve(sizeof(DemuxState)));
+        return xrit_demux_reset(&dm);
+    });
 }
 
-int xrit_demux_destroy(xrit_demux *dm)
-{
-    if (!dm) return XRIT_OK;
-    (void)hipSetDevice(dm->device);
-    if (dm->stream) {
-        (void)hipStreamSynchronize(dm->stream);
-        (void)hipStreamDestroy(dm->stream);
-    }
-    if (dm->last_stream && dm->last_stream != dm->stream) (void)hipStreamSynchronize((hipStream_t)dm->last_stream);
-    for (DevBuf *b : {&dm->state, &dm->scratch, &dm->h_hits, &dm->h_cadu, &dm->h_block, &dm->h_info, &dm->h_vcdu,
-                      &dm->h_offsets, &dm->h_records})
-        b->release();
-    delete dm;
-    return XRIT_OK;
-}
+int xrit_demux_destroy(xrit_demux *dm) { return stage_destroy(dm); }
 
 int xrit_demux_reset(xrit_demux *dm)
 {
     if (!dm) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(dm->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)dm->last_stream));
-    return upload_start_state(dm);
+    static const DemuxState s0 = start_state();
+    return dm->write_state(dm->state.p, &s0, sizeof s0);
 }
 
 // the device path with the cadu rows `cadu_stride` bytes apart (the host path uploads only their first four bytes)
@@ -106,22 +60,12 @@ static int demux_run(xrit_demux *dm, const xrit_sync_hit *d_hits, const uint8_t 
                      const uint8_t *d_block, const xrit_frame_info *d_info, size_t nf, uint8_t *d_vcdu, uint32_t *d_offsets,
                      xrit_frame_stats *d_records, hipStream_t s)
 {
-    const size_t T = (nf + DEMUX_TILE - 1) / DEMUX_TILE;
-    const size_t a64 = align8(T * NVC * 4), a4 = align8(T * 4 * 4), a5 = T * 5 * 8;
-    XR_TRY(dm->scratch.reserve(5 * a64 + a4 + a5 + 2 * NVC * 8));
-    char *p = dm->scratch.as<char>();
     DemuxScratch sc;
-    sc.cnt = reinterpret_cast<unsigned *>(p);
-    sc.firstc = reinterpret_cast<int *>(p + a64);
-    sc.lastc = reinterpret_cast<int *>(p + 2 * a64);
-    sc.base = reinterpret_cast<unsigned *>(p + 3 * a64);
-    sc.P = reinterpret_cast<int *>(p + 4 * a64);
-    sc.tsum = reinterpret_cast<unsigned *>(p + 5 * a64);
-    sc.tin = reinterpret_cast<unsigned long long *>(p + 5 * a64 + a4);
-    sc.vcb = reinterpret_cast<long long *>(p + 5 * a64 + a4 + a5);
+    XR_TRY(dm->scratch.reserve(demux_scratch_carve(nullptr, nf, sc)));
+    demux_scratch_carve(dm->scratch.p, nf, sc);
     XR_TRY(launch_demux(d_hits, d_cadu, cadu_stride, d_block, d_info, nf, dm->state.as<DemuxState>(), sc, d_vcdu, d_offsets,
                         d_records, s));
-    dm->last_stream = s;
+    dm->ran_on(s);
     return XRIT_OK;
 }
 
@@ -136,13 +80,13 @@ int xrit_demux_process_device(xrit_demux *dm, const xrit_sync_hit *d_hits, const
         set_error("null argument");
         return XRIT_E_INVALID;
     }
-    if (nf > DM_MAX_FRAMES) { set_error("demux: at most %zu frames per call", DM_MAX_FRAMES); return XRIT_E_INVALID; }
+    if (nf > MAX_ROWS_PER_CALL) { set_error("demux: at most %zu frames per call", MAX_ROWS_PER_CALL); return XRIT_E_INVALID; }
     if (((size_t)d_cadu | (size_t)d_block | (size_t)d_vcdu) & 3) {
         set_error("demux: cadu, block and vcdu must be 4-byte aligned");
         return XRIT_E_INVALID;
     }
     XR_HIP(hipSetDevice(dm->device));
-    return demux_run(dm, d_hits, d_cadu, DM_CADU, d_block, d_info, nf, d_vcdu, d_offsets, d_records, (hipStream_t)stream);
+    return demux_run(dm, d_hits, d_cadu, CADU_BYTES, d_block, d_info, nf, d_vcdu, d_offsets, d_records, (hipStream_t)stream);
 }
 
 int xrit_demux_process(xrit_demux *dm, const xrit_sync_hit *hits, const uint8_t *cadu, const uint8_t *block,
@@ -153,31 +97,30 @@ int xrit_demux_process(xrit_demux *dm, const xrit_sync_hit *hits, const uint8_t 
         set_error("null argument");
         return XRIT_E_INVALID;
     }
-    if (nf > DM_MAX_FRAMES) { set_error("demux: at most %zu frames per call", DM_MAX_FRAMES); return XRIT_E_INVALID; }
+    if (nf > MAX_ROWS_PER_CALL) { set_error("demux: at most %zu frames per call", MAX_ROWS_PER_CALL); return XRIT_E_INVALID; }
     if (nf == 0) {
         if (offsets) std::memset(offsets, 0, (NVC + 1) * sizeof(uint32_t));
         return XRIT_OK;
     }
-    XR_HIP(hipSetDevice(dm->device));
+    hipStream_t s;
+    XR_TRY(dm->adopt_own_stream(s));
     size_t good = 0;                                 // the rows the call writes: known before it runs
     for (size_t f = 0; f < nf; ++f) good += (info[f].valid && info[f].ok) ? 1 : 0;
     XR_TRY(dm->h_hits.reserve(nf * sizeof(xrit_sync_hit)));
     XR_TRY(dm->h_cadu.reserve(nf * 4));
-    XR_TRY(dm->h_block.reserve(nf * DM_BLOCK));
+    XR_TRY(dm->h_block.reserve(nf * BLOCK_BYTES));
     XR_TRY(dm->h_info.reserve(nf * sizeof(xrit_frame_info)));
-    XR_TRY(dm->h_vcdu.reserve(nf * DM_VCDU));
+    XR_TRY(dm->h_vcdu.reserve(nf * VCDU_BYTES));
     XR_TRY(dm->h_offsets.reserve((NVC + 1) * sizeof(uint32_t)));
     XR_TRY(dm->h_records.reserve(nf * sizeof(xrit_frame_stats)));
-    hipStream_t s = dm->stream;
-    if (dm->last_stream != dm->stream) XR_HIP(hipStreamSynchronize((hipStream_t)dm->last_stream));   // the state's last writer
     XR_HIP(hipMemcpyAsync(dm->h_hits.p, hits, nf * sizeof(xrit_sync_hit), hipMemcpyHostToDevice, s));
-    XR_HIP(hipMemcpy2DAsync(dm->h_cadu.p, 4, cadu, DM_CADU, 4, nf, hipMemcpyHostToDevice, s));       // syncWord only
-    XR_HIP(hipMemcpyAsync(dm->h_block.p, block, nf * DM_BLOCK, hipMemcpyHostToDevice, s));
+    XR_HIP(hipMemcpy2DAsync(dm->h_cadu.p, 4, cadu, CADU_BYTES, 4, nf, hipMemcpyHostToDevice, s));       // syncWord only
+    XR_HIP(hipMemcpyAsync(dm->h_block.p, block, nf * BLOCK_BYTES, hipMemcpyHostToDevice, s));
     XR_HIP(hipMemcpyAsync(dm->h_info.p, info, nf * sizeof(xrit_frame_info), hipMemcpyHostToDevice, s));
     XR_TRY(demux_run(dm, dm->h_hits.as<xrit_sync_hit>(), dm->h_cadu.as<uint8_t>(), 4, dm->h_block.as<uint8_t>(),
                      dm->h_info.as<xrit_frame_info>(), nf, dm->h_vcdu.as<uint8_t>(), dm->h_offsets.as<uint32_t>(),
                      dm->h_records.as<xrit_frame_stats>(), s));
-    if (good) XR_HIP(hipMemcpyAsync(vcdu, dm->h_vcdu.p, good * DM_VCDU, hipMemcpyDeviceToHost, s));
+    if (good) XR_HIP(hipMemcpyAsync(vcdu, dm->h_vcdu.p, good * VCDU_BYTES, hipMemcpyDeviceToHost, s));
     XR_HIP(hipMemcpyAsync(offsets, dm->h_offsets.p, (NVC + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     XR_HIP(hipMemcpyAsync(records, dm->h_records.p, nf * sizeof(xrit_frame_stats), hipMemcpyDeviceToHost, s));
     XR_HIP(hipStreamSynchronize(s));
@@ -187,11 +130,8 @@ int xrit_demux_process(xrit_demux *dm, const xrit_sync_hit *hits, const uint8_t 
 int xrit_demux_stats(xrit_demux *dm, xrit_decoder_stats *out)
 {
     if (!dm || !out) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(dm->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)dm->last_stream));
     DemuxState s;
-    XR_HIP(hipMemcpyAsync(&s, dm->state.p, sizeof s, hipMemcpyDeviceToHost, dm->stream));
-    XR_HIP(hipStreamSynchronize(dm->stream));
+    XR_TRY(dm->read_back(&s, dm->state.p, sizeof s));
     std::memset(out, 0, sizeof *out);
     out->total_packets = s.frames;
     out->dropped_packets = s.dropped;

@@ -14,13 +14,13 @@
 // is no predecessor), so the per-channel sum telescopes: lostPerVC[v] after the K-th good frame of v in the call is
 // lost_in[v] + c - P0[v] - K, and the call adds last - P0 - count.  Everything is integer; no atomics.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
 namespace {
 constexpr int TILE = DEMUX_TILE;            // frames per tile = threads per workgroup
 constexpr int WAVES = TILE / 64;
-constexpr int NVC = 64;
 constexpr int DEMUX_PARTS = 4;              // scatter workgroups per tile (each ranks the whole tile, copies a quarter)
 
 // lanes of this wave whose frame is good and on the same VCID (0 for a lane that is not good)
@@ -56,20 +56,6 @@ __device__ __forceinline__ Frame load_frame(const xrit_frame_info *info, size_t 
     return q;
 }
 
-template <typename T> __device__ __forceinline__ T wave_sum(T x)
-{
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
-template <typename T> __device__ __forceinline__ T wave_incl_scan(T x, int lane)
-{
-    for (int off = 1; off < 64; off <<= 1) {
-        const T y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
 }  // namespace
 
 // (a) ------------------------------------------------------------------------------------------------------------------
@@ -360,6 +346,22 @@ __global__ void __launch_bounds__(1024) demux_scatter_kernel(const xrit_sync_hit
         for (int u = 0; u < 8; ++u)
             if (dr[u] != 0xFFFFFFFFu) dst32[dr[u]] = x[u];
     }
+}
+
+// T tiles: what (a) leaves for (b), then what (b) leaves for (c)
+size_t demux_scratch_carve(void *base, size_t nf, DemuxScratch &sc)
+{
+    const size_t T = div_up(nf, TILE);
+    Carver c{static_cast<char *>(base)};
+    sc.cnt = c.take<unsigned>(T * NVC, 8);
+    sc.firstc = c.take<int>(T * NVC, 8);
+    sc.lastc = c.take<int>(T * NVC, 8);
+    sc.base = c.take<unsigned>(T * NVC, 8);
+    sc.P = c.take<int>(T * NVC, 8);
+    sc.tsum = c.take<unsigned>(T * 4, 8);
+    sc.tin = c.take<unsigned long long>(T * 5, 8);
+    sc.vcb = c.take<long long>(2 * NVC, 8);
+    return c.used();
 }
 
 int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "stage_handle.h"
 
 using namespace xrit;
 
@@ -23,85 +24,43 @@ static_assert(sizeof(xrit_file_key) == 56 && offsetof(xrit_file_key, next_seq) =
               "xrit_file_key layout");
 
 namespace {
-constexpr int NVC = 64;
 constexpr size_t STATE_BYTES = (size_t)FILES_KEYS * sizeof(xrit_file_key) + sizeof(xrit_files_counters);
 }
 
-struct xrit_files {
-    int device = 0;
-    hipStream_t stream = nullptr;                   // the host-buffer path's
-    void *last_stream = nullptr;                    // the stream of the most recent call (reset and stats wait for it)
+struct xrit_files : StageHandle {
     DevBuf state, scratch;                          // the keys, then the counters
     DevBuf h_in, h_packets, h_offsets, h_bytes, h_pieces, h_files, h_summary;
     xrit_file_key *keys() const { return state.as<xrit_file_key>(); }
     xrit_files_counters *counters() const { return reinterpret_cast<xrit_files_counters *>(keys() + FILES_KEYS); }
+    void close_all() { close({&state, &scratch, &h_in, &h_packets, &h_offsets, &h_bytes, &h_pieces, &h_files, &h_summary}); }
 };
-
-static int clear_state(xrit_files *fa)
-{
-    XR_HIP(hipMemsetAsync(fa->state.p, 0, STATE_BYTES, fa->stream));
-    XR_HIP(hipStreamSynchronize(fa->stream));
-    fa->last_stream = fa->stream;
-    return XRIT_OK;
-}
 
 int xrit_files_create(xrit_files **out, int device)
 {
-    if (!out) { set_error("null argument"); return XRIT_E_INVALID; }
-    *out = nullptr;
-    XR_TRY(select_device(device));
-    xrit_files *fa = new (std::nothrow) xrit_files;
-    if (!fa) { set_error("out of host memory"); return XRIT_E_NOMEM; }
-    fa->device = device;
-    int rc = fa->state.reserve(STATE_BYTES);
-    if (rc == XRIT_OK && hipStreamCreateWithFlags(&fa->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipStreamCreate failed");
-        fa->stream = nullptr;
-        rc = XRIT_E_HIP;
-    }
-    if (rc == XRIT_OK) rc = clear_state(fa);
-    if (rc != XRIT_OK) {
-        xrit_files_destroy(fa);
-        return rc;
-    }
-    *out = fa;
-    return XRIT_OK;
+    return stage_create(out, device, [](xrit_files &fa) {
+        XR_TRY(fa.state.reserve(STATE_BYTES));
+        return xrit_files_reset(&fa);
+    });
 }
 
-int xrit_files_destroy(xrit_files *fa)
-{
-    if (!fa) return XRIT_OK;
-    (void)hipSetDevice(fa->device);
-    if (fa->stream) {
-        (void)hipStreamSynchronize(fa->stream);
-        (void)hipStreamDestroy(fa->stream);
-    }
-    if (fa->last_stream && fa->last_stream != fa->stream) (void)hipStreamSynchronize((hipStream_t)fa->last_stream);
-    for (DevBuf *b : {&fa->state, &fa->scratch, &fa->h_in, &fa->h_packets, &fa->h_offsets, &fa->h_bytes, &fa->h_pieces, &fa->h_files,
-                      &fa->h_summary})
-        b->release();
-    delete fa;
-    return XRIT_OK;
-}
+int xrit_files_destroy(xrit_files *fa) { return stage_destroy(fa); }
 
 int xrit_files_reset(xrit_files *fa)
 {
     if (!fa) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(fa->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)fa->last_stream));
-    return clear_state(fa);
+    return fa->write_state(fa->state.p, nullptr, STATE_BYTES);
 }
 
 static int files_run(xrit_files *fa, const uint8_t *d_in, size_t in_bytes, const xrit_packet *d_packets, const uint32_t *d_pkt_offsets,
                      size_t max_in, uint8_t *d_bytes, size_t max_bytes, xrit_file_piece *d_pieces, size_t max_pieces,
                      xrit_file_record *d_files, size_t max_files, xrit_files_summary *d_summary, hipStream_t s)
 {
-    XR_TRY(fa->scratch.reserve(files_scratch_bytes(max_in)));
     FilesScratch sc;
+    XR_TRY(fa->scratch.reserve(files_scratch_carve(nullptr, max_in, sc)));
     files_scratch_carve(fa->scratch.p, max_in, sc);
     XR_TRY(launch_files(d_in, in_bytes, d_packets, d_pkt_offsets, max_in, fa->keys(), fa->counters(), sc, d_bytes, max_bytes, d_pieces,
                         max_pieces, d_files, max_files, d_summary, s));
-    fa->last_stream = s;
+    fa->ran_on(s);
     return XRIT_OK;
 }
 
@@ -140,7 +99,8 @@ int xrit_files_process(xrit_files *fa, const uint8_t *in_bytes, size_t n_in_byte
     const size_t n = pkt_offsets[NVC];
     if (n && !packets) { set_error("null argument"); return XRIT_E_INVALID; }
     if (n > XRIT_FILES_MAX_PACKETS) { set_error("files: at most %zu packets per call", XRIT_FILES_MAX_PACKETS); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(fa->device));
+    hipStream_t s;
+    XR_TRY(fa->adopt_own_stream(s));
     // no call emits more than this, so the device side of a generous host buffer stays small
     const size_t bound_files = XRIT_FILES_MAX_FILES(n);
     const size_t cap_bytes = max_bytes < n_in_bytes ? max_bytes : n_in_bytes;
@@ -153,49 +113,28 @@ int xrit_files_process(xrit_files *fa, const uint8_t *in_bytes, size_t n_in_byte
     XR_TRY(fa->h_pieces.reserve(cap_pieces * sizeof(xrit_file_piece) + 8));
     XR_TRY(fa->h_files.reserve(cap_files * sizeof(xrit_file_record) + 8));
     XR_TRY(fa->h_summary.reserve(sizeof(xrit_files_summary)));
-    hipStream_t s = fa->stream;
-    if (fa->last_stream != fa->stream) XR_HIP(hipStreamSynchronize((hipStream_t)fa->last_stream));   // the state's last writer
     if (n_in_bytes) XR_HIP(hipMemcpyAsync(fa->h_in.p, in_bytes, n_in_bytes, hipMemcpyHostToDevice, s));
     if (n) XR_HIP(hipMemcpyAsync(fa->h_packets.p, packets, n * sizeof(xrit_packet), hipMemcpyHostToDevice, s));
     XR_HIP(hipMemcpyAsync(fa->h_offsets.p, pkt_offsets, (NVC + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     XR_TRY(files_run(fa, fa->h_in.as<uint8_t>(), n_in_bytes, fa->h_packets.as<xrit_packet>(), fa->h_offsets.as<uint32_t>(), n,
                      fa->h_bytes.as<uint8_t>(), cap_bytes, fa->h_pieces.as<xrit_file_piece>(), cap_pieces,
                      fa->h_files.as<xrit_file_record>(), cap_files, fa->h_summary.as<xrit_files_summary>(), s));
-    XR_HIP(hipMemcpyAsync(summary, fa->h_summary.p, sizeof *summary, hipMemcpyDeviceToHost, s));
-    XR_HIP(hipStreamSynchronize(s));
     // the written prefix: descriptors and records below their capacities; bytes up to the capacity (a piece's bytes are
     // written iff it fits whole, so what lies beyond the last one that fits is not meaningful)
-    const size_t np = summary->pieces < cap_pieces ? (size_t)summary->pieces : cap_pieces;
-    const size_t nf = summary->files < cap_files ? (size_t)summary->files : cap_files;
-    const size_t nb = summary->bytes < cap_bytes ? (size_t)summary->bytes : cap_bytes;
-    if (np) XR_HIP(hipMemcpyAsync(pieces, fa->h_pieces.p, np * sizeof(xrit_file_piece), hipMemcpyDeviceToHost, s));
-    if (nf) XR_HIP(hipMemcpyAsync(files, fa->h_files.p, nf * sizeof(xrit_file_record), hipMemcpyDeviceToHost, s));
-    if (nb) XR_HIP(hipMemcpyAsync(bytes, fa->h_bytes.p, nb, hipMemcpyDeviceToHost, s));
-    XR_HIP(hipStreamSynchronize(s));
-    if (summary->overflow) {
-        set_error("files: %llu pieces, %llu bytes, %llu records: the output buffers are too small", (unsigned long long)summary->pieces,
-                  (unsigned long long)summary->bytes, (unsigned long long)summary->files);
-        return XRIT_E_CAPACITY;
-    }
-    return XRIT_OK;
+    return download_written(s, "files", summary, fa->h_summary.p, sizeof *summary, &summary->overflow,
+                            {{pieces, fa->h_pieces.p, sizeof(xrit_file_piece), &summary->pieces, cap_pieces, "pieces"},
+                             {bytes, fa->h_bytes.p, 1, &summary->bytes, cap_bytes, "bytes"},
+                             {files, fa->h_files.p, sizeof(xrit_file_record), &summary->files, cap_files, "records"}});
 }
 
 int xrit_files_stats(xrit_files *fa, xrit_files_counters *out)
 {
     if (!fa || !out) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(fa->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)fa->last_stream));
-    XR_HIP(hipMemcpyAsync(out, fa->counters(), sizeof *out, hipMemcpyDeviceToHost, fa->stream));
-    XR_HIP(hipStreamSynchronize(fa->stream));
-    return XRIT_OK;
+    return fa->read_back(out, fa->counters(), sizeof *out);
 }
 
 int xrit_files_key(xrit_files *fa, unsigned vcid, unsigned apid, xrit_file_key *out)
 {
-    if (!fa || !out || vcid >= 64 || apid >= 2048) { set_error("files: null argument or no such key"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(fa->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)fa->last_stream));
-    XR_HIP(hipMemcpyAsync(out, fa->keys() + (size_t)vcid * 2048 + apid, sizeof *out, hipMemcpyDeviceToHost, fa->stream));
-    XR_HIP(hipStreamSynchronize(fa->stream));
-    return XRIT_OK;
+    if (!fa || !out || vcid >= (unsigned)NVC || apid >= 2048) { set_error("files: null argument or no such key"); return XRIT_E_INVALID; }
+    return fa->read_back(out, fa->keys() + (size_t)vcid * 2048 + apid, sizeof *out);
 }

@@ -19,7 +19,7 @@
 namespace xrit {
 
 namespace {
-constexpr unsigned NVC = 64, NAP = 2048;
+constexpr unsigned NAP = 2048;
 constexpr unsigned SORT_WAVES = 8, SORT_THREADS = 64 * SORT_WAVES;
 constexpr unsigned NCNT = 7;            // begun, completed, aborted, bad, gaps, short, orphans
 constexpr unsigned GPIECES = 8;
@@ -505,33 +505,23 @@ __global__ void __launch_bounds__(256) files_gather_kernel(const unsigned char *
     }
 }
 
-namespace {
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-}
-
-size_t files_scratch_bytes(size_t max_in)
+size_t files_scratch_carve(void *base, size_t max_in, FilesScratch &sc)
 {
     const size_t N = max_in ? max_in : 1;
-    return align16(N * 4) * 2 + align16(N * 8) * 2 + align16((size_t)FILES_KEYS * 4) * 4 + align16((size_t)FILES_KEYS * 8) +
-           align16((size_t)FILES_KEYS * NCNT * 4) + align16(64 * FILES_TSUM * 8) + align16(64 * 3 * 8);
-}
-
-void files_scratch_carve(void *base, size_t max_in, FilesScratch &sc)
-{
-    const size_t N = max_in ? max_in : 1;
-    char *p = static_cast<char *>(base);
-    sc.psrc = reinterpret_cast<unsigned long long *>(p); p += align16(N * 8);
-    sc.pdst = reinterpret_cast<unsigned long long *>(p); p += align16(N * 8);
-    sc.kbytes = reinterpret_cast<unsigned long long *>(p); p += align16((size_t)FILES_KEYS * 8);
-    sc.tsum = reinterpret_cast<unsigned long long *>(p); p += align16(64 * FILES_TSUM * 8);
-    sc.tbase = reinterpret_cast<unsigned long long *>(p); p += align16(64 * 3 * 8);
-    sc.order = reinterpret_cast<unsigned *>(p); p += align16(N * 4);
-    sc.plen = reinterpret_cast<unsigned *>(p); p += align16(N * 4);
-    sc.kstart = reinterpret_cast<unsigned *>(p); p += align16((size_t)FILES_KEYS * 4);
-    sc.kcount = reinterpret_cast<unsigned *>(p); p += align16((size_t)FILES_KEYS * 4);
-    sc.kpieces = reinterpret_cast<unsigned *>(p); p += align16((size_t)FILES_KEYS * 4);
-    sc.krecs = reinterpret_cast<unsigned *>(p); p += align16((size_t)FILES_KEYS * 4);
-    sc.kcnt = reinterpret_cast<unsigned *>(p);
+    Carver c{static_cast<char *>(base)};
+    sc.psrc = c.take<unsigned long long>(N, 16);
+    sc.pdst = c.take<unsigned long long>(N, 16);
+    sc.kbytes = c.take<unsigned long long>(FILES_KEYS, 16);
+    sc.tsum = c.take<unsigned long long>(64 * FILES_TSUM, 16);
+    sc.tbase = c.take<unsigned long long>(64 * 3, 16);
+    sc.order = c.take<unsigned>(N, 16);
+    sc.plen = c.take<unsigned>(N, 16);
+    sc.kstart = c.take<unsigned>(FILES_KEYS, 16);
+    sc.kcount = c.take<unsigned>(FILES_KEYS, 16);
+    sc.kpieces = c.take<unsigned>(FILES_KEYS, 16);
+    sc.krecs = c.take<unsigned>(FILES_KEYS, 16);
+    sc.kcnt = c.take<unsigned>((size_t)FILES_KEYS * NCNT, 16);
+    return c.used();
 }
 
 int launch_files(const unsigned char *in_bytes, size_t n_in_bytes, const xrit_packet *packets, const unsigned *pkt_offsets,

@@ -440,6 +440,24 @@ int launch_sync_correlate(const int8_t *data, size_t n, const unsigned long long
 int launch_sync_fix(const int8_t *data, size_t n, const xrit_sync_hit *hits, unsigned frame, unsigned min_corr,
                     int8_t *frames, unsigned char *valid, hipStream_t s);
 int launch_quantize_i8(const float *in, int8_t *out, size_t n, hipStream_t s);
+// ---- the back end (decoder, demux, packets, files, rice) --------------------
+// frame geometry: soft symbols of a frame; bytes of a CADU, of the block behind its sync marker, of a VCDU (the block
+// without the RS parity) and of a VCDU's packet zone
+constexpr int FRAME_SYMBOLS = 16384, CADU_BYTES = 1024, BLOCK_BYTES = 1020, VCDU_BYTES = 892, ZONE_BYTES = 884;
+constexpr int NVC = 64;                                 // virtual channels
+constexpr size_t MAX_ROWS_PER_CALL = (size_t)1 << 24;   // frames, rows or lines one call takes at most
+// Hands out consecutive pieces of one scratch allocation; with p = nullptr it only counts the bytes.
+struct Carver {
+    char *p;
+    size_t n = 0;
+    template <class T> T *take(size_t count, size_t align)
+    {
+        T *r = p ? reinterpret_cast<T *>(p + n) : nullptr;
+        n += (count * sizeof(T) + align - 1) & ~(align - 1);
+        return r;
+    }
+    size_t used() const { return n; }
+};
 // decoder (viterbi.hip, rs.hip): decision words of one resident window; Viterbi + carry, then derandomiser + RS
 size_t viterbi_slot_bytes();
 int launch_viterbi(const int8_t *frames, const unsigned char *valid, size_t nf, int hrit, int8_t *carry, int *prev, int *last,
@@ -449,7 +467,7 @@ int launch_rs(const unsigned char *cadu, const unsigned char *valid, const unsig
 // demux (demux.hip): one tile of DEMUX_TILE frames per workgroup; the handle's state and the per-call scratch
 constexpr int DEMUX_TILE = 1024;
 struct DemuxState {                       // newdecoder.cpp:44-53, 133-137 (entries 64..255 are never touched)
-    long long last[64], received[64], lost[64];
+    long long last[NVC], received[NVC], lost[NVC];
     unsigned long long frames, dropped, sum_vit, sum_rs, lost_total;
 };
 struct DemuxScratch {
@@ -457,6 +475,7 @@ struct DemuxScratch {
     unsigned *base; int *P; unsigned long long *tin;         // (b): [T][64] x 2, [T][5]
     long long *vcb;                                          // (b): [2][64]
 };
+size_t demux_scratch_carve(void *p, size_t nf, DemuxScratch &sc);     // returns the bytes; p = nullptr: only that
 int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,
                  const xrit_frame_info *info, size_t nf, DemuxState *state, DemuxScratch &sc, unsigned char *vcdu,
                  unsigned *offsets, xrit_frame_stats *records, hipStream_t s);
@@ -480,8 +499,7 @@ struct PacketsScratch {
     unsigned long long *tbase_b;    // [T] ... and its byte offset
     unsigned *crcfail;              // [R] emitted packets of the row whose CRC does not match
 };
-size_t packets_scratch_bytes(size_t max_rows);
-void packets_scratch_carve(void *p, size_t max_rows, PacketsScratch &sc);
+size_t packets_scratch_carve(void *p, size_t max_rows, PacketsScratch &sc);
 int launch_packets(const unsigned char *vcdu, const unsigned *offsets, size_t max_rows, PacketsState *state,
                    unsigned char *pend, PacketsScratch &sc, unsigned char *bytes, size_t max_bytes, xrit_packet *packets,
                    size_t max_packets, unsigned *pkt_offsets, xrit_packets_summary *summary, hipStream_t s);
@@ -499,8 +517,7 @@ struct FilesScratch {
     unsigned long long *psrc, *pdst;// [N] per piece: where its payload lies in the input, where it goes
     unsigned *plen;                 // [N]
 };
-size_t files_scratch_bytes(size_t max_in);
-void files_scratch_carve(void *p, size_t max_in, FilesScratch &sc);
+size_t files_scratch_carve(void *p, size_t max_in, FilesScratch &sc);
 int launch_files(const unsigned char *in_bytes, size_t n_in_bytes, const xrit_packet *packets, const unsigned *pkt_offsets,
                  size_t max_in, xrit_file_key *keys, xrit_files_counters *counters, FilesScratch &sc, unsigned char *bytes,
                  size_t max_bytes, xrit_file_piece *pieces, size_t max_pieces, xrit_file_record *files, size_t max_files,

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "stage_handle.h"
 
 using namespace xrit;
 
@@ -15,10 +16,6 @@ static_assert(sizeof(xrit_packets_summary) == 72 && offsetof(xrit_packets_summar
 static_assert(sizeof(xrit_packets_counters) == 48 + 6 * 512 + 512 + 2 * 256, "xrit_packets_counters layout");
 
 namespace {
-constexpr size_t PK_ROW = 892;
-constexpr size_t PK_MAX_ROWS = (size_t)1 << 24;     // as the demux
-constexpr int NVC = 64;
-
 PacketsState start_state()
 {
     PacketsState s{};
@@ -27,81 +24,40 @@ PacketsState start_state()
 }
 }  // namespace
 
-struct xrit_packets {
-    int device = 0;
-    hipStream_t stream = nullptr;                   // the host-buffer path's
-    void *last_stream = nullptr;                    // the stream of the most recent call (reset and stats wait for it)
+struct xrit_packets : StageHandle {
     DevBuf state, pend, scratch;
     DevBuf h_vcdu, h_offsets, h_bytes, h_packets, h_pkt_offsets, h_summary;
+    void close_all() { close({&state, &pend, &scratch, &h_vcdu, &h_offsets, &h_bytes, &h_packets, &h_pkt_offsets, &h_summary}); }
 };
-
-static int upload_start_state(xrit_packets *pa)
-{
-    static const PacketsState s0 = start_state();
-    XR_HIP(hipMemcpyAsync(pa->state.p, &s0, sizeof s0, hipMemcpyHostToDevice, pa->stream));
-    XR_HIP(hipStreamSynchronize(pa->stream));
-    pa->last_stream = pa->stream;
-    return XRIT_OK;
-}
 
 int xrit_packets_create(xrit_packets **out, int device)
 {
-    if (!out) { set_error("null argument"); return XRIT_E_INVALID; }
-    *out = nullptr;
-    XR_TRY(select_device(device));
-    xrit_packets *pa = new (std::nothrow) xrit_packets;
-    if (!pa) { set_error("out of host memory"); return XRIT_E_NOMEM; }
-    pa->device = device;
-    int rc = pa->state.reserve(sizeof(PacketsState));
-    if (rc == XRIT_OK) rc = pa->pend.reserve((size_t)NVC * PACKETS_PEND_STRIDE);
-    if (rc == XRIT_OK && hipStreamCreateWithFlags(&pa->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipStreamCreate failed");
-        pa->stream = nullptr;
-        rc = XRIT_E_HIP;
-    }
-    if (rc == XRIT_OK) rc = upload_start_state(pa);
-    if (rc != XRIT_OK) {
-        xrit_packets_destroy(pa);
-        return rc;
-    }
-    *out = pa;
-    return XRIT_OK;
+    return stage_create(out, device, [](xrit_packets &pa) {
+        XR_TRY(pa.state.reserve(sizeof(PacketsState)));
+        XR_TRY(pa.pend.reserve((size_t)NVC * PACKETS_PEND_STRIDE));
+        return xrit_packets_reset(&pa);
+    });
 }
 
-int xrit_packets_destroy(xrit_packets *pa)
-{
-    if (!pa) return XRIT_OK;
-    (void)hipSetDevice(pa->device);
-    if (pa->stream) {
-        (void)hipStreamSynchronize(pa->stream);
-        (void)hipStreamDestroy(pa->stream);
-    }
-    if (pa->last_stream && pa->last_stream != pa->stream) (void)hipStreamSynchronize((hipStream_t)pa->last_stream);
-    for (DevBuf *b : {&pa->state, &pa->pend, &pa->scratch, &pa->h_vcdu, &pa->h_offsets, &pa->h_bytes, &pa->h_packets,
-                      &pa->h_pkt_offsets, &pa->h_summary})
-        b->release();
-    delete pa;
-    return XRIT_OK;
-}
+int xrit_packets_destroy(xrit_packets *pa) { return stage_destroy(pa); }
 
 int xrit_packets_reset(xrit_packets *pa)
 {
     if (!pa) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(pa->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)pa->last_stream));
-    return upload_start_state(pa);
+    static const PacketsState s0 = start_state();
+    return pa->write_state(pa->state.p, &s0, sizeof s0);
 }
 
 static int packets_run(xrit_packets *pa, const uint8_t *d_vcdu, const uint32_t *d_offsets, size_t max_rows, uint8_t *d_bytes,
                        size_t max_bytes, xrit_packet *d_packets, size_t max_packets, uint32_t *d_pkt_offsets,
                        xrit_packets_summary *d_summary, hipStream_t s)
 {
-    XR_TRY(pa->scratch.reserve(packets_scratch_bytes(max_rows)));
     PacketsScratch sc;
+    XR_TRY(pa->scratch.reserve(packets_scratch_carve(nullptr, max_rows, sc)));
     packets_scratch_carve(pa->scratch.p, max_rows, sc);
     XR_TRY(launch_packets(d_vcdu, d_offsets, max_rows, pa->state.as<PacketsState>(), pa->pend.as<unsigned char>(), sc, d_bytes,
                           max_bytes, d_packets, max_packets, d_pkt_offsets, d_summary, s));
-    pa->last_stream = s;
+    pa->ran_on(s);
     return XRIT_OK;
 }
 
@@ -114,7 +70,7 @@ int xrit_packets_process_device(xrit_packets *pa, const uint8_t *d_vcdu, const u
         set_error("null argument");
         return XRIT_E_INVALID;
     }
-    if (max_rows > PK_MAX_ROWS) { set_error("packets: at most %zu rows per call", PK_MAX_ROWS); return XRIT_E_INVALID; }
+    if (max_rows > MAX_ROWS_PER_CALL) { set_error("packets: at most %zu rows per call", MAX_ROWS_PER_CALL); return XRIT_E_INVALID; }
     if (((size_t)d_packets | (size_t)d_summary) & 7) {
         set_error("packets: the descriptors and the summary must be 8-byte aligned");
         return XRIT_E_INVALID;
@@ -133,50 +89,36 @@ int xrit_packets_process(xrit_packets *pa, const uint8_t *vcdu, const uint32_t *
     }
     const size_t rows = offsets[NVC];
     if (rows && !vcdu) { set_error("null argument"); return XRIT_E_INVALID; }
-    if (rows > PK_MAX_ROWS) { set_error("packets: at most %zu rows per call", PK_MAX_ROWS); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(pa->device));
+    if (rows > MAX_ROWS_PER_CALL) { set_error("packets: at most %zu rows per call", MAX_ROWS_PER_CALL); return XRIT_E_INVALID; }
+    hipStream_t s;
+    XR_TRY(pa->adopt_own_stream(s));
     // no call emits more than this, so the device side of a generous host buffer stays small
     const size_t bound_bytes = XRIT_PACKETS_MAX_BYTES(rows), bound_packets = 127 * rows + NVC;
     const size_t cap_bytes = max_bytes < bound_bytes ? max_bytes : bound_bytes;
     const size_t cap_packets = max_packets < bound_packets ? max_packets : bound_packets;
-    XR_TRY(pa->h_vcdu.reserve(rows * PK_ROW + 8));
+    XR_TRY(pa->h_vcdu.reserve(rows * VCDU_BYTES + 8));
     XR_TRY(pa->h_offsets.reserve((NVC + 1) * sizeof(uint32_t)));
     XR_TRY(pa->h_bytes.reserve(cap_bytes + 8));
     XR_TRY(pa->h_packets.reserve(cap_packets * sizeof(xrit_packet) + 8));
     XR_TRY(pa->h_pkt_offsets.reserve((NVC + 1) * sizeof(uint32_t)));
     XR_TRY(pa->h_summary.reserve(sizeof(xrit_packets_summary)));
-    hipStream_t s = pa->stream;
-    if (pa->last_stream != pa->stream) XR_HIP(hipStreamSynchronize((hipStream_t)pa->last_stream));   // the state's last writer
-    if (rows) XR_HIP(hipMemcpyAsync(pa->h_vcdu.p, vcdu, rows * PK_ROW, hipMemcpyHostToDevice, s));
+    if (rows) XR_HIP(hipMemcpyAsync(pa->h_vcdu.p, vcdu, rows * VCDU_BYTES, hipMemcpyHostToDevice, s));
     XR_HIP(hipMemcpyAsync(pa->h_offsets.p, offsets, (NVC + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     XR_TRY(packets_run(pa, pa->h_vcdu.as<uint8_t>(), pa->h_offsets.as<uint32_t>(), rows, pa->h_bytes.as<uint8_t>(), cap_bytes,
                        pa->h_packets.as<xrit_packet>(), cap_packets, pa->h_pkt_offsets.as<uint32_t>(),
                        pa->h_summary.as<xrit_packets_summary>(), s));
-    XR_HIP(hipMemcpyAsync(summary, pa->h_summary.p, sizeof *summary, hipMemcpyDeviceToHost, s));
     XR_HIP(hipMemcpyAsync(pkt_offsets, pa->h_pkt_offsets.p, (NVC + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    XR_HIP(hipStreamSynchronize(s));
     // the written prefix: descriptors below the capacity; bytes up to the end of the last packet that fits
-    const size_t np = summary->packets < cap_packets ? (size_t)summary->packets : cap_packets;
-    const size_t nb = summary->bytes < cap_bytes ? (size_t)summary->bytes : cap_bytes;
-    if (np) XR_HIP(hipMemcpyAsync(packets, pa->h_packets.p, np * sizeof(xrit_packet), hipMemcpyDeviceToHost, s));
-    if (nb) XR_HIP(hipMemcpyAsync(bytes, pa->h_bytes.p, nb, hipMemcpyDeviceToHost, s));
-    XR_HIP(hipStreamSynchronize(s));
-    if (summary->overflow) {
-        set_error("packets: %llu packets, %llu bytes: the output buffers are too small", (unsigned long long)summary->packets,
-                  (unsigned long long)summary->bytes);
-        return XRIT_E_CAPACITY;
-    }
-    return XRIT_OK;
+    return download_written(s, "packets", summary, pa->h_summary.p, sizeof *summary, &summary->overflow,
+                            {{packets, pa->h_packets.p, sizeof(xrit_packet), &summary->packets, cap_packets, "packets"},
+                             {bytes, pa->h_bytes.p, 1, &summary->bytes, cap_bytes, "bytes"}});
 }
 
 int xrit_packets_stats(xrit_packets *pa, xrit_packets_counters *out)
 {
     if (!pa || !out) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(pa->device));
-    XR_HIP(hipStreamSynchronize((hipStream_t)pa->last_stream));
     PacketsState s;
-    XR_HIP(hipMemcpyAsync(&s, pa->state.p, sizeof s, hipMemcpyDeviceToHost, pa->stream));
-    XR_HIP(hipStreamSynchronize(pa->stream));
+    XR_TRY(pa->read_back(&s, pa->state.p, sizeof s));
     std::memset(out, 0, sizeof *out);
     for (int v = 0; v < NVC; ++v) {
         out->packets += out->vc_packets[v] = s.packets[v];

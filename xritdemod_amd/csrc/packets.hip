@@ -21,11 +21,12 @@
 // Everything is integer; no atomics; every launch is sized from the host's bound on the row count and reads the count
 // itself from offsets[64] on the device.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
 namespace {
-constexpr unsigned ZONE = 884, ROW = 892, ZOFF = 8, NVC = 64, FILL_VC = 63;
+constexpr unsigned ZONE = ZONE_BYTES, ROW = VCDU_BYTES, ZOFF = 8, FILL_VC = 63;
 constexpr unsigned FHP_NONE = 2047, APID_FILL = 2047;
 constexpr unsigned ORG_NONE = 0, ORG_STATE = 1;     // origin of pending bytes: none, the handle's state, 2 + row
 constexpr unsigned FILL_BIT = 0x80000000u;
@@ -52,12 +53,6 @@ __device__ __forceinline__ unsigned channel_of(const unsigned *s_off, unsigned r
         if (s_off[mid] <= r) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-template <typename T> __device__ __forceinline__ T wave_sum(T x)
-{
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
 }
 
 // a * b mod x^16 + x^12 + x^5 + 1
@@ -559,31 +554,22 @@ __global__ void __launch_bounds__(64) packets_summary_kernel(const PacketsState 
     }
 }
 
-namespace {
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-}
-
-size_t packets_scratch_bytes(size_t max_rows)
+// spanB and newp lie together, state_disc behind them: one memset clears both
+size_t packets_scratch_carve(void *base, size_t max_rows, PacketsScratch &sc)
 {
     const size_t R = max_rows ? max_rows : 1, T = div_up(R, PACKETS_TILE);
-    return align16(R * 8) + 2 * align16(NVC * 8) + 4 * align16(R * 4) + 2 * align16(T * 8) + align16(T * 4);
-}
-
-// spanB and newp lie together: one memset clears both
-void packets_scratch_carve(void *base, size_t max_rows, PacketsScratch &sc)
-{
-    const size_t R = max_rows ? max_rows : 1, T = div_up(R, PACKETS_TILE);
-    char *p = static_cast<char *>(base);
-    sc.spanB = reinterpret_cast<uint2 *>(p); p += align16(R * 8);
-    sc.newp = reinterpret_cast<uint2 *>(p); p += align16(NVC * 8);
-    sc.state_disc = reinterpret_cast<unsigned *>(p); p += align16(NVC * 8);
-    sc.tsum = reinterpret_cast<uint2 *>(p); p += align16(T * 8);
-    sc.tbase_b = reinterpret_cast<unsigned long long *>(p); p += align16(T * 8);
-    sc.tbase_c = reinterpret_cast<unsigned *>(p); p += align16(T * 4);
-    sc.rowA = reinterpret_cast<unsigned *>(p); p += align16(R * 4);
-    sc.plocal = reinterpret_cast<unsigned *>(p); p += align16(R * 4);
-    sc.blocal = reinterpret_cast<unsigned *>(p); p += align16(R * 4);
-    sc.crcfail = reinterpret_cast<unsigned *>(p);
+    Carver c{static_cast<char *>(base)};
+    sc.spanB = c.take<uint2>(R, 16);
+    sc.newp = c.take<uint2>(NVC, 16);
+    sc.state_disc = c.take<unsigned>(2 * NVC, 16);      // (64 words used)
+    sc.tsum = c.take<uint2>(T, 16);
+    sc.tbase_b = c.take<unsigned long long>(T, 16);
+    sc.tbase_c = c.take<unsigned>(T, 16);
+    sc.rowA = c.take<unsigned>(R, 16);
+    sc.plocal = c.take<unsigned>(R, 16);
+    sc.blocal = c.take<unsigned>(R, 16);
+    sc.crcfail = c.take<unsigned>(R, 16);
+    return c.used();
 }
 
 int launch_packets(const unsigned char *vcdu, const unsigned *offsets, size_t max_rows, PacketsState *state, unsigned char *pend,
@@ -592,7 +578,7 @@ int launch_packets(const unsigned char *vcdu, const unsigned *offsets, size_t ma
 {
     const size_t R = max_rows ? max_rows : 1;
     const unsigned rows = (unsigned)max_rows;
-    XR_HIP(hipMemsetAsync(sc.spanB, 0, align16(R * 8) + align16(NVC * 8), s));
+    XR_HIP(hipMemsetAsync(sc.spanB, 0, (size_t)((char *)sc.state_disc - (char *)sc.spanB), s));
     hipLaunchKernelGGL(packets_walk_kernel, dim3(div_up(max_rows + NVC, 256)), dim3(256), 0, s, vcdu, offsets, rows, state, pend, sc.rowA,
                        sc.spanB, sc.newp, sc.state_disc);
     XR_HIP(hipGetLastError());

@@ -40,7 +40,7 @@ static int check_args(const void *bytes, size_t n_bytes, const void *desc, size_
         set_error("rice: bits per sample 1 .. 16, block 8 / 16 / 32 / 64, samples 1 .. 65535 (got %d, %d, %d)", n, J, S);
         return XRIT_E_ARG;
     }
-    if (stride < 16 || (stride & 7) || n_lines > ((size_t)1 << 24)) {
+    if (stride < 16 || (stride & 7) || n_lines > MAX_ROWS_PER_CALL) {
         set_error("rice: the descriptor stride is a multiple of 8 from 16 on, at most 2^24 lines per call");
         return XRIT_E_ARG;
     }

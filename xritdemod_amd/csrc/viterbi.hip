@@ -21,7 +21,7 @@
 
 namespace xrit {
 
-constexpr int VIT_FRAME = 16384;
+constexpr int VIT_FRAME = FRAME_SYMBOLS;
 constexpr int VIT_CARRY = 64;
 constexpr int VIT_STEPS = (VIT_FRAME + VIT_CARRY) / 2;       // 8224
 constexpr int VIT_CHUNKS = 129;                              // 32 + 128 * 64 steps
