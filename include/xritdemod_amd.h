@@ -350,6 +350,69 @@ int xrit_sync_fix_frames(const int8_t *symbols, size_t n_symbols, const xrit_syn
                          uint32_t min_correlation, int8_t *frames, uint8_t *valid, int device);
 
 /* ------------------------------------------------------------------------
+ * Stream frame synchroniser: the reference decoder's walk over a STREAM of
+ * soft symbols (newdecoder.cpp:212-270 with flywheelRecheck = 1), state in
+ * device memory.  Exact integer contract: DESIGN.md section 17 and
+ * tests/framer_spec.py.  The stream arrives in calls of any length; the
+ * handle keeps a cursor c (absolute offset, 0 at start) and the symbols from
+ * c on that are not consumed yet (at most 2 * frame - 66).  While
+ * c + frame <= symbols received:
+ *  - hit = the correlator's answer on stream[c .. c + frame) (as
+ *    xrit_sync_correlate gives it for that window);
+ *  - hit.correlation < min_correlation: a row with the hit, valid = 0, a zero
+ *    frame, start = c; c += frame (:244-247);
+ *  - else if c + hit.position + frame runs past the symbols received: stop,
+ *    the chunk is walked again in the next call (the reference blocks in
+ *    Receive);
+ *  - else a row with the hit, valid = 1, start = c + hit.position, the frame
+ *    stream[start .. start + frame), every byte XOR 0xFF when hit.word != 0 on
+ *    a LRIT handle (HRIT never inverts, :266-270); c = start + frame.
+ * The rows do not depend on how the stream is cut into calls.  A call of n
+ * symbols emits at most xrit_framer_rows(fr, n) = (n + 2 * frame - 66) / frame
+ * rows; the outputs hold that many rows, those from *count on are all-zero
+ * with valid = 0 -- what xrit_decoder_decode_device and
+ * xrit_demux_process_device treat as absent, so both can be queued behind a
+ * push with nf = xrit_framer_rows(fr, n) and no read-back.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_framer xrit_framer;
+typedef struct xrit_framer_counters {   /* 80 bytes */
+    uint64_t symbols;            /* received */
+    uint64_t cursor;             /* absolute offset of the next chunk */
+    uint64_t rows;               /* emitted, valid or not */
+    uint64_t frames;             /* rows with valid = 1 */
+    uint64_t dropped_chunks;     /* rows with valid = 0 */
+    uint64_t resyncs;            /* frames found at position != 0 */
+    uint64_t carry;              /* symbols held for the next call: symbols - cursor */
+    uint64_t rewalked_chunks;    /* chunks the joints had to walk again (the walkers' guess of the entry cursor missed) */
+    uint64_t adopted_chunks;     /* chunks taken over from a segment walker's record */
+    uint64_t calls;
+} xrit_framer_counters;
+#define XRIT_FRAMER_MAX_SYMBOLS ((size_t)1 << 30)   /* per call */
+
+/* hrit = 0: LRIT words (newdecoder.cpp:21-24), 1: HRIT; frame = 16384, min_correlation = 46 */
+int xrit_framer_create(xrit_framer **fr, int hrit, int device);
+int xrit_framer_destroy(xrit_framer *fr);
+/* frame 65 .. 2^20 symbols, min_correlation 0 .. 64; only before the handle's first push */
+int xrit_framer_set_frame(xrit_framer *fr, uint32_t frame, uint32_t min_correlation);
+/* chunks per walker segment (0: chosen per call, the power of two up to the square root of the call's chunks); the rows do not depend on it */
+int xrit_framer_set_segment(xrit_framer *fr, uint32_t chunks);
+/* cursor 0, nothing carried, counters zero; waits for the handle's last call */
+int xrit_framer_reset(xrit_framer *fr);
+/* rows the outputs of a call of n symbols must hold (0 for a null handle) */
+size_t xrit_framer_rows(const xrit_framer *fr, size_t n);
+/* device pointers, asynchronous on `stream`, no host synchronisation; cursor and carry are updated on the device.
+ * With rows = xrit_framer_rows(fr, n): d_frames rows * frame bytes, d_valid rows bytes, d_hits rows entries (raw, as
+ * the correlator found them), d_start rows entries (absolute offsets), d_count one entry: the rows emitted.
+ * n <= XRIT_FRAMER_MAX_SYMBOLS; n = 0 is a call like any other (d_symbols may then be null). */
+int xrit_framer_push_device(xrit_framer *fr, const int8_t *d_symbols, size_t n, int8_t *d_frames, uint8_t *d_valid,
+                            xrit_sync_hit *d_hits, uint64_t *d_start, uint32_t *d_count, void *stream);
+/* host buffers of the same sizes: one upload, one download; returns the rows emitted (>= 0) or an error code (< 0) */
+int xrit_framer_push(xrit_framer *fr, const int8_t *symbols, size_t n, int8_t *frames, uint8_t *valid, xrit_sync_hit *hits,
+                     uint64_t *start);
+/* the counters after the last call; waits for it */
+int xrit_framer_stats(xrit_framer *fr, xrit_framer_counters *out);
+
+/* ------------------------------------------------------------------------
  * Decoder: Viterbi27 + NRZ-M (HRIT) + DeRandomizer + 4 x RS(255,223), the
  * per-frame FEC of decoder/src/newdecoder.cpp:272-348 on the frames that
  * xrit_sync_fix_frames[_device] writes (16384 int8 symbols each, valid[nf]).

@@ -14,9 +14,13 @@ files    xrit_files_process_device on that case's packets (random bytes: nearly 
 rice     xrit_rice_decode_device: --lines x --samples 8-bit lines, J = 16, on both kernel forms and then on the default
          (512 distinct lines tiled, a fifth of each of the specification's five generators, so every option occurs), as
          Msamples/s and as a fraction of the device read rate measured in the same run on bytes in plus bytes out.
-all      the five, in this order.
+framer   xrit_framer_push_device (the stream frame synchroniser) on a frame-aligned LRIT stream of --frames frames, the same
+         stream with one symbol deleted every 50 frames, and what existed before it on the aligned stream:
+         xrit_sync_correlate_device + xrit_sync_fix_frames_device over fixed windows (calls of at most 65535 frames).  Then
+         the framer at other segment lengths, with the share of chunks its joints walked again.
+all      the six, in this order.
 
-    python scripts/bench_backend.py {decode,demux,packets,files,rice,all} [--frames N] [--reps R] [--warmup W]
+    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,all} [--frames N] [--reps R] [--warmup W]
                                     [--lines L] [--samples S] [--no-cpu]"""
 import argparse
 import json
@@ -35,7 +39,7 @@ import packet_spec as ps
 import rice_spec as rs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "all"])
+ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "all"])
 ap.add_argument("--frames", type=int, default=1 << 16)
 ap.add_argument("--reps", type=int, default=None, help="timed calls per case (decode: 5, the others: 20)")
 ap.add_argument("--warmup", type=int, default=None, help="calls before them (decode: 2, the others: 3)")
@@ -309,6 +313,63 @@ def bench_rice():
              device_read_GB_per_s=round(hbm, 1), fraction_of_read_rate=round(moved / ms / 1e6 / hbm, 5))
 
 
+def bench_framer():
+    rng = np.random.default_rng(1)
+    base_n = min(256, nf)
+    blocks = [ccsds.make_block(0x8C, i % 64, i, rng) for i in range(base_n)]
+    aligned = tiled(np.stack([ccsds.cadu_from_block(b) for b in blocks]), np.int8).reshape(-1)
+    whole = (nf // 50) * 50                      # one symbol deleted every 50 frames: the last of each run of 50
+    deleted = torch.cat([aligned[:whole * FR].view(-1, 50 * FR)[:, :-1].reshape(-1), aligned[whole * FR:]]) if whole else aligned
+    sync = xa.FrameSynchroniser("lrit")
+    cap = sync.rows(len(aligned))
+    frames, valid, hits = u8(cap * FR), u8(cap), u8(cap * 16)
+    start, count = u8(cap * 8), u8(4)
+    reps, warm = args.reps or 10, 2 if args.warmup is None else args.warmup
+
+    def push(x):
+        return lambda: sync.push_device(x.data_ptr(), len(x), frames.data_ptr(), valid.data_ptr(), hits.data_ptr(), start.data_ptr(),
+                                        count.data_ptr(), stream=st)
+
+    def pair():                                  # the fixed-window pair takes at most 65535 frames per call
+        for a in range(0, nf, 65535):
+            k = min(65535, nf - a)
+            xa.sync_correlate_device(aligned[a * FR:].data_ptr(), k * FR, hits[a * 16:].data_ptr(), stream=st)
+            xa.sync_fix_frames_device(aligned[a * FR:].data_ptr(), k * FR, hits[a * 16:].data_ptr(), frames[a * FR:].data_ptr(),
+                                      valid[a:].data_ptr(), stream=st)
+
+    def framer_case(name, x, segment):
+        sync.set_segment(segment)
+        times = []
+        for i in range(warm + reps):             # every call from a fresh cursor: the reset is outside the events
+            sync.reset()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            push(x)()
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warm:
+                times.append(a.elapsed_time(b))
+        s = sync.stats()
+        rows = int(s["rows"])
+        emit(case=name, segment=segment or "default", symbols=len(x), ms_median=round(float(np.median(times)), 4), ms_min=round(min(times), 4),
+             frames_per_ms=round(int(s["frames"]) / float(np.median(times)), 1), GB_per_s_in=round(len(x) / float(np.median(times)) / 1e6, 1),
+             rows=rows, frames=int(s["frames"]), dropped_chunks=int(s["dropped_chunks"]), resyncs=int(s["resyncs"]),
+             rewalked_chunks=int(s["rewalked_chunks"]), rewalked_share=round(int(s["rewalked_chunks"]) / max(rows, 1), 5))
+        return float(np.median(times))
+
+    ms_a = framer_case("framer aligned", aligned, 0)
+    emit(case="framer aligned check", count=int(count.cpu().numpy().view(np.uint32)[0]), valid=int(valid[:nf].sum()), frames=nf)
+    ms_d = framer_case("framer one symbol deleted every 50 frames", deleted, 0)
+    ms_p, mn_p = timed(pair, reps, warm)
+    emit(case="fixed windows: correlate + fix_frames, aligned", frames=nf, ms_median=round(ms_p, 4), ms_min=round(mn_p, 4),
+         frames_per_ms=round(nf / ms_p, 1), GB_per_s_in=round(nf * FR / ms_p / 1e6, 1), valid=int(valid[:nf].sum()))
+    emit(case="framer check", aligned_over_pair=round(ms_a / ms_p, 3), deleted_over_pair=round(ms_d / ms_p, 3))
+    for segment in (16, 64, 128, 256, 1024):
+        framer_case("framer aligned", aligned, segment)
+        framer_case("framer one symbol deleted every 50 frames", deleted, segment)
+    sync.close()
+
+
 shared = []                                     # the packets and the files cases run on one stream of frames
 
 
@@ -318,6 +379,6 @@ def packet_chain():
     return shared[0]
 
 
-for what in ["decode", "demux", "packets", "files", "rice"] if args.what == "all" else [args.what]:
-    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "packets": lambda: bench_packets(packet_chain()),
+for what in ["decode", "demux", "packets", "files", "rice", "framer"] if args.what == "all" else [args.what]:
+    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "packets": lambda: bench_packets(packet_chain()),
      "files": lambda: bench_files(packet_chain())}[what]()

@@ -89,6 +89,15 @@ _SIGNATURES = {
     "xrit_sync_correlate": (C.c_int, [_vp, _sz, _vp, C.c_int, C.c_uint32, _vp, C.c_int]),
     "xrit_sync_fix_frames_device": (C.c_int, [_vp, _sz, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int, _vp]),
     "xrit_sync_fix_frames": (C.c_int, [_vp, _sz, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int]),
+    "xrit_framer_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
+    "xrit_framer_destroy": (C.c_int, [_vp]),
+    "xrit_framer_set_frame": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "xrit_framer_set_segment": (C.c_int, [_vp, C.c_uint32]),
+    "xrit_framer_reset": (C.c_int, [_vp]),
+    "xrit_framer_rows": (_sz, [_vp, _sz]),
+    "xrit_framer_push_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xrit_framer_push": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "xrit_framer_stats": (C.c_int, [_vp, _vp]),
     "xrit_decoder_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "xrit_decoder_destroy": (C.c_int, [_vp]),
     "xrit_decoder_reset": (C.c_int, [_vp]),
@@ -696,6 +705,84 @@ def sync_correlate_device(d_symbols_ptr, n, d_hits_ptr, words=(LRIT_UW0, LRIT_UW
     w = np.asarray(words, np.uint64)
     _check(lib().xrit_sync_correlate_device(C.c_void_p(d_symbols_ptr), n, _p(w), len(w), frame, C.c_void_p(d_hits_ptr),
                                             device, C.c_void_p(stream) if stream else None))
+
+
+# ---- stream frame synchroniser: the decoder's walk over a stream, chunk by chunk (newdecoder.cpp:212-270) -----
+# xrit_framer_counters
+FRAMER_STATS_DTYPE = np.dtype([(f, np.uint64) for f in ("symbols", "cursor", "rows", "frames", "dropped_chunks", "resyncs", "carry",
+                                                        "rewalked_chunks", "adopted_chunks", "calls")])
+assert FRAMER_STATS_DTYPE.itemsize == 80
+FRAMER_MAX_SYMBOLS = 1 << 30
+
+
+class FrameSynchroniser(_Handle):
+    """The reference decoder's frame synchronisation over a stream of int8 soft symbols that arrives in calls of any
+    length: a cursor and the symbols not consumed yet are kept on the device, every chunk of `frame` symbols from the
+    cursor on is correlated, a hit moves the cursor behind its frame, a miss by one chunk.  The rows do not depend on how
+    the stream is cut into calls.  mode: "lrit" (frames found with the inverted word are inverted) or "hrit"."""
+    _destroy = "xrit_framer_destroy"
+
+    def __init__(self, mode="lrit", device=0, frame=None, min_correlation=None, segment=0):
+        super().__init__()
+        if mode not in ("lrit", "hrit"):
+            raise ValueError(f"mode {mode!r}: 'lrit' or 'hrit'")
+        self.mode = mode
+        _check(lib().xrit_framer_create(C.byref(self._h), 1 if mode == "hrit" else 0, device))
+        self.frame = CODED_FRAME_SIZE
+        if frame is not None or min_correlation is not None:
+            self.set_frame(CODED_FRAME_SIZE if frame is None else frame,
+                           MIN_CORRELATION_BITS if min_correlation is None else min_correlation)
+        if segment:
+            self.set_segment(segment)
+
+    def set_frame(self, frame, min_correlation=MIN_CORRELATION_BITS):
+        """Symbols per frame (65 .. 2^20) and the acceptance; only before the first push."""
+        _check(lib().xrit_framer_set_frame(self._h, int(frame), int(min_correlation)))
+        self.frame = int(frame)
+
+    def set_segment(self, chunks):
+        """Chunks per walker segment (0: chosen per call).  The rows do not depend on it."""
+        _check(lib().xrit_framer_set_segment(self._h, int(chunks)))
+
+    def rows(self, n):
+        """Rows the outputs of a push of n symbols must hold."""
+        return int(lib().xrit_framer_rows(self._h, int(n)))
+
+    def push(self, symbols, trim=True):
+        """Host buffers: (frames (r, frame) int8, valid (r,) uint8, hits (r, 4) uint32 as the correlator found them,
+        start (r,) uint64 absolute offsets) of the rows this call emits; trim = False: all rows(n) rows, those past the
+        emitted ones all-zero, and the count as a fifth item."""
+        d = np.ascontiguousarray(symbols, np.int8).reshape(-1)
+        cap = self.rows(len(d))
+        frames = np.zeros((cap, self.frame), np.int8)
+        valid = np.zeros(cap, np.uint8)
+        hits = np.zeros((cap, 4), np.uint32)
+        start = np.zeros(cap, np.uint64)
+        got = lib().xrit_framer_push(self._h, _p(d) if len(d) else None, len(d), _p(frames), _p(valid), _p(hits), _p(start))
+        if got < 0:
+            _check(got)
+        if trim:
+            return frames[:got], valid[:got], hits[:got], start[:got]
+        return frames, valid, hits, start, got
+
+    def push_device(self, d_symbols_ptr, n, d_frames_ptr, d_valid_ptr, d_hits_ptr, d_start_ptr, d_count_ptr, stream=None):
+        """Device pointers (frames rows(n) * frame bytes, valid rows(n), hits rows(n) * 16, start rows(n) * 8, count 4
+        bytes), asynchronous on stream; FrameDecoder.decode_device and ChannelDemux.process_device may be queued behind
+        it with nf = rows(n)."""
+        _check(lib().xrit_framer_push_device(self._h, C.c_void_p(d_symbols_ptr) if d_symbols_ptr else None, n,
+                                             C.c_void_p(d_frames_ptr), C.c_void_p(d_valid_ptr), C.c_void_p(d_hits_ptr),
+                                             C.c_void_p(d_start_ptr), C.c_void_p(d_count_ptr),
+                                             C.c_void_p(stream) if stream else None))
+
+    def stats(self):
+        """The counters after the last call (a FRAMER_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, FRAMER_STATS_DTYPE)
+        _check(lib().xrit_framer_stats(self._h, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Cursor 0, nothing carried, counters zero."""
+        _check(lib().xrit_framer_reset(self._h))
 
 
 # ---- decoder: Viterbi27 + NRZ-M + derandomiser + 4 x RS(255,223) (decoder/src/newdecoder.cpp:272-348) ------------

@@ -4,6 +4,7 @@
 #include <functional>
 
 #include "common.h"
+#include "framer_host.h"
 #include "loop_core.h"
 #include "taps.h"
 
@@ -479,6 +480,33 @@ size_t demux_scratch_carve(void *p, size_t nf, DemuxScratch &sc);     // returns
 int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,
                  const xrit_frame_info *info, size_t nf, DemuxState *state, DemuxScratch &sc, unsigned char *vcdu,
                  unsigned *offsets, xrit_frame_stats *records, hipStream_t s);
+// stream frame synchroniser (framer.hip): carry ++ new symbols is the call's view V; offsets below are relative to V[0],
+// the cursor at the start of the call
+struct FramerPar {
+    unsigned frame, min_corr, invert;       // invert: LRIT (a frame found with word != 0 is inverted)
+    unsigned whi[2], wlo[2];                // the two sync words
+    unsigned n;                             // new symbols of this call
+    unsigned seg_chunks, seg_bytes, segs;   // S, S * frame, segments (walkers) of this call
+    unsigned cap;                           // rows the outputs hold
+};
+struct FramerCall {                         // what the joints leave for the gather of the same call
+    unsigned long long base;                // absolute offset of V[0]
+    unsigned carry, total, cursor, count;   // bytes of carry in V, bytes of V, the cursor after the call, rows emitted
+};
+struct FramerScratch {
+    unsigned *bits;                 // hard bits of V, 32 per word, MSB = first byte
+    unsigned *bmax;                 // per run of 64 positions: the best (count << 6 | 63 - offset) of word 0 | of word 1 << 16
+    uint4 *rec;                     // [segs][S] a walker's steps: (cursor, word, position, correlation)
+    unsigned *nrec;                 // [segs] steps recorded
+    uint2 *wout;                    // [segs] (the cursor the walker left with, 1: it stopped for want of symbols)
+    uint4 *rows;                    // [cap] the call's rows, as the steps
+    FramerCall *call;
+};
+size_t framer_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chunks, FramerScratch &sc);
+unsigned framer_segments(size_t n, unsigned frame, unsigned seg_chunks);
+int launch_framer(const FramerPar &par, FramerState *state, const int8_t *carry_in, int8_t *carry_out, const int8_t *symbols,
+                  FramerScratch &sc, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits, unsigned long long *start,
+                  unsigned *count, hipStream_t s);
 // packet assembler (packets.hip): the handle's state, the per-call scratch (R = max(max_rows, 1) rows)
 constexpr unsigned PACKETS_PEND_MAX = 65541;        // a pending packet is shorter than the longest packet (65542)
 constexpr unsigned PACKETS_TILE = 1024;             // rows per tile of the scan

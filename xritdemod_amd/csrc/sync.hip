@@ -11,6 +11,7 @@
 // offset and word, instead of 64 byte compares.  One workgroup per frame window; the per-word maximum keeps the FIRST offset that reaches it and the
 // overall result the FIRST word, like the reference's strict '>' scans.
 #include "kernels.h"
+#include "sync_core.h"
 
 namespace xrit {
 
@@ -21,15 +22,6 @@ struct SyncWords { unsigned long long w[SYNC_MAX_WORDS]; int n; };
 
 // key orders (correlation desc, position asc): larger key = better.  correlation <= 64, position < 2^20.
 __device__ __forceinline__ unsigned sync_key(unsigned corr, unsigned pos) { return (corr << 20) | (0xFFFFFu - pos); }
-
-// hard bits of four soft bytes (lowest address first -> most significant bit of the nibble)
-__device__ __forceinline__ unsigned sync_nibble(unsigned x)
-{
-    // unsigned byte >= 127  <=>  bit 7 set, or the low seven bits are all ones
-    const unsigned ge = (x | ((x & 0x7f7f7f7fu) + 0x01010101u)) & 0x80808080u;
-    const unsigned one = (~ge & 0x80808080u) >> 7;        // 1 at bit 0 / 8 / 16 / 24
-    return ((one * 0x08040201u) >> 24) & 0xFu;            // byte 0 -> bit 3 ... byte 3 -> bit 0, no carries
-}
 
 __global__ void __launch_bounds__(SYNC_THREADS) sync_correlate_kernel(const int8_t *__restrict__ data, unsigned frame,
                                                                       SyncWords words, xrit_sync_hit *__restrict__ hits)
@@ -70,11 +62,12 @@ __global__ void __launch_bounds__(SYNC_THREADS) sync_correlate_kernel(const int8
     for (int i = tid; i < max_search; i += SYNC_THREADS) {
         const unsigned j = (unsigned)i >> 5, r = (unsigned)i & 31;
         const unsigned a = bits[j], b = bits[j + 1], c = bits[j + 2];
-        const unsigned hi = __funnelshift_l(b, a, r), lo = __funnelshift_l(c, b, r);     // r = 0: a, b
+        unsigned hi, lo;
+        sync_window(a, b, c, r, hi, lo);
 #pragma unroll
         for (int n = 0; n < SYNC_MAX_WORDS; ++n) {
             if (n < words.n) {
-                const unsigned cnt = 64u - (unsigned)__popc(hi ^ whi[n]) - (unsigned)__popc(lo ^ wlo[n]);
+                const unsigned cnt = sync_agree(hi, lo, whi[n], wlo[n]);
                 k[n] = max(k[n], sync_key(cnt, (unsigned)i));
             }
         }

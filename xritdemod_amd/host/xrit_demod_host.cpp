@@ -86,6 +86,7 @@ struct Options {
     std::string packets;           // --packets DIR: the CRC-checked space packets, DIR/vc{vcid}_apid{apid}.bin
     std::string files;             // --files DIR: the LRIT/HRIT files, DIR/vc{vcid}_apid{apid}_{serial}.lrit
     bool files_decompress = false; // --files-decompress: the scan lines of rice-coded image files, ..._{serial}.img
+    bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -101,6 +102,9 @@ void usage()
                  "         [--fifo [--fifo-block SAMPLES] [--fifo-lag BLOCKS]]   (the reference's FIFO chunking, demodulator.cpp:108-119)\n"
                  "         [--decode PATH]   (correlate, fix, Viterbi, derandomise, RS(255,223) on the GPU: the 892-byte VCDU of every\n"
                  "                            good frame appended to PATH, counts on stderr at exit; --sink null for a decode-only run)\n"
+                 "         [--stream-sync]   (with --decode and the options behind it: frames are found by the stream frame synchroniser,\n"
+                 "                            which walks the symbols chunk by chunk from where the last frame ended like the reference's\n"
+                 "                            decoder, instead of by correlating fixed 16384-symbol windows; resynchronisations on stderr at exit)\n"
                  "         [--channels DIR]   (the decoder's ChannelWriter: every good VCDU appended to DIR/channel_{vcid}.bin)\n"
                  "         [--decoder-stats PATH]   (the decoder's Statistics_st, 4167 bytes per valid frame; lost packets on stderr at exit)\n"
                  "         [--packets DIR]   (CCSDS space packets out of the channels' VCDUs: every packet whose CRC-16 matches appended whole,\n"
@@ -147,6 +151,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--packets") { if (!(v = need("--packets"))) return false; o.packets = v; }
         else if (a == "--files") { if (!(v = need("--files"))) return false; o.files = v; }
         else if (a == "--files-decompress") o.files_decompress = true;
+        else if (a == "--stream-sync") o.stream_sync = true;
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -177,6 +182,10 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--files: one GPU, without --drop\n");
         return false;
     }
+    if (o.stream_sync && o.decode.empty() && o.channels.empty() && o.decoder_stats.empty() && o.packets.empty() && o.files.empty()) {
+        std::fprintf(stderr, "--stream-sync needs --decode, --channels, --decoder-stats, --packets or --files\n");
+        return false;
+    }
     if (o.files_decompress && o.files.empty()) {
         std::fprintf(stderr, "--files-decompress needs --files DIR\n");
         return false;
@@ -197,6 +206,9 @@ struct FrameDecode {
     FILE *out = nullptr;
     FILE *stats_out = nullptr;
     xrit_decoder *dec = nullptr;
+    xrit_framer *fr = nullptr;      // --stream-sync
+    std::vector<uint64_t> starts;
+    xrit_framer_counters fr_stats{};
     xrit_demux *dm = nullptr;
     xrit_packets *pk = nullptr;
     std::string channel_dir, packet_dir;
@@ -229,11 +241,15 @@ struct FrameDecode {
     size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
 
     bool open(const std::string &path, const std::string &channels, const std::string &stats_path, const std::string &packets,
-              const std::string &files, bool files_decompress, bool hrit_mode, int dev)
+              const std::string &files, bool files_decompress, bool hrit_mode, int dev, bool stream_sync = false)
     {
         hrit = hrit_mode;
         device = dev;
         if (xrit_decoder_create(&dec, hrit ? 1 : 0, device) != XRIT_OK) {
+            std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+            return false;
+        }
+        if (stream_sync && xrit_framer_create(&fr, hrit ? 1 : 0, device) != XRIT_OK) {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
         }
@@ -275,8 +291,28 @@ struct FrameDecode {
         }
         return true;
     }
+    // --stream-sync: the framer keeps the cursor and the unconsumed symbols on the device; its rows are what the fixed windows'
+    // correlate + fix give, found chunk by chunk from where the last frame ended
+    bool sync_stream(const int8_t *sym, size_t n, size_t &take)
+    {
+        const size_t cap = xrit_framer_rows(fr, n);
+        hits.resize(cap);
+        frames.resize(cap * FRAME);
+        valid.resize(cap);
+        starts.resize(cap);
+        const int got = xrit_framer_push(fr, sym, n, frames.data(), valid.data(), hits.data(), starts.data());
+        if (got < 0) return fail("frame synchroniser");
+        take = (size_t)got;
+        raw_hits.assign(hits.begin(), hits.begin() + (std::ptrdiff_t)take);
+        return true;
+    }
     bool add(const int8_t *sym, size_t n)
     {
+        if (fr) {
+            size_t take = 0;
+            if (!sync_stream(sym, n, take)) return false;
+            return take == 0 || decode_frames(take);
+        }
         pending.insert(pending.end(), sym, sym + n);
         const size_t nw = pending.size() / FRAME;
         if (nw == 0) return true;
@@ -296,6 +332,13 @@ struct FrameDecode {
         if (xrit_sync_fix_frames(pending.data(), pending.size(), hits.data(), FRAME, MIN_CORRELATION, frames.data(), valid.data(),
                                  device) != XRIT_OK)
             return fail("fix frames");
+        if (!decode_frames(take)) return false;
+        pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)(take * FRAME));
+        return true;
+    }
+    // the frame decoder and the stages behind it on the first `take` rows of frames / valid / raw_hits
+    bool decode_frames(size_t take)
+    {
         cadu.resize(take * 1024);
         block.resize(take * 1020);
         info.resize(take);
@@ -310,9 +353,7 @@ struct FrameDecode {
             for (int k = 0; k < 4; ++k) rs_corrections += info[f].rs_errors[k] > 0 ? (size_t)info[f].rs_errors[k] : 0;
             if (out && std::fwrite(block.data() + f * 1020, 1, VCDU, out) != VCDU) { std::perror("decode output"); return false; }
         }
-        if (dm && !demux(take)) return false;
-        pending.erase(pending.begin(), pending.begin() + (std::ptrdiff_t)(take * FRAME));
-        return true;
+        return !dm || demux(take);
     }
     // ChannelWriter::writeChannel per good frame (newdecoder.cpp:356-360) and the statistics record of every valid frame
     bool demux(size_t take)
@@ -446,6 +487,15 @@ struct FrameDecode {
                          n_ok, n_dropped, rs_corrections, n_frames ? (double)viterbi_errors / (double)n_frames : 0.0);
             xrit_decoder_destroy(dec);
             dec = nullptr;
+        }
+        if (fr) {
+            if (xrit_framer_stats(fr, &fr_stats) == XRIT_OK)
+                std::fprintf(stderr, "sync: %llu symbols, %llu frames, %llu chunks dropped, %llu resynchronisations, %llu symbols left\n",
+                             (unsigned long long)fr_stats.symbols, (unsigned long long)fr_stats.frames,
+                             (unsigned long long)fr_stats.dropped_chunks, (unsigned long long)fr_stats.resyncs,
+                             (unsigned long long)fr_stats.carry);
+            xrit_framer_destroy(fr);
+            fr = nullptr;
         }
         if (dm) {
             std::fprintf(stderr, "demux: lost packets %lld (", (long long)dm_stats.lost_packets);
@@ -788,7 +838,7 @@ int main(int argc, char **argv)
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
     if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
-        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device)) {
+        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
