@@ -451,6 +451,10 @@ int xrit_decoder_create(xrit_decoder **d, int hrit, int device);
 int xrit_decoder_destroy(xrit_decoder *d);
 /* carry back to erasures (lastFrameEnd = 128 everywhere, :141); waits for the handle's last call */
 int xrit_decoder_reset(xrit_decoder *d);
+/* resident Viterbi windows (waves, each with its own 66 KB of decision scratch) that a call starts at most; a call of
+ * more frames walks them windows apart.  0: the default, 8 per compute unit; other values are clamped to 1 .. default.
+ * Takes effect from the next call; the outputs do not depend on it. */
+int xrit_decoder_set_windows(xrit_decoder *d, uint32_t windows);
 /* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation; the carry is updated on
  * the device.  d_cadu: nf * 1024 bytes and d_block: nf * 1020 bytes, both 16-byte aligned; d_info: nf entries.
  * Calls on one handle share its carry and scratch: the caller keeps them in order (one stream, or events). */

@@ -105,18 +105,182 @@ def encode_ccsds(data):
     return np.concatenate([d, T[cw[223:]]]).astype(np.uint8)
 
 
+_ROOT_LOG = (PRIM * (FCR + np.arange(NROOTS))) % 255            # log of the i-th generator root
+
+
 def syndromes(codeword, dual=True):
-    """The 32 syndromes S_i = c(alpha^(11 (112 + i))) of one 255-byte codeword (zero for a codeword)."""
+    """The 32 syndromes S_i = c(alpha^(11 (112 + i))) of a 255-byte codeword (zero for a codeword): (255,) -> (32,),
+    or (n, 255) -> (n, 32), by Horner over all the words and roots at once."""
     c = np.asarray(codeword, np.uint8)
-    c = (TINV[c] if dual else c).astype(np.int64)
-    s = np.zeros(NROOTS, np.int64)
-    for i in range(NROOTS):
-        r = EXP[(PRIM * (FCR + i)) % 255]
-        acc = 0
-        for b in c:
-            acc = int(gf_mul(acc, r)) ^ int(b)
-        s[i] = acc
-    return s
+    assert c.shape[-1] == 255 and c.ndim in (1, 2)
+    c2 = (TINV[c] if dual else c).astype(np.int64).reshape(-1, 255)
+    acc = np.zeros((len(c2), NROOTS), np.int64)
+    for j in range(255):
+        acc = np.where(acc == 0, 0, EXP[LOG[acc] + _ROOT_LOG]) ^ c2[:, j, None]
+    return acc.reshape(c.shape[:-1] + (NROOTS,))
+
+
+# ---- a reference decoder by Peterson-Gorenstein-Zierler, independent of Berlekamp-Massey ------------------------
+MUL = gf_mul(np.arange(256)[:, None], np.arange(256)[None, :]).astype(np.int64)       # the 256 x 256 product table
+INV = np.zeros(256, np.int64)
+INV[1:] = EXP[(255 - LOG[1:]) % 255]
+_BETA_LOG = (PRIM * np.arange(255)) % 255                       # log of X = beta^k, the locator of the degree-k symbol
+
+
+def gf_eliminate(a):
+    """Gauss-Jordan over GF(2^8) on a copy of the matrix a (rows x cols, an augmented matrix if the caller wants):
+    (reduced matrix, pivot columns).  The rank is the number of pivots."""
+    a = np.array(a, np.int64)
+    rows, cols = a.shape
+    piv, r = [], 0
+    for c in range(cols):
+        if r == rows:
+            break
+        nz = np.nonzero(a[r:, c])[0]
+        if not len(nz):
+            continue
+        p = r + nz[0]
+        if p != r:
+            a[[r, p]] = a[[p, r]]
+        a[r] = MUL[INV[a[r, c]], a[r]]
+        f = a[:, c].copy()
+        f[r] = 0
+        a ^= MUL[f[:, None], a[r][None, :]]
+        piv.append(c)
+        r += 1
+    return a, piv
+
+
+def gf_solve(m, rhs):
+    """x with m x = rhs for a square non-singular m over GF(2^8), or None when m is singular."""
+    m = np.asarray(m, np.int64)
+    n = len(m)
+    a, piv = gf_eliminate(np.concatenate([m, np.asarray(rhs, np.int64).reshape(n, 1)], axis=1))
+    return a[:, n].copy() if piv == list(range(n)) else None
+
+
+def _pgz(S):
+    """Errors-only decoding from 32 non-zero syndromes: (degrees k, conventional magnitudes Y) of the unique error
+    pattern of weight <= 16 with these syndromes, or None.  With Z_l = Y_l X_l^112 the syndromes are the power sums
+    S_i = sum Z_l X_l^i, and the monic p(x) = prod (x - X_l) of degree v obeys S_(i+v) = sum_b p_b S_(i+b): v is the
+    largest size at which the Hankel matrix [S_(a+b)] is non-singular.  Every leading block larger than the rank of the
+    16 x 16 one is singular, so the search starts there."""
+    S = np.asarray(S, np.int64)
+    hankel = S[np.arange(16)[:, None] + np.arange(16)[None, :]]
+    for v in range(len(gf_eliminate(hankel)[1]), 0, -1):
+        p = gf_solve(hankel[:v, :v], S[v:2 * v])
+        if p is None:
+            continue
+        # the roots of x^v + p_(v-1) x^(v-1) + ... + p_0 among all 255 locators, by evaluation
+        x = EXP[_BETA_LOG]
+        val = np.ones(255, np.int64)
+        for b in range(v - 1, -1, -1):
+            val = MUL[val, x] ^ p[b]
+        k = np.nonzero(val == 0)[0]
+        if len(k) != v:
+            return None
+        # magnitudes from the first v syndromes: S_i = sum_l Y_l X_l^(112 + i)
+        van = EXP[(_BETA_LOG[k][None, :] * (FCR + np.arange(v))[:, None]) % 255]
+        y = gf_solve(van, S[:v])
+        if y is None or not y.all():
+            return None
+        # ... and it is the answer only if it explains all 32
+        full = EXP[(_BETA_LOG[k][None, :] * (FCR + np.arange(NROOTS))[:, None]) % 255]
+        if not np.array_equal(np.bitwise_xor.reduce(MUL[full, y[None, :]], axis=1), S):
+            return None
+        return k, y
+    return None
+
+
+def rs_decode_many(codewords_dual):
+    """Reference errors-only decoder of RS(255,223) in the dual basis, (n, 255) -> (corrected (n, 255), counts (n,)):
+    the unique codeword within 16 symbols and the distance to it, or the word unchanged and -1."""
+    w = np.array(codewords_dual, np.uint8).reshape(-1, 255)
+    out = w.copy()
+    S = syndromes(w)
+    counts = np.zeros(len(w), np.int64)
+    for i in np.nonzero(S.any(axis=1))[0]:
+        found = _pgz(S[i])
+        if found is None:
+            counts[i] = -1
+            continue
+        k, y = found
+        conv = TINV[w[i]].astype(np.int64)
+        conv[254 - k] ^= y                                     # byte 0 is the highest degree
+        out[i] = T[conv]
+        counts[i] = len(k)
+    assert not syndromes(out[counts >= 0]).any()
+    return out, counts
+
+
+def rs_decode(codeword_dual):
+    """One codeword: (corrected_dual (255,), n), n = -1 and the input back when it is uncorrectable."""
+    out, n = rs_decode_many(np.asarray(codeword_dual, np.uint8).reshape(1, 255))
+    return out[0], int(n[0])
+
+
+def rs_decode_blocks(blocks):
+    """The RS stage of the frame decoder on derandomised blocks (n, 1020): (blocks after correction, rs_errors (n, 4),
+    ok (n,)); a frame is ok unless all four of its codewords are -1 (newdecoder.cpp:321)."""
+    b = np.asarray(blocks, np.uint8).reshape(-1, BLOCK_BYTES)
+    cws = b.reshape(-1, 255, 4).transpose(0, 2, 1).reshape(-1, 255)           # frame-major, codeword k = bytes k::4
+    out, n = rs_decode_many(cws)
+    fixed = out.reshape(-1, 4, 255).transpose(0, 2, 1).reshape(-1, BLOCK_BYTES)
+    n = n.reshape(-1, 4)
+    return fixed, n, (~(n == -1).all(axis=1)).astype(np.int64)
+
+
+def header_fields(blocks):
+    """(scid, vcid, counter) as newdecoder.cpp:342-348 reads them from bytes 0 .. 4 of every block."""
+    b = np.asarray(blocks, np.uint8).reshape(-1, BLOCK_BYTES).astype(np.int64)
+    return ((b[:, 0] & 0x3F) << 2) | ((b[:, 1] & 0xC0) >> 6), b[:, 1] & 0x3F, (b[:, 2] << 16) | (b[:, 3] << 8) | b[:, 4]
+
+
+# ---- constructed error patterns (wire basis, 255 bytes, to be XORed onto a codeword) ----------------------------
+def error_pattern(positions, values_conv):
+    """Conventional-basis error values at byte positions, as the wire (dual-basis) XOR pattern: T is GF(2)-linear."""
+    e = np.zeros(255, np.int64)
+    e[np.asarray(positions, np.int64)] = np.asarray(values_conv, np.int64)
+    return T[e]
+
+
+def zero_syndrome_errors(positions, zero, rng):
+    """An error pattern on the given byte positions, every value non-zero, whose syndromes S_i, i in zero, vanish: a
+    linear system in the values (S_i = sum Y_l X_l^(112 + i)) with len(zero) < len(positions); the other values are
+    drawn."""
+    pos = np.asarray(positions, np.int64)
+    nz, v = len(zero), len(pos)
+    assert 0 < nz < v
+    lx = _BETA_LOG[254 - pos]
+    coef = EXP[(lx[None, :] * (FCR + np.asarray(zero, np.int64))[:, None]) % 255]          # (nz, v)
+    for _ in range(100):
+        free = rng.integers(1, 256, v - nz)
+        rhs = np.bitwise_xor.reduce(MUL[coef[:, nz:], free[None, :]], axis=1)
+        head = gf_solve(coef[:, :nz], rhs)
+        if head is not None and head.all():
+            e = error_pattern(pos, np.concatenate([head, free]))
+            assert not syndromes(e)[list(zero)].any()
+            return e
+    raise AssertionError("no pattern found")
+
+
+def generator_codeword(shift, scale):
+    """The codeword scale * x^shift * g(x), wire basis: 33 non-zero symbols at bytes 222 - shift .. 254 - shift."""
+    assert 0 <= shift <= 222 and 1 <= scale <= 255
+    c = np.zeros(255, np.int64)
+    c[222 - shift:255 - shift] = MUL[scale, GENPOLY]
+    return T[c]
+
+
+def near_codeword_error(shift, scale, j, rng):
+    """(error pattern, the codeword it lies next to): 33 - j of the symbols of generator_codeword(shift, scale), so
+    that a word sent + pattern is at distance 33 - j from sent and j from sent + that codeword."""
+    g = generator_codeword(shift, scale)
+    support = np.nonzero(g)[0]
+    assert len(support) == 33
+    e = g.copy()
+    e[rng.choice(support, j, replace=False)] = 0
+    return e, g
 
 
 def interleave(codewords):

@@ -101,6 +101,7 @@ _SIGNATURES = {
     "xrit_decoder_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "xrit_decoder_destroy": (C.c_int, [_vp]),
     "xrit_decoder_reset": (C.c_int, [_vp]),
+    "xrit_decoder_set_windows": (C.c_int, [_vp, C.c_uint32]),
     "xrit_decoder_decode_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "xrit_decoder_decode": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "xrit_demux_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -831,6 +832,11 @@ class FrameDecoder(_Handle):
     def reset(self):
         """The carry back to erasures (the decoder's start state)."""
         _check(lib().xrit_decoder_reset(self._h))
+
+    def set_windows(self, windows):
+        """At most this many resident Viterbi windows per call from the next call on (0: the default, 8 per compute
+        unit; clamped to 1 .. default).  The outputs do not depend on it."""
+        _check(lib().xrit_decoder_set_windows(self._h, int(windows)))
 
 
 # ---- channel demultiplexer and packet accounting (decoder/src/newdecoder.cpp:309-395) -------------------------------

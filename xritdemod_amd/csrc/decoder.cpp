@@ -13,6 +13,7 @@ constexpr unsigned DEC_WINDOWS_PER_CU = 8;        // resident Viterbi windows pe
 struct xrit_decoder : StageHandle {
     int hrit = 0;
     unsigned slots = 0;                             // resident windows: CUs x DEC_WINDOWS_PER_CU
+    unsigned windows = 0;                           // ... of which a call uses at most this many (xrit_decoder_set_windows)
     DevBuf carry, prev, last, dec, verr;
     DevBuf h_frames, h_valid, h_cadu, h_block, h_info;
     void close_all() { close({&carry, &prev, &last, &dec, &verr, &h_frames, &h_valid, &h_cadu, &h_block, &h_info}); }
@@ -27,6 +28,7 @@ int xrit_decoder_create(xrit_decoder **out, int hrit, int device)
         XR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device));
         d.hrit = hrit;
         d.slots = (unsigned)(cus > 0 ? cus : 1) * DEC_WINDOWS_PER_CU;
+        d.windows = d.slots;
         XR_TRY(d.carry.reserve(64));
         XR_TRY(d.last.reserve(sizeof(int)));
         return xrit_decoder_reset(&d);
@@ -41,6 +43,13 @@ int xrit_decoder_reset(xrit_decoder *d)
     return d->write_state(d->carry.p, nullptr, 64);
 }
 
+int xrit_decoder_set_windows(xrit_decoder *d, uint32_t windows)
+{
+    if (!d) { set_error("null argument"); return XRIT_E_INVALID; }
+    d->windows = windows == 0 || windows > d->slots ? d->slots : windows;
+    return XRIT_OK;
+}
+
 int xrit_decoder_decode_device(xrit_decoder *d, const int8_t *d_frames, const uint8_t *d_valid, size_t nf, uint8_t *d_cadu,
                                uint8_t *d_block, xrit_frame_info *d_info, void *stream)
 {
@@ -50,7 +59,7 @@ int xrit_decoder_decode_device(xrit_decoder *d, const int8_t *d_frames, const ui
     if (nf > MAX_ROWS_PER_CALL) { set_error("decoder: at most %zu frames per call", MAX_ROWS_PER_CALL); return XRIT_E_INVALID; }
     if (((size_t)d_cadu | (size_t)d_block) & 15) { set_error("decoder: cadu and block must be 16-byte aligned"); return XRIT_E_INVALID; }
     XR_HIP(hipSetDevice(d->device));
-    const unsigned windows = nf < d->slots ? (unsigned)nf : d->slots;
+    const unsigned windows = nf < d->windows ? (unsigned)nf : d->windows;
     XR_TRY(d->prev.reserve(nf * sizeof(int)));
     XR_TRY(d->verr.reserve(nf * sizeof(unsigned)));
     XR_TRY(d->dec.reserve((size_t)windows * viterbi_slot_bytes()));
