@@ -465,6 +465,81 @@ int xrit_decoder_decode(xrit_decoder *d, const int8_t *frames, const uint8_t *va
                         uint8_t *cadu, uint8_t *block, xrit_frame_info *info);
 
 /* ------------------------------------------------------------------------
+ * Frame lock: the stream frame synchroniser and the decoder as the ONE loop
+ * the reference runs (newdecoder.cpp:218-237, 321-338; flywheelRecheck,
+ * parameters.h:41, default 4).  Exact integer contract: DESIGN.md section 18
+ * and tests/lock_spec.py.  Besides the framer's cursor and carry and the
+ * decoder's 64-symbol carry the handle keeps ok (lastFrameOK) and fc
+ * (flywheelCount) in device memory, both 0 at start.  The frame is 16384
+ * symbols and min_correlation 46.  While c + frame <= symbols received, with
+ * the state as it was at the chunk's entry:
+ *  1. fc == recheck: ok = 0, fc = 0 (:218-221);
+ *  2. ok == 0: the hit over the whole chunk, positions 0 .. frame - 65
+ *     (XRIT_LOCK_FULL).  Otherwise the hit over the first frame / 16 symbols,
+ *     positions 0 .. frame / 16 - 65: at position 0 it is kept
+ *     (XRIT_LOCK_SHORT); anywhere else the whole-chunk hit is taken, ok = 0,
+ *     fc = 0 (XRIT_LOCK_MISS, :228-235);
+ *  3. fc += 1;
+ *  4. hit.correlation < 46: a row with the hit, valid = 0, zeros, start = c;
+ *     c += frame; ok is not touched (:244-247);
+ *  5. else if c + hit.position + frame runs past the symbols received: stop;
+ *     nothing is emitted or consumed and ok, fc keep their values of the
+ *     chunk's entry: the chunk is walked again in the next call;
+ *  6. else a row with the hit, valid = 1, start = c + hit.position, the frame
+ *     (inverted when hit.word != 0 on LRIT), decoded behind the carry exactly
+ *     as xrit_decoder does; ok = info.ok (:321-338); c = start + frame.
+ * With recheck = 1 the rows are those of xrit_framer followed by xrit_decoder.
+ * The rows do not depend on how the stream is cut into calls.  The outputs
+ * hold xrit_lock_rows(lk, n) rows; those from *count on are all-zero with
+ * valid = 0 (rs_errors -1), so d_hits, d_cadu, d_block and d_info go to
+ * xrit_demux_process_device as they are.  mode[r]: XRIT_LOCK_FULL / SHORT /
+ * MISS, plus XRIT_LOCK_RECHECK when step 1 fired on the chunk; hits[r] is the
+ * hit that was used.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_lock xrit_lock;
+#define XRIT_LOCK_FULL 0
+#define XRIT_LOCK_SHORT 1
+#define XRIT_LOCK_MISS 2
+#define XRIT_LOCK_RECHECK 4
+typedef struct xrit_lock_counters {     /* 136 bytes */
+    xrit_framer_counters framer;        /* as xrit_framer_stats gives them; rewalked_chunks counts a chunk once, when it is consumed */
+    uint64_t short_kept;                /* chunks taken in mode SHORT */
+    uint64_t short_missed;              /* ... in mode MISS */
+    uint64_t rechecks;                  /* chunks on which step 1 fired */
+    uint64_t sensitive_chunks;          /* whole-chunk hit not at 0, short hit at 0, fc != recheck at entry: the outcome hangs on ok */
+    uint64_t rounds;                    /* passes of joints, gather, decoder and commit: calls + the stops for an RS outcome */
+    uint64_t frames_ok;                 /* valid rows with info.ok */
+    uint64_t frames_bad;                /* valid rows without */
+} xrit_lock_counters;
+
+int xrit_lock_create(xrit_lock **lk, int hrit, int device);
+int xrit_lock_destroy(xrit_lock *lk);
+/* cursor 0, nothing carried, ok = 0, fc = 0, the decoder's carry back to erasures, counters zero; waits for the last call */
+int xrit_lock_reset(xrit_lock *lk);
+/* flywheelRecheck, 1 .. 255 (default 4; 1: no flywheel); only before the handle's first push -- xrit_lock_reset does not
+ * reopen it: a handle keeps its recheck for life once it has pushed */
+int xrit_lock_set_flywheel(xrit_lock *lk, uint32_t recheck);
+/* as xrit_framer_set_segment and xrit_decoder_set_windows; the outputs do not depend on them */
+int xrit_lock_set_segment(xrit_lock *lk, uint32_t chunks);
+int xrit_lock_set_windows(xrit_lock *lk, uint32_t windows);
+/* rows the outputs of a call of n symbols must hold: xrit_framer_rows at frame 16384 (0 for a null handle) */
+size_t xrit_lock_rows(const xrit_lock *lk, size_t n);
+/* device pointers; the work is queued on `stream`, and the call SYNCHRONISES that stream once per round to read back one
+ * small record (rows so far, stopped or done): a round ends where the walk needs the RS outcome of a row the round
+ * itself emitted, so a call is 1 + (such stops) rounds, one on a stream in lock.  That read-back is the price of the
+ * coupling; no value goes from the host to the device between rounds.  With rows = xrit_lock_rows(lk, n): d_frames
+ * rows * 16384 bytes, d_valid rows, d_hits rows, d_start rows, d_mode rows bytes, d_cadu rows * 1024 (16-byte aligned),
+ * d_block rows * 1020, d_info rows, d_count one entry.  n <= XRIT_FRAMER_MAX_SYMBOLS; n = 0 is a call like any other. */
+int xrit_lock_push_device(xrit_lock *lk, const int8_t *d_symbols, size_t n, int8_t *d_frames, uint8_t *d_valid,
+                          xrit_sync_hit *d_hits, uint64_t *d_start, uint8_t *d_mode, uint8_t *d_cadu, uint8_t *d_block,
+                          xrit_frame_info *d_info, uint32_t *d_count, void *stream);
+/* host buffers of the same sizes; returns the rows emitted (>= 0) or an error code (< 0) */
+int xrit_lock_push(xrit_lock *lk, const int8_t *symbols, size_t n, int8_t *frames, uint8_t *valid, xrit_sync_hit *hits,
+                   uint64_t *start, uint8_t *mode, uint8_t *cadu, uint8_t *block, xrit_frame_info *info);
+/* the counters after the last call; waits for it */
+int xrit_lock_stats(xrit_lock *lk, xrit_lock_counters *out);
+
+/* ------------------------------------------------------------------------
  * Channel demultiplexer and packet accounting: the last stage of the
  * reference decoder's data path (decoder/src/newdecoder.cpp:309-395), on the
  * decoder's outputs.  Exact integer contract: DESIGN.md "Channel demux".

@@ -18,9 +18,13 @@ framer   xrit_framer_push_device (the stream frame synchroniser) on a frame-alig
          stream with one symbol deleted every 50 frames, and what existed before it on the aligned stream:
          xrit_sync_correlate_device + xrit_sync_fix_frames_device over fixed windows (calls of at most 65535 frames).  Then
          the framer at other segment lengths, with the share of chunks its joints walked again.
-all      the six, in this order.
+lock     xrit_lock_push_device (the frame lock: framer and decoder as the reference's one loop, with its flywheel) on the
+         framer leg's two streams, at recheck 4 and at recheck 1, next to xrit_framer_push_device +
+         xrit_decoder_decode_device queued on one stream: ms per call, rounds, sensitive chunks, chunks kept and missed in
+         the short range.
+all      the seven, in this order.
 
-    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,all} [--frames N] [--reps R] [--warmup W]
+    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,lock,all} [--frames N] [--reps R] [--warmup W]
                                     [--lines L] [--samples S] [--no-cpu]"""
 import argparse
 import json
@@ -39,7 +43,7 @@ import packet_spec as ps
 import rice_spec as rs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "all"])
+ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "lock", "all"])
 ap.add_argument("--frames", type=int, default=1 << 16)
 ap.add_argument("--reps", type=int, default=None, help="timed calls per case (decode: 5, the others: 20)")
 ap.add_argument("--warmup", type=int, default=None, help="calls before them (decode: 2, the others: 3)")
@@ -313,13 +317,20 @@ def bench_rice():
              device_read_GB_per_s=round(hbm, 1), fraction_of_read_rate=round(moved / ms / 1e6 / hbm, 5))
 
 
-def bench_framer():
+def framer_streams():
+    """A frame-aligned LRIT stream of nf frames (256 distinct CADUs tiled), and the same with one symbol deleted every 50
+    frames."""
     rng = np.random.default_rng(1)
     base_n = min(256, nf)
     blocks = [ccsds.make_block(0x8C, i % 64, i, rng) for i in range(base_n)]
     aligned = tiled(np.stack([ccsds.cadu_from_block(b) for b in blocks]), np.int8).reshape(-1)
     whole = (nf // 50) * 50                      # one symbol deleted every 50 frames: the last of each run of 50
     deleted = torch.cat([aligned[:whole * FR].view(-1, 50 * FR)[:, :-1].reshape(-1), aligned[whole * FR:]]) if whole else aligned
+    return aligned, deleted
+
+
+def bench_framer():
+    aligned, deleted = framer_streams()
     sync = xa.FrameSynchroniser("lrit")
     cap = sync.rows(len(aligned))
     frames, valid, hits = u8(cap * FR), u8(cap), u8(cap * 16)
@@ -370,6 +381,52 @@ def bench_framer():
     sync.close()
 
 
+def bench_lock():
+    aligned, deleted = framer_streams()
+    sync, dec = xa.FrameSynchroniser("lrit"), xa.FrameDecoder("lrit")
+    locks = {4: xa.FrameLock("lrit", flywheel=4), 1: xa.FrameLock("lrit", flywheel=1)}
+    cap = sync.rows(len(aligned))
+    frames, valid, hits, start, mode, count = u8(cap * FR), u8(cap), u8(cap * 16), u8(cap * 8), u8(cap), u8(4)
+    cadu, block, info = u8(cap * 1024), u8(cap * 1020), u8(cap * xa.FRAME_INFO_DTYPE.itemsize)
+    reps, warm = args.reps or 5, 2 if args.warmup is None else args.warmup
+
+    def from_reset(reset, fn):                   # every call from the start state: the reset is outside the events
+        times = []
+        for i in range(warm + reps):
+            reset()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warm:
+                times.append(a.elapsed_time(b))
+        return float(np.median(times)), min(times)
+
+    for name, x in (("aligned", aligned), ("one symbol deleted every 50 frames", deleted)):
+        def pair():
+            sync.push_device(x.data_ptr(), len(x), frames.data_ptr(), valid.data_ptr(), hits.data_ptr(), start.data_ptr(),
+                             count.data_ptr(), stream=st)
+            dec.decode_device(frames.data_ptr(), valid.data_ptr(), cap, cadu.data_ptr(), block.data_ptr(), info.data_ptr(), stream=st)
+
+        ms_p, mn_p = from_reset(lambda: (sync.reset(), dec.reset()), pair)
+        inf = info.cpu().numpy().view(xa.FRAME_INFO_DTYPE)
+        emit(case="framer + decoder on one stream, " + name, symbols=len(x), ms_median=round(ms_p, 3), ms_min=round(mn_p, 3),
+             rows=int(sync.stats()["rows"]), frames_ok=int(inf["ok"].sum()), frames_bad=int((inf["valid"] != 0).sum() - inf["ok"].sum()))
+        for recheck, lk in locks.items():
+            ms, mn = from_reset(lk.reset, lambda: lk.push_device(
+                x.data_ptr(), len(x), frames.data_ptr(), valid.data_ptr(), hits.data_ptr(), start.data_ptr(), mode.data_ptr(),
+                cadu.data_ptr(), block.data_ptr(), info.data_ptr(), count.data_ptr(), stream=st))
+            s = lk.stats()
+            emit(case="lock, " + name, recheck=recheck, symbols=len(x), ms_median=round(ms, 3), ms_min=round(mn, 3),
+                 over_pair=round(ms / ms_p, 4), rounds=int(s["rounds"]), sensitive_chunks=int(s["sensitive_chunks"]),
+                 short_kept=int(s["short_kept"]), short_missed=int(s["short_missed"]), rechecks=int(s["rechecks"]),
+                 rows=int(s["rows"]), frames_ok=int(s["frames_ok"]), frames_bad=int(s["frames_bad"]), resyncs=int(s["resyncs"]),
+                 rewalked_chunks=int(s["rewalked_chunks"]))
+    for h in (sync, dec, *locks.values()):
+        h.close()
+
+
 shared = []                                     # the packets and the files cases run on one stream of frames
 
 
@@ -379,6 +436,6 @@ def packet_chain():
     return shared[0]
 
 
-for what in ["decode", "demux", "packets", "files", "rice", "framer"] if args.what == "all" else [args.what]:
-    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "packets": lambda: bench_packets(packet_chain()),
+for what in ["decode", "demux", "packets", "files", "rice", "framer", "lock"] if args.what == "all" else [args.what]:
+    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "lock": bench_lock, "packets": lambda: bench_packets(packet_chain()),
      "files": lambda: bench_files(packet_chain())}[what]()

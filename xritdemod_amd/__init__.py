@@ -19,5 +19,6 @@ from ._capi import (  # noqa: F401
     PacketAssembler, PACKET_DTYPE, PACKETS_SUMMARY_DTYPE, PACKETS_STATS_DTYPE, packets_max_bytes,
     FileAssembler, FILE_PIECE_DTYPE, FILE_RECORD_DTYPE, FILES_SUMMARY_DTYPE, FILES_STATS_DTYPE, FILE_KEY_DTYPE,
     FrameSynchroniser, FRAMER_STATS_DTYPE, FRAMER_MAX_SYMBOLS,
+    FrameLock, LOCK_STATS_DTYPE, LOCK_FULL, LOCK_SHORT, LOCK_MISS, LOCK_RECHECK, FLYWHEEL_RECHECK,
     FILE_BEGINS, FILE_ENDS, FILE_ABORTED, FILE_LENGTH_MATCH, RiceDecoder, rice_form, is_rice_coded, decode_file_lines,
 )

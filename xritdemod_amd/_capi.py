@@ -98,6 +98,16 @@ _SIGNATURES = {
     "xrit_framer_push_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "xrit_framer_push": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "xrit_framer_stats": (C.c_int, [_vp, _vp]),
+    "xrit_lock_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
+    "xrit_lock_destroy": (C.c_int, [_vp]),
+    "xrit_lock_reset": (C.c_int, [_vp]),
+    "xrit_lock_set_flywheel": (C.c_int, [_vp, C.c_uint32]),
+    "xrit_lock_set_segment": (C.c_int, [_vp, C.c_uint32]),
+    "xrit_lock_set_windows": (C.c_int, [_vp, C.c_uint32]),
+    "xrit_lock_rows": (_sz, [_vp, _sz]),
+    "xrit_lock_push_device": (C.c_int, [_vp, _vp, _sz] + [_vp] * 10),
+    "xrit_lock_push": (C.c_int, [_vp, _vp, _sz] + [_vp] * 8),
+    "xrit_lock_stats": (C.c_int, [_vp, _vp]),
     "xrit_decoder_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "xrit_decoder_destroy": (C.c_int, [_vp]),
     "xrit_decoder_reset": (C.c_int, [_vp]),
@@ -837,6 +847,97 @@ class FrameDecoder(_Handle):
         """At most this many resident Viterbi windows per call from the next call on (0: the default, 8 per compute
         unit; clamped to 1 .. default).  The outputs do not depend on it."""
         _check(lib().xrit_decoder_set_windows(self._h, int(windows)))
+
+
+# ---- frame lock: framer and decoder as the reference's one loop, with its flywheel (newdecoder.cpp:218-237, 321-338; DESIGN.md 18)
+LOCK_FULL, LOCK_SHORT, LOCK_MISS, LOCK_RECHECK = 0, 1, 2, 4
+FLYWHEEL_RECHECK = 4                 # decoder/src/parameters.h:41
+# xrit_lock_counters: the framer's, then the loop's
+LOCK_STATS_DTYPE = np.dtype(FRAMER_STATS_DTYPE.descr + [(f, np.uint64) for f in (
+    "short_kept", "short_missed", "rechecks", "sensitive_chunks", "rounds", "frames_ok", "frames_bad")])
+assert LOCK_STATS_DTYPE.itemsize == 136
+
+
+class FrameLock(_Handle):
+    """FrameSynchroniser and FrameDecoder as the one loop the reference runs: after a good frame (its Reed-Solomon
+    outcome) only the first frame / 16 positions of the next chunk are correlated and position 0 is kept if it is the best
+    of them; every `flywheel` chunks the whole chunk is correlated again.  flywheel = 1 is the framer followed by the
+    decoder.  The rows do not depend on how the stream is cut into calls.  mode: "lrit" or "hrit"."""
+    _destroy = "xrit_lock_destroy"
+
+    def __init__(self, mode="lrit", device=0, flywheel=None, segment=0, windows=0):
+        super().__init__()
+        if mode not in ("lrit", "hrit"):
+            raise ValueError(f"mode {mode!r}: 'lrit' or 'hrit'")
+        self.mode = mode
+        _check(lib().xrit_lock_create(C.byref(self._h), 1 if mode == "hrit" else 0, device))
+        self.frame = CODED_FRAME_SIZE
+        if flywheel is not None:
+            self.set_flywheel(flywheel)
+        if segment:
+            self.set_segment(segment)
+        if windows:
+            self.set_windows(windows)
+
+    def set_flywheel(self, recheck):
+        """flywheelRecheck, 1 .. 255 (default 4); only before the first push."""
+        if not 0 <= int(recheck) < 1 << 32:
+            raise ValueError("flywheel recheck 1..255")
+        _check(lib().xrit_lock_set_flywheel(self._h, int(recheck)))
+
+    def set_segment(self, chunks):
+        """Chunks per walker segment (0: chosen per call).  The outputs do not depend on it."""
+        _check(lib().xrit_lock_set_segment(self._h, int(chunks)))
+
+    def set_windows(self, windows):
+        """Resident Viterbi windows a call uses at most (0: the default).  The outputs do not depend on it."""
+        _check(lib().xrit_lock_set_windows(self._h, int(windows)))
+
+    def rows(self, n):
+        """Rows the outputs of a push of n symbols must hold."""
+        return int(lib().xrit_lock_rows(self._h, int(n)))
+
+    def push(self, symbols, trim=True):
+        """Host buffers: (frames, valid, hits, start) as FrameSynchroniser.push gives them, mode (r,) uint8, and (cadu,
+        block, info) as FrameDecoder.decode gives them, of the rows this call emits; trim = False: all rows(n) rows, those
+        past the emitted ones absent, and the count as a ninth item."""
+        d = np.ascontiguousarray(symbols, np.int8).reshape(-1)
+        cap = self.rows(len(d))
+        frames = np.zeros((cap, self.frame), np.int8)
+        valid = np.zeros(cap, np.uint8)
+        hits = np.zeros((cap, 4), np.uint32)
+        start = np.zeros(cap, np.uint64)
+        mode = np.zeros(cap, np.uint8)
+        cadu = np.zeros((cap, CADU_SIZE), np.uint8)
+        block = np.zeros((cap, BLOCK_SIZE), np.uint8)
+        info = np.zeros(cap, FRAME_INFO_DTYPE)
+        got = lib().xrit_lock_push(self._h, _p(d) if len(d) else None, len(d), _p(frames), _p(valid), _p(hits), _p(start),
+                                   _p(mode), _p(cadu), _p(block), _p(info))
+        if got < 0:
+            _check(got)
+        out = (frames, valid, hits, start, mode, cadu, block, info)
+        if trim:
+            return tuple(a[:got] for a in out)
+        return out + (got,)
+
+    def push_device(self, d_symbols_ptr, n, d_frames_ptr, d_valid_ptr, d_hits_ptr, d_start_ptr, d_mode_ptr, d_cadu_ptr,
+                    d_block_ptr, d_info_ptr, d_count_ptr, stream=None):
+        """Device pointers, rows(n) rows each (cadu 16-byte aligned).  Queued on stream, which the call synchronises once
+        per round; ChannelDemux.process_device takes hits, cadu, block and info as they are with nf = rows(n)."""
+        ptrs = (d_frames_ptr, d_valid_ptr, d_hits_ptr, d_start_ptr, d_mode_ptr, d_cadu_ptr, d_block_ptr, d_info_ptr, d_count_ptr)
+        _check(lib().xrit_lock_push_device(self._h, C.c_void_p(d_symbols_ptr) if d_symbols_ptr else None, n,
+                                           *(C.c_void_p(q) if q else None for q in ptrs),
+                                           C.c_void_p(stream) if stream else None))
+
+    def stats(self):
+        """The counters after the last call (a LOCK_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, LOCK_STATS_DTYPE)
+        _check(lib().xrit_lock_stats(self._h, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Cursor 0, nothing carried, ok and fc cleared, the decoder's carry back to erasures, counters zero."""
+        _check(lib().xrit_lock_reset(self._h))
 
 
 # ---- channel demultiplexer and packet accounting (decoder/src/newdecoder.cpp:309-395) -------------------------------

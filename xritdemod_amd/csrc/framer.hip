@@ -15,6 +15,7 @@
 //  (d) framer_gather_kernel: the rows' frames with inversion, dword-wide across the carry / new-symbols seam, the zero
 //      rows, the small per-row outputs and the next call's carry.
 #include "kernels.h"
+#include "framer_query.h"
 #include "sync_core.h"
 
 namespace xrit {
@@ -92,49 +93,6 @@ __global__ void __launch_bounds__(FR_THREADS) framer_bits_kernel(FramerPar par, 
     unsigned u = k0 | (k1 << 16);
     const unsigned o = (unsigned)__shfl_xor((int)u, 1, 64);
     if (!(tid & 1u)) bmax[j >> 1] = max(u & 0xFFFFu, o & 0xFFFFu) | (max(u >> 16, o >> 16) << 16);
-}
-
-struct FrHit { unsigned word, pos, corr; };
-
-// One chunk's correlation, by a whole wave: positions c .. c + frame - 65 of V, every lane returns the answer.
-// Keys order (count desc, position asc) per word; the first word with the strictly greatest count wins (sync.hip).
-__device__ FrHit fr_query(const FramerPar &par, const unsigned *__restrict__ bits, const unsigned *__restrict__ bmax, unsigned c,
-                          unsigned lane)
-{
-    const unsigned first = c, last = c + par.frame - 65u;
-    const unsigned bf = first >> 6, bl = last >> 6;
-    unsigned k0 = 0, k1 = 0;
-    auto point = [&](unsigned p) {
-        const unsigned j = p >> 5, r = p & 31u;
-        unsigned hi, lo;
-        sync_window(bits[j], bits[j + 1], bits[j + 2], r, hi, lo);
-        const unsigned rel = 0xFFFFFu - (p - c);
-        k0 = max(k0, (sync_agree(hi, lo, par.whi[0], par.wlo[0]) << 20) | rel);
-        k1 = max(k1, (sync_agree(hi, lo, par.whi[1], par.wlo[1]) << 20) | rel);
-    };
-    const unsigned ph = (bf << 6) + lane;
-    if (ph >= first && ph <= last) point(ph);
-    if (bl != bf) {
-        const unsigned pt = (bl << 6) + lane;
-        if (pt <= last) point(pt);
-        for (unsigned b = bf + 1 + lane; b < bl; b += 64) {
-            const unsigned u = bmax[b], u0 = u & 0xFFFFu, u1 = u >> 16;
-            const unsigned base = (b << 6) - c;
-            k0 = max(k0, ((u0 >> 6) << 20) | (0xFFFFFu - (base + 63u - (u0 & 63u))));
-            k1 = max(k1, ((u1 >> 6) << 20) | (0xFFFFFu - (base + 63u - (u1 & 63u))));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        k0 = max(k0, (unsigned)__shfl_xor((int)k0, off, 64));
-        k1 = max(k1, (unsigned)__shfl_xor((int)k1, off, 64));
-    }
-    // every word starts at correlation 0 / position 0 and is replaced on '>': no agreeing bit at all reports position 0
-    FrHit h{0, 0, 0};
-    const unsigned c0 = k0 >> 20, c1 = k1 >> 20;
-    if (c0 > 0) { h.corr = c0; h.pos = 0xFFFFFu - (k0 & 0xFFFFFu); h.word = 0; }
-    if (c1 > h.corr) { h.corr = c1; h.pos = 0xFFFFFu - (k1 & 0xFFFFFu); h.word = 1; }
-    return h;
 }
 
 // (b) one wave per segment
@@ -328,20 +286,36 @@ size_t framer_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chun
     return c.used();
 }
 
+int launch_framer_bits(const FramerPar &par, const FramerState *state, const int8_t *carry_in, const int8_t *symbols,
+                       FramerScratch &sc, hipStream_t s)
+{
+    const unsigned tiles = bit_tiles(par.n, par.frame);
+    hipLaunchKernelGGL(framer_bits_kernel, dim3(tiles), dim3(FR_THREADS), 0, s, par, state, carry_in, symbols, sc.bits, sc.bmax);
+    XR_HIP(hipGetLastError());
+    return XRIT_OK;
+}
+
+int launch_framer_gather(const FramerPar &par, const FramerCall *call, const int8_t *carry_in, const int8_t *symbols,
+                         const uint4 *rows, int8_t *carry_out, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits,
+                         unsigned long long *start, hipStream_t s)
+{
+    const unsigned per = (par.frame / 4 + FR_THREADS - 1) / FR_THREADS;
+    hipLaunchKernelGGL(framer_gather_kernel, dim3(par.cap + 1, per > 16 ? 16 : (per ? per : 1)), dim3(FR_THREADS), 0, s, par, call,
+                       carry_in, symbols, rows, carry_out, frames, valid, hits, start);
+    XR_HIP(hipGetLastError());
+    return XRIT_OK;
+}
+
 int launch_framer(const FramerPar &par, FramerState *state, const int8_t *carry_in, int8_t *carry_out, const int8_t *symbols,
                   FramerScratch &sc, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits, unsigned long long *start,
                   unsigned *count, hipStream_t s)
 {
-    const unsigned tiles = bit_tiles(par.n, par.frame);
-    hipLaunchKernelGGL(framer_bits_kernel, dim3(tiles), dim3(FR_THREADS), 0, s, par, state, carry_in, symbols, sc.bits, sc.bmax);
+    XR_TRY(launch_framer_bits(par, state, carry_in, symbols, sc, s));
     hipLaunchKernelGGL(framer_walk_kernel, dim3(par.segs), dim3(64), 0, s, par, state, sc.bits, sc.bmax, sc.rec, sc.nrec, sc.wout);
     hipLaunchKernelGGL(framer_joints_kernel, dim3(1), dim3(64), 0, s, par, state, sc.bits, sc.bmax, sc.rec, sc.nrec, sc.wout, sc.rows,
                        sc.call, count);
-    const unsigned per = (par.frame / 4 + FR_THREADS - 1) / FR_THREADS;
-    hipLaunchKernelGGL(framer_gather_kernel, dim3(par.cap + 1, per > 16 ? 16 : (per ? per : 1)), dim3(FR_THREADS), 0, s, par, sc.call,
-                       carry_in, symbols, sc.rows, carry_out, frames, valid, hits, start);
     XR_HIP(hipGetLastError());
-    return XRIT_OK;
+    return launch_framer_gather(par, sc.call, carry_in, symbols, sc.rows, carry_out, frames, valid, hits, start, s);
 }
 
 }  // namespace xrit

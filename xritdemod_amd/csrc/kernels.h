@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "framer_host.h"
+#include "lock_host.h"
 #include "loop_core.h"
 #include "taps.h"
 
@@ -507,6 +508,31 @@ unsigned framer_segments(size_t n, unsigned frame, unsigned seg_chunks);
 int launch_framer(const FramerPar &par, FramerState *state, const int8_t *carry_in, int8_t *carry_out, const int8_t *symbols,
                   FramerScratch &sc, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits, unsigned long long *start,
                   unsigned *count, hipStream_t s);
+// ... its first and last launches on their own, for the frame lock: the hard bits and per-64 maxima of V; the frames,
+// valid, hits and start of par.cap rows (of which call->count exist) and the next call's carry
+int launch_framer_bits(const FramerPar &par, const FramerState *state, const int8_t *carry_in, const int8_t *symbols,
+                       FramerScratch &sc, hipStream_t s);
+int launch_framer_gather(const FramerPar &par, const FramerCall *call, const int8_t *carry_in, const int8_t *symbols,
+                         const uint4 *rows, int8_t *carry_out, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits,
+                         unsigned long long *start, hipStream_t s);
+// frame lock (lock.hip): the framer's walk with the reference's flywheel, coupled to the decoder's RS outcome.  A call is
+// one pass of bits / maxima / walkers and then rounds of joints, gather, decoder and commit; a round ends where the walk
+// needs the RS outcome of a row that the round itself emitted.
+struct LockPar {
+    unsigned recheck;                       // flywheelRecheck, 1 .. 255
+    unsigned span;                          // the short range: frame / 16 symbols
+    unsigned first;                         // 1: the call's first round (cursor 0, no rows yet)
+    unsigned r0;                            // rows the call's earlier rounds emitted
+};
+struct LockScratch {
+    FramerScratch fr;                       // rec[].y: word | short hit at position 0 << 1 | short word << 2 | short count << 8
+    unsigned char *flags;                   // [cap] per row: full position != 0 | short position == 0 << 1 | short hit used << 2
+};
+size_t lock_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chunks, LockScratch &sc);
+int launch_lock_walk(const FramerPar &par, const LockPar &lp, const LockState *state, LockScratch &sc, hipStream_t s);
+int launch_lock_joints(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, unsigned *count, hipStream_t s);
+int launch_lock_commit(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, const xrit_frame_info *info,
+                       unsigned char *mode, hipStream_t s);
 // packet assembler (packets.hip): the handle's state, the per-call scratch (R = max(max_rows, 1) rows)
 constexpr unsigned PACKETS_PEND_MAX = 65541;        // a pending packet is shorter than the longest packet (65542)
 constexpr unsigned PACKETS_TILE = 1024;             // rows per tile of the scan

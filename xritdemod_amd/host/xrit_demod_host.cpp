@@ -87,6 +87,7 @@ struct Options {
     std::string files;             // --files DIR: the LRIT/HRIT files, DIR/vc{vcid}_apid{apid}_{serial}.lrit
     bool files_decompress = false; // --files-decompress: the scan lines of rice-coded image files, ..._{serial}.img
     bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
+    int flywheel = 0;              // --flywheel [N]: the frame lock (xrit_lock_*) in place of framer and decoder, flywheelRecheck = N
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -105,6 +106,11 @@ void usage()
                  "         [--stream-sync]   (with --decode and the options behind it: frames are found by the stream frame synchroniser,\n"
                  "                            which walks the symbols chunk by chunk from where the last frame ended like the reference's\n"
                  "                            decoder, instead of by correlating fixed 16384-symbol windows; resynchronisations on stderr at exit)\n"
+                 "         [--flywheel [N]]   (implies --stream-sync: synchroniser and decoder run as the reference's one loop, the frame lock --\n"
+                 "                             after a frame that Reed-Solomon accepts only the first 1024 positions of the next chunk are\n"
+                 "                             correlated and position 0 is kept if it is the best of them; every N chunks (1..255, default 4,\n"
+                 "                             the reference's flywheelRecheck) the whole chunk is correlated again; a token behind the\n"
+                 "                             flag that begins with a digit is taken as N, so a bare --flywheel goes last or before an option)\n"
                  "         [--channels DIR]   (the decoder's ChannelWriter: every good VCDU appended to DIR/channel_{vcid}.bin)\n"
                  "         [--decoder-stats PATH]   (the decoder's Statistics_st, 4167 bytes per valid frame; lost packets on stderr at exit)\n"
                  "         [--packets DIR]   (CCSDS space packets out of the channels' VCDUs: every packet whose CRC-16 matches appended whole,\n"
@@ -152,6 +158,16 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--files") { if (!(v = need("--files"))) return false; o.files = v; }
         else if (a == "--files-decompress") o.files_decompress = true;
         else if (a == "--stream-sync") o.stream_sync = true;
+        else if (a == "--flywheel") {
+            o.flywheel = 4;                 // parameters.h:41
+            o.stream_sync = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {      // a token that begins with a digit is N, whole
+                char *end = nullptr;
+                const long r = std::strtol(argv[++i], &end, 10);
+                if (*end != '\0' || r < 1 || r > 255) { std::fprintf(stderr, "--flywheel %s: 1..255\n", argv[i]); return false; }
+                o.flywheel = (int)r;
+            }
+        }
         else if (a == "--fifo") o.fifo = true;
         else if (a == "--front-exact") {
             o.front_exact = 1;
@@ -207,6 +223,8 @@ struct FrameDecode {
     FILE *stats_out = nullptr;
     xrit_decoder *dec = nullptr;
     xrit_framer *fr = nullptr;      // --stream-sync
+    xrit_lock *lk = nullptr;        // --flywheel: in place of fr and dec
+    std::vector<uint8_t> modes;
     std::vector<uint64_t> starts;
     xrit_framer_counters fr_stats{};
     xrit_demux *dm = nullptr;
@@ -241,15 +259,21 @@ struct FrameDecode {
     size_t n_frames = 0, n_ok = 0, n_dropped = 0, rs_corrections = 0, viterbi_errors = 0;
 
     bool open(const std::string &path, const std::string &channels, const std::string &stats_path, const std::string &packets,
-              const std::string &files, bool files_decompress, bool hrit_mode, int dev, bool stream_sync = false)
+              const std::string &files, bool files_decompress, bool hrit_mode, int dev, bool stream_sync = false,
+              int flywheel = 0)
     {
         hrit = hrit_mode;
         device = dev;
-        if (xrit_decoder_create(&dec, hrit ? 1 : 0, device) != XRIT_OK) {
+        if (flywheel) {
+            if (xrit_lock_create(&lk, hrit ? 1 : 0, device) != XRIT_OK || xrit_lock_set_flywheel(lk, (uint32_t)flywheel) != XRIT_OK) {
+                std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                return false;
+            }
+        } else if (xrit_decoder_create(&dec, hrit ? 1 : 0, device) != XRIT_OK) {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
         }
-        if (stream_sync && xrit_framer_create(&fr, hrit ? 1 : 0, device) != XRIT_OK) {
+        if (stream_sync && !flywheel && xrit_framer_create(&fr, hrit ? 1 : 0, device) != XRIT_OK) {
             std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
             return false;
         }
@@ -306,8 +330,32 @@ struct FrameDecode {
         raw_hits.assign(hits.begin(), hits.begin() + (std::ptrdiff_t)take);
         return true;
     }
+    // --flywheel: the lock's rows are the framer's and the decoder's at once
+    bool lock_stream(const int8_t *sym, size_t n, size_t &take)
+    {
+        const size_t cap = xrit_lock_rows(lk, n);
+        hits.resize(cap);
+        frames.resize(cap * FRAME);
+        valid.resize(cap);
+        starts.resize(cap);
+        modes.resize(cap);
+        cadu.resize(cap * 1024);
+        block.resize(cap * 1020);
+        info.resize(cap);
+        const int got = xrit_lock_push(lk, sym, n, frames.data(), valid.data(), hits.data(), starts.data(), modes.data(), cadu.data(),
+                                       block.data(), info.data());
+        if (got < 0) return fail("frame lock");
+        take = (size_t)got;
+        raw_hits.assign(hits.begin(), hits.begin() + (std::ptrdiff_t)take);
+        return true;
+    }
     bool add(const int8_t *sym, size_t n)
     {
+        if (lk) {
+            size_t take = 0;
+            if (!lock_stream(sym, n, take)) return false;
+            return take == 0 || account_frames(take);
+        }
         if (fr) {
             size_t take = 0;
             if (!sync_stream(sym, n, take)) return false;
@@ -344,6 +392,11 @@ struct FrameDecode {
         info.resize(take);
         if (xrit_decoder_decode(dec, frames.data(), valid.data(), take, cadu.data(), block.data(), info.data()) != XRIT_OK)
             return fail("decode");
+        return account_frames(take);
+    }
+    // the counts, the VCDUs of the good frames and the stages behind the decoder on the first `take` rows of cadu / block / info
+    bool account_frames(size_t take)
+    {
         for (size_t f = 0; f < take; ++f) {
             if (!info[f].valid) continue;
             ++n_frames;
@@ -482,11 +535,27 @@ struct FrameDecode {
     }
     void close()
     {
-        if (dec) {
+        if (dec || lk)
             std::fprintf(stderr, "decode: %zu frames, %zu ok, %zu dropped, %zu RS corrections, mean Viterbi errors %.2f\n", n_frames,
                          n_ok, n_dropped, rs_corrections, n_frames ? (double)viterbi_errors / (double)n_frames : 0.0);
+        if (dec) {
             xrit_decoder_destroy(dec);
             dec = nullptr;
+        }
+        if (lk) {
+            xrit_lock_counters c{};
+            if (xrit_lock_stats(lk, &c) == XRIT_OK) {
+                std::fprintf(stderr, "sync: %llu symbols, %llu frames, %llu chunks dropped, %llu resynchronisations, %llu symbols left\n",
+                             (unsigned long long)c.framer.symbols, (unsigned long long)c.framer.frames,
+                             (unsigned long long)c.framer.dropped_chunks, (unsigned long long)c.framer.resyncs,
+                             (unsigned long long)c.framer.carry);
+                std::fprintf(stderr, "lock: %llu chunks kept at position 0 of the short range, %llu missed there, %llu rechecks, "
+                                     "%llu chunks that hung on the frame before, %llu rounds in %llu calls\n",
+                             (unsigned long long)c.short_kept, (unsigned long long)c.short_missed, (unsigned long long)c.rechecks,
+                             (unsigned long long)c.sensitive_chunks, (unsigned long long)c.rounds, (unsigned long long)c.framer.calls);
+            }
+            xrit_lock_destroy(lk);
+            lk = nullptr;
         }
         if (fr) {
             if (xrit_framer_stats(fr, &fr_stats) == XRIT_OK)
@@ -838,7 +907,7 @@ int main(int argc, char **argv)
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
     if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
-        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync)) {
+        !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync, o.flywheel)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
@@ -967,7 +1036,7 @@ int main(int argc, char **argv)
             rc = xrit_quantize_i8(chain, soft.data(), q.data(), nsym);
             if (rc != XRIT_OK) { std::fprintf(stderr, "quantize: %s\n", xrit_last_error()); exit_code = 1; break; }
             if (!sink.send_all(q.data(), nsym)) { exit_code = 1; break; }
-            if (decode.dec && !decode.add(q.data(), nsym)) { exit_code = 1; break; }
+            if ((decode.dec || decode.lk) && !decode.add(q.data(), nsym)) { exit_code = 1; break; }
         }
         if (diag.fd >= 0 && nsym > 0) {
             // the first symbols of the call, complex (stage 4); only what the tap can take is copied back
