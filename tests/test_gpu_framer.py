@@ -186,6 +186,31 @@ def test_tiny_frames_joints_and_rewalk(xa, tiny, segment):
     sync.close()
 
 
+def test_rewalked_chunks_counts_a_chunk_once_when_it_is_consumed(xa, oracle_mod):
+    """frame = 320, segments of one chunk, 10 frames behind 100 symbols of noise with one symbol inserted in front of
+    frame 6: behind chunk 0 the chain never stands on a walker's start, so every step is a real one.  The first call ends
+    one symbol short of frame 6: its real step must wait and is walked again in the second call.  It is counted there,
+    once: rewalked_chunks + adopted_chunks is the number of rows after either call."""
+    rng = np.random.default_rng(5)
+    frame, n, offset = 320, 10, 100
+    word = np.array([60 if (fs.LRIT_WORDS[0] >> (63 - k)) & 1 else -60 for k in range(64)], np.int8)
+    body = rng.choice(np.array([-60, 60], np.int8), (n, frame))
+    body[:, :64] = word
+    noise = rng.integers(-20, 21, offset).astype(np.int8)
+    stream = np.concatenate([noise, body[:6].reshape(-1), noise[:1], body[6:].reshape(-1)])
+    cut = offset + 7 * frame                                    # frame 6 begins at offset + 6 * frame + 1
+    sync, spec = xa.FrameSynchroniser("lrit", frame=frame, segment=1), fs.Framer(frame=frame)
+    first = push_and_compare(sync, spec, [stream[:cut]])
+    assert len(first) == 6 and spec.carry == frame              # the chunk at the cursor is whole, its frame is not
+    st = check_stats(sync, spec)
+    assert int(st["adopted_chunks"]) == 1 and int(st["rewalked_chunks"]) == 5
+    rest = push_and_compare(sync, spec, [stream[cut:]])
+    assert len(rest) == 4 and int(rest.hits[0][1]) == 1
+    st = check_stats(sync, spec)
+    assert int(st["rewalked_chunks"]) + int(st["adopted_chunks"]) == int(st["rows"]) == 10
+    sync.close()
+
+
 def test_reset_in_mid_stream(xa, drifting):
     stream = drifting["stream"]
     sync = xa.FrameSynchroniser("lrit")

@@ -278,3 +278,75 @@ def test_hundreds_of_frames_in_lock_with_whole_waves_of_records(xa, oracle_mod):
         lock.close()
     sync.close()
     dec.close()
+
+
+def test_recheck_1_adopts_batches_out_of_lock_in_parallel(xa, oracle_mod):
+    """200 frames (8 coded frames tiled) with the last symbol of every 50th frame deleted and one chunk zeroed, walker
+    segments of 128 chunks, two calls cut in mid-frame: with flywheel = 1 the joints copy a walker's record, longer than a
+    wave and not all in lock, batch by batch.  The synchroniser against the specification first, then the lock against
+    the synchroniser followed by the decoder; once more with segments of 7 chunks, real steps and adoption in one call."""
+    frames, _ = fc.coded_frames(8, np.random.default_rng(3))
+    sent = np.tile(frames, (25, 1))
+    sent[20] = 0
+    stream = np.concatenate([f[:-1] if i % 50 == 49 else f for i, f in enumerate(sent)])
+    cuts = [140 * F + 5000]
+    assert len(stream) == 200 * F - 4
+    want_rows, per_call, spec = fs.walk(stream, cuts)
+    assert spec.resyncs >= 3 and spec.dropped >= 1 and len(want_rows) > 128 and len(per_call[0]) > 128
+    assert int(want_rows.hits[0][1]) == 0                               # the stream's first chunk is a frame at position 0
+
+    sync, dec = xa.FrameSynchroniser("lrit", segment=128), xa.FrameDecoder("lrit")
+    want = []
+    for piece, rows in zip(pieces_of(stream, cuts), per_call):
+        w = sync.push(piece, trim=False)
+        assert w[4] == len(rows)
+        for name, got in zip(("frames", "valid", "hits", "start"), w):
+            assert np.array_equal(got[:w[4]], getattr(rows, name)), name
+            assert not got[w[4]:].any(), name
+        want.append(w + dec.decode(w[0], w[1]))
+    b = sync.stats()
+    assert [int(b[k]) for k in fs.STATS] == [spec.stats()[k] for k in fs.STATS]
+
+    for segment in (128, 7):
+        lock = xa.FrameLock("lrit", flywheel=1, segment=segment)
+        first = True
+        for piece, w in zip(pieces_of(stream, cuts), want):
+            *out, count = lock.push(piece, trim=False)
+            assert count == w[4]
+            for name, got, wanted in zip(ls.FIELDS, out, w[:4] + (None,) + w[5:]):
+                if name == "mode":
+                    want_mode = [xa.LOCK_FULL | xa.LOCK_RECHECK] * count + [0] * (len(got) - count)
+                    if first:
+                        want_mode[0] = xa.LOCK_FULL
+                    assert got.tolist() == want_mode
+                elif name == "info":
+                    assert got.tobytes() == wanted.tobytes()
+                else:
+                    assert np.array_equal(got, wanted), (name, segment)
+            first = False
+        a = lock.stats()
+        print("segment", segment, {k: int(a[k]) for k in a.dtype.names})
+        if segment == 128:
+            assert [int(a[k]) for k in b.dtype.names] == [int(b[k]) for k in b.dtype.names]
+            assert int(a["adopted_chunks"]) > 64
+            assert int(a["short_kept"]) == int(a["short_missed"]) == int(a["sensitive_chunks"]) == 0
+            assert int(a["rounds"]) == int(a["calls"]) == 2
+        lock.close()
+    sync.close()
+    dec.close()
+
+
+def test_recheck_1_counts_the_first_chunk_behind_a_reset_sensitive(xa, oracle_mod):
+    """A plant in frame 0 and nothing in front of it: the stream's first chunk is entered with fc = 0 != recheck, its
+    whole-chunk hit is the plant and its short hit is at position 0.  With flywheel = 1 the chunk is FULL and follows the
+    plant, and it is the one chunk that sensitive_chunks can count: whether the first call emits a row or none, and not
+    again behind it or in the calls that follow."""
+    stream, starts = lc.stream_a(plants=(0,))
+    stream = stream[int(starts[0]):]
+    for cuts in ([], [100, 5 * F]):
+        lock, spec = xa.FrameLock("lrit", flywheel=1), ls.Lock(recheck=1)
+        got = push_and_compare(lock, spec, pieces_of(stream, cuts))
+        assert int(got.hits[0][1]) == lc.PLANT_AT and int(got.mode[0]) == xa.LOCK_FULL
+        st = check_stats(lock, spec)
+        assert int(st["sensitive_chunks"]) == 1 and int(st["rounds"]) == int(st["calls"]) == len(cuts) + 1
+        lock.close()

@@ -1,6 +1,7 @@
-// framer_host.h -- the plain host parts of the stream frame synchroniser (framer.cpp): the handle's state record as the
-// kernels keep it, the row bound, the argument checks, the segment length and the counters' copy.  No HIP here, so that a
-// stand-alone program can run these under a sanitizer on the CPU.
+// framer_host.h -- the plain host parts of the stream frame synchroniser (framer.cpp, and lock.cpp through frame_cores.h):
+// the handle's state record as the kernels keep it, the sync words, the row bound, the argument checks, the segment
+// length, a call's parameters and the counters' copy.  No HIP here, so that a stand-alone program can run these under a
+// sanitizer on the CPU.
 #pragma once
 
 #include <cstddef>
@@ -18,9 +19,26 @@ struct FramerState {
     unsigned reserved;
 };
 
+// a call's parameters, as every kernel of the call takes them: carry ++ new symbols is the call's view V; offsets are
+// relative to V[0], the cursor at the start of the call
+struct FramerPar {
+    unsigned frame, min_corr, invert;       // invert: LRIT (a frame found with word != 0 is inverted)
+    unsigned whi[2], wlo[2];                // the two sync words
+    unsigned n;                             // new symbols of this call
+    unsigned seg_chunks, seg_bytes, segs;   // S, S * frame, segments (walkers) of this call
+    unsigned cap;                           // rows the outputs hold
+};
+
 namespace framer_host {
 
 constexpr uint32_t FRAME_MIN = 65, FRAME_MAX = 1u << 20;
+
+// the two encoded 64-bit sync words the correlator is given (newdecoder.cpp:21-24)
+inline void sync_words(int hrit, uint64_t words[2])
+{
+    words[0] = hrit ? 0xfc4ef4fd0cc2df89ull : 0xfca2b63db00d9794ull;
+    words[1] = hrit ? 0x25010b02f33d2076ull : 0x035d49c24ff2686bull;
+}
 
 // rows a call of n symbols emits at most: the carry is at most 2 * frame - 66 bytes and every row consumes a frame
 inline size_t rows_cap(size_t n, uint32_t frame) { return (n + 2 * (size_t)frame - 66) / frame; }
@@ -60,6 +78,34 @@ inline uint32_t segment_chunks(size_t span, uint32_t frame, uint32_t set)
     }
     const uint32_t most = (uint32_t)(((size_t)1 << 31) / frame);
     return s > most ? most : s;
+}
+
+// walker segments of S chunks that cover the longest view of a call of n symbols
+inline uint32_t segments(size_t n, uint32_t frame, uint32_t seg_chunks)
+{
+    const size_t seg = (size_t)seg_chunks * frame;
+    return (uint32_t)((span_max(n, frame) + seg - 1) / seg);
+}
+
+// the parameters of a call of n symbols; `segment` as given to segment_chunks
+inline FramerPar call_par(int hrit, uint32_t frame, uint32_t min_corr, uint32_t segment, size_t n)
+{
+    uint64_t words[2];
+    sync_words(hrit, words);
+    FramerPar par{};
+    par.frame = frame;
+    par.min_corr = min_corr;
+    par.invert = hrit ? 0u : 1u;
+    for (int w = 0; w < 2; ++w) {
+        par.whi[w] = (unsigned)(words[w] >> 32);
+        par.wlo[w] = (unsigned)(words[w] & 0xFFFFFFFFull);
+    }
+    par.n = (unsigned)n;
+    par.seg_chunks = segment_chunks(span_max(n, frame), frame, segment);
+    par.seg_bytes = par.seg_chunks * frame;
+    par.segs = segments(n, frame, par.seg_chunks);
+    par.cap = (unsigned)rows_cap(n, frame);
+    return par;
 }
 
 inline void copy_counters(const FramerState &s, xrit_framer_counters *out)

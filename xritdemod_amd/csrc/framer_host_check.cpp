@@ -1,5 +1,6 @@
 // framer_host_check.cpp -- the stream frame synchroniser's plain host parts (framer_host.h) in a program of their own:
-// the row bound against a serial count, the argument checks, the segment length and the counters' copy.  Built and run
+// the row bound against a serial count, the argument checks, the sync words, the segment length, a call's parameters and
+// the counters' copy.  Built and run
 // by `make framer-host-check` with -fsanitize=address,undefined; exits non-zero on the first failed check.
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +61,27 @@ int main()
     for (uint32_t frame : {65u, 320u, 16384u, 1u << 20})
         for (uint32_t set : {0u, 1u, 64u, 1u << 20, 0xFFFFFFFFu})
             CHECK((uint64_t)segment_chunks(span_max((size_t)1 << 30, frame), frame, set) * frame <= ((uint64_t)1 << 31));
+
+    // the sync words (each the other's complement on LRIT: the other phase of the lock) and a call's parameters
+    uint64_t lrit[2], hrit[2];
+    sync_words(0, lrit);
+    sync_words(1, hrit);
+    CHECK(lrit[0] == 0xfca2b63db00d9794ull && lrit[1] == 0x035d49c24ff2686bull && (lrit[0] ^ lrit[1]) == ~0ull);
+    CHECK(hrit[0] == 0xfc4ef4fd0cc2df89ull && hrit[1] == 0x25010b02f33d2076ull);
+    CHECK(segments(0, 16384, 4) == 1 && segments((size_t)1 << 30, 16384, 256) == 257 && segments(1, 65, 1) == 1);
+    for (uint32_t frame : {65u, 320u, 16384u, 1u << 20})
+        for (size_t n : {(size_t)0, (size_t)1, (size_t)100000, (size_t)1 << 30})
+            for (uint32_t set : {0u, 1u, 7u, 0xFFFFFFFFu}) {
+                const FramerPar par = call_par(frame == 320, frame, 46, set, n);
+                CHECK(par.frame == frame && par.min_corr == 46 && par.n == n && par.invert == (frame == 320 ? 0u : 1u));
+                CHECK((((uint64_t)par.whi[0] << 32) | par.wlo[0]) == (frame == 320 ? hrit[0] : lrit[0]));
+                CHECK((((uint64_t)par.whi[1] << 32) | par.wlo[1]) == (frame == 320 ? hrit[1] : lrit[1]));
+                CHECK(par.cap == rows_cap(n, frame) && par.seg_chunks == segment_chunks(span_max(n, frame), frame, set));
+                CHECK(par.seg_chunks >= 1 && par.seg_bytes == par.seg_chunks * frame && par.segs >= 1);
+                // the segments cover the longest view, and the last one is needed for it
+                CHECK((uint64_t)par.segs * par.seg_bytes >= span_max(n, frame));
+                CHECK((uint64_t)(par.segs - 1) * par.seg_bytes < span_max(n, frame));
+            }
 
     FramerState s{};
     s.symbols = 11; s.cursor = 7; s.rows = 5; s.frames = 4; s.dropped = 1; s.resyncs = 2; s.rewalked = 3; s.adopted = 2; s.calls = 9;

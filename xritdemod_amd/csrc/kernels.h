@@ -481,15 +481,10 @@ size_t demux_scratch_carve(void *p, size_t nf, DemuxScratch &sc);     // returns
 int launch_demux(const xrit_sync_hit *hits, const unsigned char *cadu, size_t cadu_stride, const unsigned char *block,
                  const xrit_frame_info *info, size_t nf, DemuxState *state, DemuxScratch &sc, unsigned char *vcdu,
                  unsigned *offsets, xrit_frame_stats *records, hipStream_t s);
-// stream frame synchroniser (framer.hip): carry ++ new symbols is the call's view V; offsets below are relative to V[0],
-// the cursor at the start of the call
-struct FramerPar {
-    unsigned frame, min_corr, invert;       // invert: LRIT (a frame found with word != 0 is inverted)
-    unsigned whi[2], wlo[2];                // the two sync words
-    unsigned n;                             // new symbols of this call
-    unsigned seg_chunks, seg_bytes, segs;   // S, S * frame, segments (walkers) of this call
-    unsigned cap;                           // rows the outputs hold
-};
+// stream frame synchroniser and frame lock (framer.hip, lock.hip).  A call's view V is carry ++ new symbols (FramerPar,
+// framer_host.h).  The synchroniser's call is bits / maxima, walkers, joints, gather; the lock's is bits / maxima and
+// walkers once and then rounds of joints, gather, decoder and commit, where a round ends at a chunk whose hit needs
+// the RS outcome of a row that the round itself emitted.
 struct FramerCall {                         // what the joints leave for the gather of the same call
     unsigned long long base;                // absolute offset of V[0]
     unsigned carry, total, cursor, count;   // bytes of carry in V, bytes of V, the cursor after the call, rows emitted
@@ -497,41 +492,36 @@ struct FramerCall {                         // what the joints leave for the gat
 struct FramerScratch {
     unsigned *bits;                 // hard bits of V, 32 per word, MSB = first byte
     unsigned *bmax;                 // per run of 64 positions: the best (count << 6 | 63 - offset) of word 0 | of word 1 << 16
-    uint4 *rec;                     // [segs][S] a walker's steps: (cursor, word, position, correlation)
+    uint4 *rec;                     // [segs][S] a walker's steps: (cursor, word | short hit at position 0 << 1 | short word << 2 |
+                                    // short count << 8, position, correlation)
     unsigned *nrec;                 // [segs] steps recorded
     uint2 *wout;                    // [segs] (the cursor the walker left with, 1: it stopped for want of symbols)
-    uint4 *rows;                    // [cap] the call's rows, as the steps
+    uint4 *rows;                    // [cap] the call's rows: (cursor, word, position, correlation) of the hit that was used
+    unsigned char *flags;           // [cap] per row: full position != 0 | short position == 0 << 1 | short hit used << 2
     FramerCall *call;
 };
+struct LockPar {
+    unsigned recheck;                       // flywheelRecheck, 1 .. 255; 1: no flywheel, the synchroniser's walk
+    unsigned span;                          // the short range: frame / 16 symbols (the synchroniser has none: 0)
+    unsigned first;                         // 1: the call's first round (cursor 0, no rows yet)
+    unsigned r0;                            // rows the call's earlier rounds emitted
+    unsigned short0;                        // 1, only with recheck 1: no chunk was consumed since the reset (fc is 0), so the
+                                            // chunk at cursor 0 may be counted sensitive; the walk records its short hit
+};
 size_t framer_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chunks, FramerScratch &sc);
-unsigned framer_segments(size_t n, unsigned frame, unsigned seg_chunks);
-int launch_framer(const FramerPar &par, FramerState *state, const int8_t *carry_in, int8_t *carry_out, const int8_t *symbols,
-                  FramerScratch &sc, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits, unsigned long long *start,
-                  unsigned *count, hipStream_t s);
-// ... its first and last launches on their own, for the frame lock: the hard bits and per-64 maxima of V; the frames,
-// valid, hits and start of par.cap rows (of which call->count exist) and the next call's carry
+// framer.hip: the hard bits and per-64 maxima of V; the frames, valid, hits and start of par.cap rows (of which
+// call->count exist) and the next call's carry
 int launch_framer_bits(const FramerPar &par, const FramerState *state, const int8_t *carry_in, const int8_t *symbols,
                        FramerScratch &sc, hipStream_t s);
 int launch_framer_gather(const FramerPar &par, const FramerCall *call, const int8_t *carry_in, const int8_t *symbols,
                          const uint4 *rows, int8_t *carry_out, int8_t *frames, unsigned char *valid, xrit_sync_hit *hits,
                          unsigned long long *start, hipStream_t s);
-// frame lock (lock.hip): the framer's walk with the reference's flywheel, coupled to the decoder's RS outcome.  A call is
-// one pass of bits / maxima / walkers and then rounds of joints, gather, decoder and commit; a round ends where the walk
-// needs the RS outcome of a row that the round itself emitted.
-struct LockPar {
-    unsigned recheck;                       // flywheelRecheck, 1 .. 255
-    unsigned span;                          // the short range: frame / 16 symbols
-    unsigned first;                         // 1: the call's first round (cursor 0, no rows yet)
-    unsigned r0;                            // rows the call's earlier rounds emitted
-};
-struct LockScratch {
-    FramerScratch fr;                       // rec[].y: word | short hit at position 0 << 1 | short word << 2 | short count << 8
-    unsigned char *flags;                   // [cap] per row: full position != 0 | short position == 0 << 1 | short hit used << 2
-};
-size_t lock_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chunks, LockScratch &sc);
-int launch_lock_walk(const FramerPar &par, const LockPar &lp, const LockState *state, LockScratch &sc, hipStream_t s);
-int launch_lock_joints(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, unsigned *count, hipStream_t s);
-int launch_lock_commit(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, const xrit_frame_info *info,
+// lock.hip: the chain -- the walk of both, the synchroniser's joints, the lock's joints and commit.  The synchroniser's
+// state is a LockState too, of which its joints are given the FramerState in front
+int launch_plain_joints(const FramerPar &par, FramerState *state, FramerScratch &sc, unsigned *count, hipStream_t s);
+int launch_lock_walk(const FramerPar &par, const LockPar &lp, const LockState *state, FramerScratch &sc, hipStream_t s);
+int launch_lock_joints(const FramerPar &par, const LockPar &lp, LockState *state, FramerScratch &sc, unsigned *count, hipStream_t s);
+int launch_lock_commit(const FramerPar &par, const LockPar &lp, LockState *state, FramerScratch &sc, const xrit_frame_info *info,
                        unsigned char *mode, hipStream_t s);
 // packet assembler (packets.hip): the handle's state, the per-call scratch (R = max(max_rows, 1) rows)
 constexpr unsigned PACKETS_PEND_MAX = 65541;        // a pending packet is shorter than the longest packet (65542)

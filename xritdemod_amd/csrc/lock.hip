@@ -1,45 +1,185 @@
-// lock.hip -- frame lock (include/xritdemod_amd.h, "Frame lock"): the reference decoder's loop with
-// its flywheel (decoder/src/newdecoder.cpp:218-237, 321-338), where the range a chunk is correlated over hangs on the
-// Reed-Solomon outcome of the frame before it.  The bits / maxima pass and the gather are the framer's (framer.hip), the
-// decoder's kernels are viterbi.hip and rs.hip; here are the three kernels that know about ok and fc.
+// lock.hip -- the chain of the stream frame synchroniser and of the frame lock (include/xritdemod_amd.h, "Stream frame
+// synchroniser", "Frame lock"; DESIGN.md sections 17 and 18): the reference decoder's walk over a stream of soft symbols,
+// chunk by chunk (decoder/src/newdecoder.cpp:212-270), with its flywheel (:218-237, 321-338), where the range a chunk is
+// correlated over hangs on the Reed-Solomon outcome of the frame before it.  lp.recheck == 1 is the walk without the
+// flywheel: the synchroniser's, and the lock's with flywheel = 1.  The bits / maxima pass and the gather are framer.hip's,
+// the decoder's kernels are viterbi.hip and rs.hip.
 //
-//  (b') lock_walk_kernel: the framer's segment walkers, which also record, where the whole-chunk hit is not at position
-//       0, the hit over the first frame / 16 symbols.  Both are functions of the cursor alone.  (Where the whole-chunk
-//       hit is at position 0 the short hit equals it: the short range is a prefix of the whole, so no word reaches a
-//       greater count there than in the whole, and the winner's count is reached at position 0, the first of both.)
-//  (c') lock_joints_kernel: one wave follows the true chain through the records and carries what it knows of (ok, fc).
-//       ok is not known behind a valid row of this round (its RS outcome comes with the round's decoder) and fc is not
-//       known behind a chunk that is MISS or FULL according to such an ok.  The hit of a chunk hangs on the state only
-//       where the whole-chunk hit is not at 0 and the short one is; there the walk goes on if what it knows decides the
-//       chunk and stops the round otherwise.
-//  (e)  lock_commit_kernel: behind the round's decoder, one wave replays steps 1-6 over the round's rows with their
-//       info.ok: the modes, the counters and the (ok, fc) that the next round or the next call begins with.  It also
-//       checks every row's hit against the one the joints chose and marks the round damaged if they differ.
+//  (b) lock_walk_kernel: V is cut into segments of S chunks; one wave per segment walks the recurrence
+//      c -> c + F | c + pos + F from the segment's nominal start and records its steps.  A step is one range query over
+//      positions c .. c + F - 65 (framer_query.h).  With the flywheel on, and where the whole-chunk hit is not at
+//      position 0, it also records the hit over the first frame / 16 symbols.  Both are functions of the cursor alone.
+//      (Where the whole-chunk hit is at position 0 the short hit equals it: the short range is a prefix of the whole, so
+//      no word reaches a greater count there than in the whole, and the winner's count is reached at position 0, the
+//      first of both.)
+//  (c) plain_joints_kernel (the synchroniser's) and lock_joints_kernel (the lock's; without the flywheel it copies the
+//      records as plain_joints_kernel does, and also writes a flag byte per row and the round's record).  The two share
+//      the record search, the tally and the epilogue.  One wave follows the true chain from the cursor.  Where its cursor is a cursor the segment's
+//      walker recorded, the rest of that record is the chain (the walk is a function of the cursor alone); elsewhere it
+//      takes real steps until it meets the record or leaves the segment.  With the flywheel on it carries what it knows
+//      of (ok, fc): ok is not known behind a valid row of this round (its RS outcome comes with the round's decoder) and
+//      fc is not known behind a chunk that is MISS or FULL according to such an ok.  The hit of a chunk hangs on the
+//      state only where the whole-chunk hit is not at 0 and the short one is; there the walk goes on if what it knows
+//      decides the chunk and stops the round otherwise.  It writes the rows, the count, the call record and the state.
+//  (e) lock_commit_kernel: behind the round's decoder, one wave replays steps 1-6 over the round's rows with their
+//      info.ok: the modes, the counters and the (ok, fc) that the next round or the next call begins with.  It also
+//      checks every row's hit against the one the joints chose and marks the round damaged if they differ.
+//
+// Without the flywheel (recheck == 1) the state changes no chunk's hit: ok = 0 and fc = 0 after a reset, fc = 1 behind
+// any chunk, so step 1 fires at the entry of every later chunk and ok is 0 whenever step 2 looks at it.  Every chunk is
+// FULL and a call is one round.  Only the sensitive_chunks counter then reads a short hit, and only that of the first
+// chunk behind a reset (the one entered with fc != recheck): the lock's host side asks for it with lp.short0.
 #include "kernels.h"
 #include "framer_query.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
 namespace {
 
-constexpr unsigned LK_NZ = 1, LK_S0 = 2, LK_USED = 4;          // LockScratch::flags
+constexpr unsigned LK_NZ = 1, LK_S0 = 2, LK_USED = 4;          // FramerScratch::flags
 constexpr unsigned LK_VALID = 8, LK_OK = 16;                   // ... and what the commit adds to them
 
-// the two hits of the chunk at c, packed as a walker's record: (c, word | short at 0 << 1 | short word << 2 |
-// short count << 8, position, count)
+// ---- what the synchroniser's chain and the lock's share ----
+
+// the search of a walker's record for the cursor x: the index of the step recorded there, or -1
+__device__ __forceinline__ int lk_find(const uint4 *__restrict__ theirs, unsigned nr, unsigned x, unsigned lane)
+{
+    int found = -1;
+    for (unsigned base = 0; base < nr && found < 0; base += 64) {
+        const unsigned idx = base + lane;
+        const unsigned long long m = __ballot(idx < nr && theirs[idx].x == x);
+        if (m) found = (int)(base + (unsigned)__ffsll((long long)m) - 1u);
+    }
+    return found;
+}
+
+// frames / dropped / resyncs of the rows a lane wrote, summed over the wave at the end
+struct LkTally {
+    unsigned frames = 0, dropped = 0, resyncs = 0;
+    __device__ __forceinline__ void row(bool good, bool moved)
+    {
+        frames += good ? 1u : 0u;
+        dropped += good ? 0u : 1u;
+        resyncs += (good && moved) ? 1u : 0u;
+    }
+};
+
+// The end of a joints kernel, by lane 0: the call record for the gather (which is given the rows from r0 on), the count
+// and the framer's state; the cursor, the carry and the call are committed unless the round stopped for an RS outcome.
+__device__ __forceinline__ void lk_finish(const FramerPar &par, FramerState *__restrict__ fr, unsigned L, unsigned long long T,
+                                          unsigned long long x, unsigned count, unsigned count0, unsigned r0, bool stopped,
+                                          const LkTally &sum, unsigned rewalked, unsigned adopted, FramerCall *__restrict__ call,
+                                          unsigned *__restrict__ d_count)
+{
+    FramerCall cr;
+    cr.base = fr->cursor;
+    cr.carry = L;
+    cr.total = (unsigned)T;
+    cr.cursor = (unsigned)x;
+    cr.count = count - r0;
+    *call = cr;
+    *d_count = count;
+    fr->rows += count - count0;
+    fr->frames += sum.frames;
+    fr->dropped += sum.dropped;
+    fr->resyncs += sum.resyncs;
+    fr->rewalked += rewalked;
+    fr->adopted += adopted;
+    if (!stopped) {
+        unsigned long long left = T - x;                         // at most 2 * frame - 66
+        if (left > 2ull * par.frame) left = 2ull * par.frame;
+        fr->symbols += par.n;
+        fr->cursor += x;
+        fr->calls += 1;
+        fr->carry = (unsigned)left;
+    }
+}
+
+__device__ __forceinline__ LkTally lk_wave_total(const LkTally &t)
+{
+    LkTally s;
+    s.frames = wave_sum(t.frames);
+    s.dropped = wave_sum(t.dropped);
+    s.resyncs = wave_sum(t.resyncs);
+    return s;
+}
+
+// ---- the synchroniser's joints: no flywheel, no loop state, no flags, rows as the steps ----
+
+// (c) one wave: the true chain through the walkers' records
+__global__ void __launch_bounds__(64) plain_joints_kernel(FramerPar par, FramerState *__restrict__ state,
+                                                          const unsigned *__restrict__ bits, const unsigned *__restrict__ bmax,
+                                                          const uint4 *__restrict__ rec, const unsigned *__restrict__ nrec,
+                                                          const uint2 *__restrict__ wout, uint4 *__restrict__ rows,
+                                                          FramerCall *__restrict__ call, unsigned *__restrict__ d_count)
+{
+    const unsigned lane = threadIdx.x;
+    const unsigned L = state->carry;
+    const unsigned long long T = (unsigned long long)L + par.n;
+    unsigned long long x = 0;
+    unsigned count = 0, rewalked = 0, adopted = 0;
+    LkTally tally;
+    while (x + par.frame <= T && count < par.cap) {
+        const unsigned k = (unsigned)(x / par.seg_bytes);
+        if (k >= par.segs) break;
+        const uint4 *theirs = rec + (size_t)k * par.seg_chunks;
+        const unsigned nr = nrec[k];
+        const int found = lk_find(theirs, nr, (unsigned)x, lane);
+        if (found >= 0) {
+            const unsigned have = nr - (unsigned)found, room = par.cap - count, m = have < room ? have : room;
+            for (unsigned base = 0; base < m; base += 64) {
+                const unsigned idx = base + lane;
+                if (idx < m) {
+                    const uint4 r = theirs[(unsigned)found + idx];
+                    rows[count + idx] = r;
+                    tally.row(r.w >= par.min_corr, r.z != 0);
+                }
+            }
+            count += m;
+            adopted += m;
+            if (m < have) { x = theirs[(unsigned)found + m].x; break; }     // (the row bound makes this unreachable)
+            const uint2 o = wout[k];
+            x = o.x;
+            if (o.y) break;
+            continue;
+        }
+        const FrHit h = fr_query(par, bits, bmax, (unsigned)x, lane);
+        const bool good = h.corr >= par.min_corr;
+        if (good && x + h.pos + par.frame > T) break;
+        if (lane == 0) {
+            rows[count] = make_uint4((unsigned)x, h.word, h.pos, h.corr);
+            tally.row(good, h.pos != 0);
+        }
+        ++count;
+        ++rewalked;                                              // counted once, when the chunk is consumed
+        x += good ? (unsigned long long)h.pos + par.frame : par.frame;
+    }
+    const LkTally sum = lk_wave_total(tally);
+    if (lane == 0) lk_finish(par, state, L, T, x, count, 0u, 0u, false, sum, rewalked, adopted, call, d_count);
+}
+
+// ---- the lock's chain ----
+
+// the hits of the chunk at c, packed as a walker's record: (c, word | short at 0 << 1 | short word << 2 |
+// short count << 8, position, count).  SHORT: where the whole-chunk hit is not at 0 the short hit is asked for too
+template <bool SHORT>
 __device__ __forceinline__ uint4 lk_record(const FramerPar &par, const LockPar &lp, const unsigned *__restrict__ bits,
                                           const unsigned *__restrict__ bmax, unsigned c, unsigned lane)
 {
     const FrHit h = fr_query(par, bits, bmax, c, lane);
     unsigned y = h.word;
-    if (h.pos != 0) {
+    if (SHORT && h.pos != 0) {
         const FrHit hs = fr_query_span(par, bits, bmax, c, lp.span, lane);
         if (hs.pos == 0) y |= 2u | (hs.word << 2) | (hs.corr << 8);
     }
     return make_uint4(c, y, h.pos, h.corr);
 }
 
-// (b') one wave per segment; the walkers step by the whole-chunk hit
+// (b) one wave per segment; the walkers step by the whole-chunk hit.  FLY: the flywheel is on (lp.recheck > 1) and every
+// step records both hits.  Without it a step is one query; the one short hit that is read then (lp.short0: that of the
+// chunk at cursor 0) is added to the first walker's first record behind the walk.
+template <bool FLY>
 __global__ void __launch_bounds__(64) lock_walk_kernel(FramerPar par, LockPar lp, const LockState *__restrict__ state,
                                                        const unsigned *__restrict__ bits, const unsigned *__restrict__ bmax,
                                                        uint4 *__restrict__ rec, unsigned *__restrict__ nrec, uint2 *__restrict__ wout)
@@ -52,7 +192,7 @@ __global__ void __launch_bounds__(64) lock_walk_kernel(FramerPar par, LockPar lp
     uint4 *mine = rec + (size_t)k * par.seg_chunks;
     while (x < seg1 && i < par.seg_chunks) {
         if (x + par.frame > T) { stop = 1; break; }
-        const uint4 r = lk_record(par, lp, bits, bmax, (unsigned)x, lane);
+        const uint4 r = lk_record<FLY>(par, lp, bits, bmax, (unsigned)x, lane);
         const bool good = r.w >= par.min_corr;
         if (good && x + r.z + par.frame > T) { stop = 1; break; }
         if (lane == 0) mine[i] = r;
@@ -62,6 +202,10 @@ __global__ void __launch_bounds__(64) lock_walk_kernel(FramerPar par, LockPar lp
     if (lane == 0) {
         nrec[k] = i;
         wout[k] = make_uint2((unsigned)x, stop);
+    }
+    if (!FLY && lp.short0 && k == 0 && i > 0) {
+        const FrHit hs = fr_query_span(par, bits, bmax, 0u, lp.span, lane);
+        if (lane == 0 && mine[0].z != 0 && hs.pos == 0) mine[0].y |= 2u | (hs.word << 2) | (hs.corr << 8);
     }
 }
 
@@ -95,16 +239,13 @@ __device__ __forceinline__ void lk_advance(LkTrack &t, unsigned R, bool nz, bool
     if (valid) t.ok = 2;
 }
 
-__device__ __forceinline__ unsigned lk_wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ unsigned lk_lane(unsigned v, unsigned i) { return (unsigned)__builtin_amdgcn_readlane((int)v, (int)i); }
 
-// (c') one wave: the true chain through the walkers' records, from where the round before stopped
+// (c) one wave: the true chain through the walkers' records, from where the round before stopped.  FLY: the flywheel is
+// on (lp.recheck > 1).  Without it nothing of the state is carried and no batch is stepped through, and a real step asks
+// for no short hit: the one chunk whose short hit is read (lp.short0) is the call's first, which is adopted from the
+// first walker's record or emits no row.
+template <bool FLY>
 __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar lp, LockState *__restrict__ state,
                                                          const unsigned *__restrict__ bits, const unsigned *__restrict__ bmax,
                                                          const uint4 *__restrict__ rec, const unsigned *__restrict__ nrec,
@@ -112,7 +253,7 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
                                                          unsigned char *__restrict__ flags, FramerCall *__restrict__ call,
                                                          unsigned *__restrict__ d_count)
 {
-    const unsigned lane = threadIdx.x, R = lp.recheck;
+    const unsigned lane = threadIdx.x, R = FLY ? lp.recheck : 1u;
     const unsigned L = state->fr.carry;
     const unsigned long long T = (unsigned long long)L + par.n;
     unsigned long long x = lp.first ? 0ull : (unsigned long long)state->round.cursor;
@@ -120,23 +261,18 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
     const unsigned count0 = count;
     LkTrack t{state->ok ? 1u : 0u, state->fc, 1u};
     unsigned rewalked = 0, adopted = 0, stopped = 0;
-    unsigned frames = 0, dropped = 0, resyncs = 0;          // per lane, summed at the end
+    LkTally tally;                                          // per lane, summed at the end
     bool leave = false;
     while (!leave && x + par.frame <= T && count < par.cap) {
         const unsigned k = (unsigned)(x / par.seg_bytes);
         if (k >= par.segs) break;
         const uint4 *theirs = rec + (size_t)k * par.seg_chunks;
         const unsigned nr = nrec[k];
-        int found = -1;
-        for (unsigned base = 0; base < nr && found < 0; base += 64) {
-            const unsigned idx = base + lane;
-            const unsigned long long m = __ballot(idx < nr && theirs[idx].x == (unsigned)x);
-            if (m) found = (int)(base + (unsigned)__ffsll((long long)m) - 1u);
-        }
+        const int found = lk_find(theirs, nr, (unsigned)x, lane);
         if (found < 0) {
             // a real step
-            const uint4 r = lk_record(par, lp, bits, bmax, (unsigned)x, lane);
-            const bool nz = r.z != 0, s0 = (r.y & 2u) != 0;
+            const uint4 r = lk_record<FLY>(par, lp, bits, bmax, (unsigned)x, lane);
+            const bool nz = r.z != 0, s0 = FLY && (r.y & 2u) != 0;
             const unsigned d = lk_decide(t, R, nz, s0);
             if (d == 2) { stopped = 1; break; }
             const unsigned word = d ? (r.y >> 2) & 1u : r.y & 1u, pos = d ? 0u : r.z, corr = d ? r.y >> 8 : r.w;
@@ -145,9 +281,7 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
             if (lane == 0) {
                 rows[count] = make_uint4((unsigned)x, word, pos, corr);
                 flags[count] = (unsigned char)((nz ? LK_NZ : 0u) | (s0 ? LK_S0 : 0u) | (d ? LK_USED : 0u));
-                frames += good ? 1u : 0u;
-                dropped += good ? 0u : 1u;
-                resyncs += (good && pos != 0) ? 1u : 0u;
+                tally.row(good, pos != 0);
             }
             lk_advance(t, R, nz, s0, good);
             ++count;
@@ -157,8 +291,24 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
         }
         // the rest of the walker's record, 64 chunks at a time
         const unsigned have = nr - (unsigned)found, room = par.cap - count, m = have < room ? have : room;
+        if (!FLY) {
+            // the state changes no hit: the rows are the records, copied by the lanes (t is not carried through them:
+            // nothing reads it behind the call's first chunk)
+            for (unsigned base = 0; base < m; base += 64) {
+                const unsigned idx = base + lane;
+                if (idx < m) {
+                    const uint4 r = theirs[(unsigned)found + idx];
+                    const bool nz = r.z != 0, good = r.w >= par.min_corr;
+                    rows[count + idx] = make_uint4(r.x, r.y & 1u, r.z, r.w);
+                    flags[count + idx] = (unsigned char)((nz ? LK_NZ : 0u) | ((r.y & 2u) ? LK_S0 : 0u));
+                    tally.row(good, nz);
+                }
+            }
+            count += m;
+            adopted += m;
+        }
         bool whole = true;                                       // the record was followed to its end
-        for (unsigned base = 0; base < m && whole; base += 64) {
+        for (unsigned base = 0; FLY && base < m && whole; base += 64) {
             const unsigned idx = base + lane, cnt = m - base < 64u ? m - base : 64u;
             const bool in = idx < m;
             const uint4 r = in ? theirs[(unsigned)found + idx] : make_uint4(0, 0, 0, 0);
@@ -168,7 +318,7 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
                 if (in) {                                        // count already holds the batches before this one
                     rows[count + lane] = make_uint4(r.x, r.y & 1u, 0u, r.w);
                     flags[count + lane] = 0;
-                    frames += 1u;
+                    tally.row(true, false);
                 }
                 if (t.fck) {
                     const unsigned last = (t.fc + cnt - 1u) % R;             // fc at the entry of the batch's last chunk, less 1
@@ -197,9 +347,7 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
                 if (lane == 0) {
                     rows[count] = make_uint4(rx, word, pos, corr);
                     flags[count] = (unsigned char)((cnz ? LK_NZ : 0u) | (s0 ? LK_S0 : 0u) | (d ? LK_USED : 0u));
-                    frames += cgood ? 1u : 0u;
-                    dropped += cgood ? 0u : 1u;
-                    resyncs += (cgood && pos != 0) ? 1u : 0u;
+                    tally.row(cgood, pos != 0);
                 }
                 lk_advance(t, R, cnz, s0, cgood);
                 ++count;
@@ -217,36 +365,15 @@ __global__ void __launch_bounds__(64) lock_joints_kernel(FramerPar par, LockPar 
         // the lock's own hit (the short one may fit where the whole-chunk one does not)
         x = wout[k].x;
     }
-    const unsigned long long f = lk_wave_sum(frames), d = lk_wave_sum(dropped), rs = lk_wave_sum(resyncs);
+    const LkTally sum = lk_wave_total(tally);
     if (lane == 0) {
-        FramerCall cr;
-        cr.base = state->fr.cursor;
-        cr.carry = L;
-        cr.total = (unsigned)T;
-        cr.cursor = (unsigned)x;
-        cr.count = count - lp.r0;                                // the gather is given the round's rows
-        *call = cr;
-        *d_count = count;
+        lk_finish(par, &state->fr, L, T, x, count, count0, lp.r0, stopped != 0, sum, rewalked, adopted, call, d_count);
         LockRound rd;
         rd.count = count;
         rd.stopped = stopped;
         rd.cursor = (unsigned)x;
         rd.reserved = 0;
         state->round = rd;
-        state->fr.rows += count - count0;
-        state->fr.frames += f;
-        state->fr.dropped += d;
-        state->fr.resyncs += rs;
-        state->fr.rewalked += rewalked;
-        state->fr.adopted += adopted;
-        if (!stopped) {
-            unsigned long long left = T - x;                     // at most 2 * frame - 66
-            if (left > 2ull * par.frame) left = 2ull * par.frame;
-            state->fr.symbols += par.n;
-            state->fr.cursor += x;
-            state->fr.calls += 1;
-            state->fr.carry = (unsigned)left;
-        }
     }
 }
 
@@ -327,34 +454,36 @@ __global__ void __launch_bounds__(64) lock_commit_kernel(FramerPar par, LockPar 
 
 }  // namespace
 
-size_t lock_scratch_carve(void *p, size_t n, unsigned frame, unsigned seg_chunks, LockScratch &sc)
+int launch_plain_joints(const FramerPar &par, FramerState *state, FramerScratch &sc, unsigned *count, hipStream_t s)
 {
-    const size_t head = framer_scratch_carve(p, n, frame, seg_chunks, sc.fr);
-    Carver c{p ? static_cast<char *>(p) + head : nullptr};
-    sc.flags = c.take<unsigned char>(framer_host::rows_cap(n, frame) + 1, 16);
-    return head + c.used();
-}
-
-int launch_lock_walk(const FramerPar &par, const LockPar &lp, const LockState *state, LockScratch &sc, hipStream_t s)
-{
-    hipLaunchKernelGGL(lock_walk_kernel, dim3(par.segs), dim3(64), 0, s, par, lp, state, sc.fr.bits, sc.fr.bmax, sc.fr.rec, sc.fr.nrec,
-                       sc.fr.wout);
+    hipLaunchKernelGGL(plain_joints_kernel, dim3(1), dim3(64), 0, s, par, state, sc.bits, sc.bmax, sc.rec, sc.nrec, sc.wout, sc.rows,
+                       sc.call, count);
     XR_HIP(hipGetLastError());
     return XRIT_OK;
 }
 
-int launch_lock_joints(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, unsigned *count, hipStream_t s)
+int launch_lock_walk(const FramerPar &par, const LockPar &lp, const LockState *state, FramerScratch &sc, hipStream_t s)
 {
-    hipLaunchKernelGGL(lock_joints_kernel, dim3(1), dim3(64), 0, s, par, lp, state, sc.fr.bits, sc.fr.bmax, sc.fr.rec, sc.fr.nrec,
-                       sc.fr.wout, sc.fr.rows, sc.flags, sc.fr.call, count);
+    const auto kernel = lp.recheck > 1 ? lock_walk_kernel<true> : lock_walk_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(par.segs), dim3(64), 0, s, par, lp, state, sc.bits, sc.bmax, sc.rec, sc.nrec,
+                       sc.wout);
     XR_HIP(hipGetLastError());
     return XRIT_OK;
 }
 
-int launch_lock_commit(const FramerPar &par, const LockPar &lp, LockState *state, LockScratch &sc, const xrit_frame_info *info,
+int launch_lock_joints(const FramerPar &par, const LockPar &lp, LockState *state, FramerScratch &sc, unsigned *count, hipStream_t s)
+{
+    const auto kernel = lp.recheck > 1 ? lock_joints_kernel<true> : lock_joints_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, s, par, lp, state, sc.bits, sc.bmax, sc.rec, sc.nrec, sc.wout, sc.rows, sc.flags,
+                       sc.call, count);
+    XR_HIP(hipGetLastError());
+    return XRIT_OK;
+}
+
+int launch_lock_commit(const FramerPar &par, const LockPar &lp, LockState *state, FramerScratch &sc, const xrit_frame_info *info,
                        unsigned char *mode, hipStream_t s)
 {
-    hipLaunchKernelGGL(lock_commit_kernel, dim3(1), dim3(64), 0, s, par, lp, state, sc.fr.rows, sc.flags, info, mode);
+    hipLaunchKernelGGL(lock_commit_kernel, dim3(1), dim3(64), 0, s, par, lp, state, sc.rows, sc.flags, info, mode);
     XR_HIP(hipGetLastError());
     return XRIT_OK;
 }

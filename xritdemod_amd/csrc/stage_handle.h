@@ -1,4 +1,5 @@
-// stage_handle.h -- what the stateful back-end handles (decoder, demux, packets, files) share on the host: the device, the
+// stage_handle.h -- what the stateful handles (framer, lock, decoder, demux, packets, files; the first three through
+// frame_cores.h) share on the host: the device, the
 // host-buffer path's own stream, the stream of the most recent call, and the "summary, written prefixes, XRIT_E_CAPACITY"
 // tail of a host-buffer call with capacities.  Host only.
 #pragma once
@@ -29,7 +30,7 @@ struct StageHandle {
         return XRIT_OK;
     }
     // every wait comes before the own stream is destroyed (last_stream may be that stream); the buffers go last
-    void close(std::initializer_list<DevBuf *> bufs)
+    void close(std::initializer_list<DevBuf *> bufs = {})
     {
         if (stream) {
             (void)hipSetDevice(device);
