@@ -1074,6 +1074,34 @@ def test_big_calls_walk_overlapping_blocks(xa, oracle_mod):
     assert [s_.costas_passes for s_ in st] == [s_.costas_passes for s_ in st2]
 
 
+# (clock_passes, clock_relay_passes, clock_relay_closed, clock_relay_segments) per call size in symbols.  Recorded from the library
+# of commit a85a4d7 -- before the call's plan moved into csrc/clock_plan.h -- on an MI355X, together with the soft symbols the
+# two libraries were compared by (profiles/clock_plan_identity.txt): LRIT at 1.25 Msps, decimation 1, the device generator at
+# Es/N0 12 dB with seed 20261019, a fresh handle per call.
+PLAN_BOUNDARIES = {
+    150000: (0, 2, 1, 1),       # one exact walk from the carried state (handles with the bit-exact front end: up to 200 k symbols)
+    199000: (10, 3, 0, 13),     # (above that limit already: the plan counts chains x chain length, 0.5 % + three chains more)
+    201000: (10, 3, 0, 13),     # hand-off passes, three relay passes over segments of 16 k symbols
+    999000: (10, 3, 0, 62),
+    1001000: (0, 1, 0, 116),    # from a million symbols: overlapping walkers, one launch
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nsym", list(PLAN_BOUNDARIES))
+def test_the_plan_changes_where_it_did(xa, nsym):
+    """The default configuration's choice of plan by call size -- one walk | hand-off passes + relay | overlapping walkers --
+    shows in the statistics; both sides of the one-walk limit and of ov_min are held to what the library gave before the
+    choice became a function of its own (ClockStage::begin -> clock_chain_plan, clock_ov_eligible)."""
+    fs = 1.25e6
+    n = int(nsym * (1.25e6 / 293883.0))
+    buf = _device_bursts(dict(fs_in=fs, esn0_db=12.0, seed=20261019), n, 1)
+    _, st = _run_plan(xa, xa.Demodulator.config("lrit", fs, 1), buf, [("go", 0)], n // 2 + 4096)
+    got = (st[0].clock_passes, st[0].clock_relay_passes, st[0].clock_relay_closed, st[0].clock_relay_segments)
+    print("plan boundaries:", nsym, got)
+    assert got == PLAN_BOUNDARIES[nsym], (nsym, got)
+
+
 def test_front_exact_warms_the_final_costas_pass_up(xa, oracle_mod):
     """cfg.front_exact = 1 (round 5, opt-in): the Costas loop's final pass starts every chain four chains early and walks those
     samples quietly, so that what the hand-offs left the chain starts beside their predecessors' ends is forgotten before a chain's

@@ -24,7 +24,9 @@
 
 namespace xrit {
 
-constexpr int CLK_OM_BLOCK = 256;     // samples per timing-estimate block
+static_assert(CLK_CTL_DONE == NEWTON_CTL_DONE && CLK_CTL_GATED == NEWTON_CTL_GATED && CLK_CTL_TAKEOVER == NEWTON_CTL_TAKEOVER,
+              "the words newton.h shares keep their numbers");
+
 constexpr float CLK_H_T = 0.0625f;    // finite-difference steps
 constexpr float CLK_H_W = 1e-3f;
 
@@ -135,7 +137,7 @@ __global__ void clock_guess_kernel(const double *__restrict__ cnt, int nb, doubl
     dirty[k] = 1;                       // every chain runs in the first pass
     written[k] = 0;                     // ... and none has left its symbols yet
     ClockState s0 = carried[0];
-    if (k == 0) { S[0] = s0; ctl[5] = 1; return; }     // first solve: gated
+    if (k == 0) { S[0] = s0; ctl[CLK_CTL_GATED] = 1; return; }     // first solve: gated
     double t0 = (double)s0.ii + (double)s0.mu;
     // the M&M read position t = ii+mu sits 3 samples before the interpolation instant
     double ca = clk_count_at(cnt, nb, sps, t0, off, BL) + 3.0 / sps;
@@ -245,30 +247,30 @@ struct ClockPolicy {
         const bool same = old.ii == nw.ii && old.mu == nw.mu && old.omega == nw.omega && hist_same;
         if (!same) { S[k + 1] = nw; dirty[k + 1] = 1; st.changed += 1; }
     }
-    // After every solve: ctl[0] done, ctl[1] passes run, ctl[2] open boundaries, ctl[3] max residual (bits),
-    // ctl[4] previous summed squared residual (bits).  The recurrence is chaotic at the 1e-5 level
+    // After every solve: DONE, PASSES run, OPEN boundaries, MAX_RESIDUAL (bits), SUM_SQ: the summed squared residual, which
+    // the next solve compares its own with (bits); the words by name: clock_ctl.h.  The recurrence is chaotic at the 1e-5 level
     // (interpolator-arm quantisation), so boundaries keep moving by that much for ever; what must close are the
     // LARGE residuals (acquisition at the head of a cold-started call, symbol slips: decision flips kick mu by up
     // to ~2e-3, acquisition and slips leave residuals >> 0.02 samples).  After that the passes go on only while
     // the summed squared residual still falls by > 45 % per pass.
     __device__ void decide(int *ctl) const
     {
-        const unsigned changed = newton_cnt_load(cnt + 0), open_ = newton_cnt_load(cnt + 1);
-        const unsigned mr = newton_cnt_load(cnt + 2), large = newton_cnt_load(cnt + 3);
-        const unsigned long long sq = (unsigned long long)newton_cnt_load(cnt + 4) |
-                                      ((unsigned long long)newton_cnt_load(cnt + 5) << 32);
-        ctl[1] += 1;
-        ctl[2] = (int)open_;
-        ctl[3] = (int)mr;
+        const unsigned changed = newton_cnt_load(cnt + CLK_CNT_CHANGED), open_ = newton_cnt_load(cnt + CLK_CNT_OPEN);
+        const unsigned mr = newton_cnt_load(cnt + CLK_CNT_MAX_R), large = newton_cnt_load(cnt + CLK_CNT_LARGE);
+        const unsigned long long sq = (unsigned long long)newton_cnt_load(cnt + CLK_CNT_SUM_SQ) |
+                                      ((unsigned long long)newton_cnt_load(cnt + CLK_CNT_SUM_SQ + 1) << 32);
+        ctl[CLK_CTL_PASSES] += 1;
+        ctl[CLK_CTL_OPEN] = (int)open_;
+        ctl[CLK_CTL_MAX_RESIDUAL] = (int)mr;
         const float q = newton_unfix(sq);
-        const float q_prev = ctl[1] == 1 ? INFINITY : __int_as_float(ctl[4]);
-        ctl[4] = __float_as_int(q);
-        ctl[5] = (large != 0 || __uint_as_float(mr) > 0.02f) ? 1 : 0;   // trust gate only while residuals are large
-        ctl[9] = (int)large;       // boundaries with a residual beyond 0.02 sample or an open slip: what a caller can act on
-        const int open_prev = ctl[1] == 1 ? 0x7fffffff : ctl[6];
-        ctl[6] = (int)open_;
-        if (changed == 0) { ctl[0] = 1; ctl[2] = 0; return; }
-        if (relay_after > 0 && ctl[1] >= relay_after && large == 0 && !(__uint_as_float(mr) > 0.02f)) { ctl[0] = 1; return; }
+        const float q_prev = ctl[CLK_CTL_PASSES] == 1 ? INFINITY : __int_as_float(ctl[CLK_CTL_SUM_SQ]);
+        ctl[CLK_CTL_SUM_SQ] = __float_as_int(q);
+        ctl[CLK_CTL_GATED] = (large != 0 || __uint_as_float(mr) > 0.02f) ? 1 : 0;   // trust gate only while residuals are large
+        ctl[CLK_CTL_LARGE] = (int)large;       // boundaries with a residual beyond 0.02 sample or an open slip: what a caller can act on
+        const int open_prev = ctl[CLK_CTL_PASSES] == 1 ? 0x7fffffff : ctl[CLK_CTL_OPEN_LAST];
+        ctl[CLK_CTL_OPEN_LAST] = (int)open_;
+        if (changed == 0) { ctl[CLK_CTL_DONE] = 1; ctl[CLK_CTL_OPEN] = 0; return; }
+        if (relay_after > 0 && ctl[CLK_CTL_PASSES] >= relay_after && large == 0 && !(__uint_as_float(mr) > 0.02f)) { ctl[CLK_CTL_DONE] = 1; return; }
         // "stalled" is the chaos floor only if the boundaries have also stopped freezing: at C2 112 653 of 113 266
         // stay open from pass to pass (they move by 1e-5 for ever), whereas a call of a few dozen chains closes
         // EXACTLY given the passes (20 -> 19 -> ... -> 0 open, then 3e-7 from the serial loop) and its summed
@@ -281,8 +283,8 @@ struct ClockPolicy {
         // which the loop is far from its fixed point and sensitive: 4e-5 sample left at the hand-offs of such a call
         // showed as 5e-3 in its symbols (fuzz: cold HRIT start, 3147 symbols, 14.7 dB).  It runs on while boundaries
         // freeze, whatever the level.
-        int memo = ctl[7];
-        if (ctl[1] >= 3 && large != 0) memo |= 0x100;
+        int memo = ctl[CLK_CTL_STALL_MEMO];
+        if (ctl[CLK_CTL_PASSES] >= 3 && large != 0) memo |= 0x100;
         const bool acquiring = (memo & 0x100) != 0;
         const bool above_floor = open_ != 0u && (acquiring || q > floor_sq * (float)open_);
         const bool freezing = above_floor && open_prev != 0x7fffffff && (long long)open_prev - (long long)open_ >= 1 &&
@@ -291,9 +293,9 @@ struct ClockPolicy {
         // carry it): one pass without a 45 % fall is not yet the floor there, two in a row are.
         const bool flat = q > 0.55f * q_prev;
         const int flat_runs = flat ? (memo & 0xff) + 1 : 0;
-        ctl[7] = (memo & 0x100) | (flat_runs > 0xff ? 0xff : flat_runs);
+        ctl[CLK_CTL_STALL_MEMO] = (memo & 0x100) | (flat_runs > 0xff ? 0xff : flat_runs);
         const bool stalled = !freezing && (open_ >= 4096u ? flat : flat_runs >= 2);
-        if (ctl[1] >= min_passes && large == 0 && stalled) ctl[0] = 1;
+        if (ctl[CLK_CTL_PASSES] >= min_passes && large == 0 && stalled) ctl[CLK_CTL_DONE] = 1;
     }
 };
 
@@ -313,23 +315,14 @@ struct ClockPolicy {
 // (a - origin) mod R), and every sample is fetched once.  A wave in which some lane
 // has left its ring (acquisition, wildly wrong start, end of input) computes that
 // sub-step from global memory.
-constexpr int CLK_M = 2;      // samples kept below the start index
-constexpr int CLK_SLACK = 3;  // head room above the schedule: R >= CLK_M + CLK_SLACK + A + 8
-// The first CLK_MIR slots of a ring are kept twice, once more behind slot R - 1: the 8-sample window of a symbol
-// then never wraps, its reads are one address and seven immediate offsets instead of eight masked indices
-// (24 of the ~95 vector instructions of a symbol went into those indices).  Row stride WS = R + CLK_MIR float2,
-// odd, so the per-lane ds_read_b64 stay spread over the banks.
+// (CLK_M samples are kept below the start index, CLK_SLACK is the head room above the schedule, the first CLK_MIR slots of a
+// ring are kept twice, row stride WS = R + CLK_ROW_EXTRA: clock_plan.h, which the host's plan shares)
 #ifndef XR_NOSTORE
 #define XR_NOSTORE 0
 #endif
 #ifndef XR_LOAD_AUX
 #define XR_LOAD_AUX 0
 #endif
-#ifndef XR_CLK_MIR
-#define XR_CLK_MIR (XR_MM_NTAPS - 1)
-#endif
-constexpr int CLK_MIR = XR_CLK_MIR;      // 0: no mirror, masked window indices (row stride R + 1)
-constexpr int CLK_ROW_EXTRA = CLK_MIR > 0 ? CLK_MIR : 1;
 
 struct ClockTile {
     float *table;          // 129 x 8, one copy per workgroup
@@ -350,11 +343,6 @@ __device__ __forceinline__ ClockTile clock_tile_carve(char *smem, int grp, int n
     t.tile = tiles + (size_t)grp * 64 * WS;
     t.dump = tiles + (size_t)ngroups * 64 * WS + threadIdx.x;
     return t;
-}
-
-static inline size_t clock_tile_bytes(int WS, int ngroups, int threads)
-{
-    return 4160 + 256 * (size_t)ngroups + ((size_t)ngroups * 64 * WS + threads) * sizeof(float2);
 }
 
 // The call's samples as a raw buffer whose base is the lowest ring origin of the workgroup: element offsets are
@@ -625,7 +613,6 @@ struct ClockPassOut {
     float4 *stage;       // soft symbols in the order the waves produce them: [wave of 64 chains][sub-step][lane] -> a wave
                          // instruction writes 1 KiB of whole lines (clock_unstage_kernel puts them where they belong)
 };
-constexpr int CLK_CTL_SYMBOLS = 13;
 
 template <int NV, int WP, int NCM, bool OUTP = false>
 __global__ void __launch_bounds__(NV > 1 ? 64 * NV : 512) clock_pass_kernel(const float2 *__restrict__ x, const float *__restrict__ table_g,
@@ -637,7 +624,7 @@ __global__ void __launch_bounds__(NV > 1 ? 64 * NV : 512) clock_pass_kernel(cons
                                                              AffMap *__restrict__ aggs, ClockPassOut po = ClockPassOut{})
 {
     // the hand-off already closed (later passes of the batch are no-ops), or the gated solve has taken over
-    if (ctl[0] || (aggs != nullptr && ctl[NEWTON_CTL_TAKEOVER])) return;
+    if (ctl[CLK_CTL_DONE] || (aggs != nullptr && ctl[CLK_CTL_TAKEOVER])) return;
     if (OUTP && blockIdx.x == 0 && threadIdx.x == 0) *po.valid = 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float2 endv[2][NV > 1 ? 64 : 1];
@@ -1018,8 +1005,6 @@ __global__ void __launch_bounds__(256) clock_jmean_kernel(const float4 *__restri
     }
 }
 
-static int relay_span(const ClockPar &par, int symbols);
-
 int ClockStage::init(float omega, float gain_omega, float mu, float gain_mu, float omega_rel_limit, int chain_syms,
                      int max_passes_)
 {
@@ -1069,15 +1054,9 @@ int ClockStage::init(float omega, float gain_omega, float mu, float gain_mu, flo
     if (const char *e = getenv("XRIT_OV_LRATIO")) { const double v = atof(e); if (v >= 0.125 && v <= 16.0) ov_lratio = v; }
 #endif
     {
-        // history a warm walker 0 needs in front of the new samples: its warm-up, the symbols it stages in front of the carried
-        // position, the two symbols of history its start state interpolates
-        const double wmax = (double)par.omega_mid + (double)par.omega_lim + 0.004;
-        ov_pad_need = (int)ceil((double)ov_hist * wmax) + XR_MM_NTAPS + XR_MM_FUDGE + 6 * (int)ceil(wmax) + 64;
-        ov_pad_need = (ov_pad_need + 15) & ~15;
-        // (only where the LDS-staged walker applies; else the pad stays what the carried tail needs)
-        const bool ring_ok = relay_span(par, 64) + 8 <= RELAY_RX - RELAY_XCH - 72;
-        xpad = 1024;
-        if (ov_enabled && ring_ok && (size_t)ov_pad_need > xpad) xpad = (size_t)ov_pad_need;
+        // history a warm walker 0 needs in front of the new samples, and the pad that holds it (clock_plan.h)
+        ov_pad_need = clock_ov_pad_need(*this);
+        xpad = clock_xpad(*this);
         XR_TRY(ov_claim.reserve(RELAY_CLAIM_WORDS * sizeof(unsigned)));
         XR_HIP(hipMemset(ov_claim.p, 0, RELAY_CLAIM_WORDS * sizeof(unsigned)));
         for (auto &j : ov)
@@ -1194,6 +1173,20 @@ double2 *ClockStage::om_slot(int nb, int BL)
     return om.as<double2>();
 }
 
+// the count curve of a statistic of nb blocks of BL samples in `buf` (the curve goes behind the statistic), with `wk` to work in
+static int clock_unwrap(DevBuf &buf, DevBuf &wk, int nb, int BL, double sps, hipStream_t s)
+{
+    const int nbB = scan_blocks(nb);
+    XR_TRY(wk.reserve((size_t)(nbB + 2) * sizeof(double)));
+    double2 *X = buf.as<double2>();
+    double *cnt = reinterpret_cast<double *>(buf.as<char>() + (size_t)nb * sizeof(double2));
+    ClkUnwrapF uf{X, cnt, nb, sps, 0.0, BL, 0.0};
+    hipLaunchKernelGGL(scan_reduce_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, wk.as<double>());
+    hipLaunchKernelGGL(scan_apply_lookback_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, wk.as<double>());
+    XR_HIP(hipGetLastError());
+    return XRIT_OK;
+}
+
 // The symbol-count curve of the producer's statistic (om_slot), unwrapped on the producer's stream behind the kernel that
 // leaves the statistic.  Counted from the first NEW sample: the curve does not depend on what the previous call carries
 // over (its integer values -- the symbol instants -- are the same whichever sample the phasor counts from, because the line
@@ -1201,32 +1194,11 @@ double2 *ClockStage::om_slot(int nb, int BL)
 // `carry` samples into the buffer.
 int ClockStage::om_scan(hipStream_t s)
 {
-    if (ov_job >= 0 && ov[ov_job].state == 1) {
-        OvJob &j = ov[ov_job];
-        if (!j.om_ext || j.nb < 1) return XRIT_OK;
-        // (an overlap job's curve is needed by its walkers' start states only: unwrapped on THEIR stream, ov_launch -- the
-        // producer's stream, which sets a burst's pace, is spared two launches)
-        if (!ov_scan_now) return XRIT_OK;
-        const int nb = j.nb, nbB = scan_blocks(nb);
-        XR_TRY(j.om_work.reserve((size_t)(nbB + 2) * sizeof(double)));
-        double2 *X = j.om.as<double2>();
-        double *cnt = reinterpret_cast<double *>(j.om.as<char>() + (size_t)nb * sizeof(double2));
-        ClkUnwrapF uf{X, cnt, nb, (double)sps, 0.0, j.BL, 0.0};
-        hipLaunchKernelGGL(scan_reduce_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, j.om_work.as<double>());
-        hipLaunchKernelGGL(scan_apply_lookback_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, j.om_work.as<double>());
-        XR_HIP(hipGetLastError());
-        j.om_scanned = true;
-        return XRIT_OK;
-    }
+    // (an overlap job's curve is needed by its walkers' start states only: unwrapped on THEIR stream, ov_launch -- the
+    // producer's stream, which sets a burst's pace, is spared two launches)
+    if (ov_job >= 0 && ov[ov_job].state == 1) return XRIT_OK;
     if (!om_ext || om_nb < 1) return XRIT_OK;
-    const int nb = om_nb, nbB = scan_blocks(nb);
-    XR_TRY(om_work.reserve((size_t)(nbB + 2) * sizeof(double)));
-    double2 *X = om.as<double2>();
-    double *cnt = reinterpret_cast<double *>(om.as<char>() + (size_t)nb * sizeof(double2));
-    ClkUnwrapF uf{X, cnt, nb, (double)sps, 0.0, om_BL, 0.0};
-    hipLaunchKernelGGL(scan_reduce_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, om_work.as<double>());
-    hipLaunchKernelGGL(scan_apply_lookback_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb, om_work.as<double>());
-    XR_HIP(hipGetLastError());
+    XR_TRY(clock_unwrap(om, om_work, om_nb, om_BL, (double)sps, s));
     om_scanned = true;
     return XRIT_OK;
 }
@@ -1264,12 +1236,10 @@ int ClockStage::input_slot(size_t n, float2 **slot, hipStream_t s)
     return XRIT_OK;
 }
 
-// control block layout in `counters`: [0..24) ctl words, [24..32) ClockResult, per-pass counter slots from 32
-constexpr int CLK_CTL_WORDS = 32;
-constexpr int CLK_RES_WORD = 24;
+// the control block at the head of `counters` (layout and word names: clock_ctl.h)
 static inline int *clock_ctl(const DevBuf &b) { return b.as<int>(); }
 static inline ClockResult *clock_res(const DevBuf &b) { return reinterpret_cast<ClockResult *>(b.as<unsigned>() + CLK_RES_WORD); }
-static inline unsigned *clock_cnt(const DevBuf &b, int pass) { return b.as<unsigned>() + CLK_CTL_WORDS + (size_t)pass * 8; }
+static inline unsigned *clock_cnt(const DevBuf &b, int pass) { return b.as<unsigned>() + CLK_CTL_WORDS + (size_t)pass * CLK_CNT_WORDS; }
 
 // dynamic LDS beyond the default limit has to be asked for, once per kernel
 template <typename KernelT> static void clock_allow_lds(KernelT kernel, size_t bytes)
@@ -1291,21 +1261,21 @@ __global__ void __launch_bounds__(256) clock_relay_finalize_kernel(const RelaySe
                                                                     float2 *__restrict__ tail_out, long long N, int *ctl, int force,
                                                                     const unsigned long long *__restrict__ moments)
 {
-    if (!ctl[0] && !force) return;      // the tiled hand-off did not close in its batch: ClockStage::finish starts over
+    if (!ctl[CLK_CTL_DONE] && !force) return;      // the tiled hand-off did not close in its batch: ClockStage::finish starts over
     __shared__ int s_term, s_buf, s_stuck;
     __shared__ long long s_ii;
     if (threadIdx.x == 0) {
         int ran = enq, closed = 0;
         for (int p = 0; p < enq; ++p)
-            if (changed[RELAY_STAT * p] == 0u) { ran = p + 1; closed = 1; break; }
-        ctl[10] = ran;
-        ctl[11] = closed;
+            if (changed[RELAY_STAT * p + RELAY_STAT_CHANGED] == 0u) { ran = p + 1; closed = 1; break; }
+        ctl[CLK_CTL_RELAY_PASSES] = ran;
+        ctl[CLK_CTL_RELAY_CLOSED] = closed;
         {
             // how far the starts still moved in the last pass: mean square (samples^2, float bits)
             const unsigned *c = changed + RELAY_STAT * (ran - 1);
-            const unsigned long long sq = (unsigned long long)c[4] | ((unsigned long long)c[5] << 32);
-            ctl[12] = __float_as_int(c[6] ? (float)((double)sq / 1099511627776.0 / (double)c[6]) : 0.0f);
-            ctl[16] = (int)(c[3] >= 0x80000000u ? 0x7f800000u : c[3]);     // ... and the largest move (a watchdog mark: infinity)
+            const unsigned long long sq = (unsigned long long)c[RELAY_STAT_MOVE_SQ] | ((unsigned long long)c[RELAY_STAT_MOVE_SQ + 1] << 32);
+            ctl[CLK_CTL_RELAY_SHIFT_SQ] = __float_as_int(c[RELAY_STAT_MOVED] ? (float)((double)sq / 1099511627776.0 / (double)c[RELAY_STAT_MOVED]) : 0.0f);
+            ctl[CLK_CTL_RELAY_MOVE_MAX] = (int)(c[RELAY_STAT_MOVE_MAX] >= 0x80000000u ? 0x7f800000u : c[RELAY_STAT_MOVE_MAX]);     // ... and the largest move (a watchdog mark: infinity)
         }
         s_buf = (ran - 1) & 1;
         s_term = 0x7fffffff;
@@ -1322,7 +1292,7 @@ __global__ void __launch_bounds__(256) clock_relay_finalize_kernel(const RelaySe
     if (threadIdx.x == 0) {
         ClockState s;
         const int k = s_stuck ? G : s_term;
-        ctl[15] = s_stuck;
+        ctl[CLK_CTL_STUCK] = s_stuck;
         if (k >= G) {
             res->ok = 0;
             res->n_symbols = 0;
@@ -1339,7 +1309,7 @@ __global__ void __launch_bounds__(256) clock_relay_finalize_kernel(const RelaySe
             const double nsym = res->ok ? (double)res->n_symbols : 0.0;
             const double a1 = nsym > 0 ? (double)moments[0] / 1048576.0 / nsym : 0.0, a2 = nsym > 0 ? (double)moments[1] / 1048576.0 / nsym : 0.0;
             const double var = a2 - a1 * a1;
-            ctl[14] = __float_as_int(nsym > 0 && var > 0 ? (float)(a1 * a1 / var) : 1e30f);
+            ctl[CLK_CTL_SNR2] = __float_as_int(nsym > 0 && var > 0 ? (float)(a1 * a1 / var) : 1e30f);
         }
         long long ii = s.ii;
         if (ii > N) ii = N;
@@ -1361,70 +1331,35 @@ __global__ void __launch_bounds__(256) clock_relay_finalize_kernel(const RelaySe
     for (long long i = threadIdx.x; i < carry; i += blockDim.x) tail_out[i] = x[ii + i];
 }
 
-// segments of the exact closure: 3 per CU (what its LDS holds of the staged walk) unless a window is given; the relay
-// buffer holds three segment records per segment and four counters per pass
-// samples a block of `symbols` symbols can cover at the fastest admissible clock
-static int relay_span(const ClockPar &par, int symbols)
+// segments of the exact closure (clock_relay_segments, clock_plan.h): 3 per CU (what its LDS holds of the staged walk) unless a
+// window is given.
+// the walker: a team of 8, 4 or 2 waves (clock_relay_wide.h) where a block of 62 symbols per wave fits the team's sample
+// ring, else one wave (64 symbols per step; any symbol rate: clock_relay.h)
+int ClockStage::relay_w_plan() const
 {
-    return (int)ceil((double)symbols * ((double)par.omega_mid + (double)par.omega_lim + 0.004)) + 24;
-}
-
-int ClockStage::relay_plan()
-{
-    Job &j = job;
-    // the walker: a team of 8, 4 or 2 waves (clock_relay_wide.h) where a block of 62 symbols per wave fits the team's sample
-    // ring, else one wave (64 symbols per step; any symbol rate: clock_relay.h)
-    j.relay_w = 0;
 #ifdef XRIT_EXPERIMENTS
     if (!relay_global && relay_waves >= 2) {
-        if (relay_waves >= 4 && relay_span(par, RW_OWN * 4) + 8 <= RelayWide<4>::MAX_SPAN) j.relay_w = 4;
-        else if (relay_span(par, RW_OWN * 2) + 8 <= RelayWide<2>::MAX_SPAN) j.relay_w = 2;
+        if (relay_waves >= 4 && relay_span(par, RW_OWN * 4) + 8 <= RelayWide<4>::MAX_SPAN) return 4;
+        if (relay_span(par, RW_OWN * 2) + 8 <= RelayWide<2>::MAX_SPAN) return 2;
     }
 #endif
-    // (without hand-off passes: two walkers per CU -- 24.8 k symbols per segment at C2, three passes; measured in the streamed
-    // bench against one per CU with two passes and three per CU with four: 2.12 / 2.35 / 2.27 ms per burst)
-    // ... and where the call is long enough for MORE walkers whose segments still hold auto_long_seg symbols -- the two-pass plan:
-    // bursts at the circuit rate, 63 M (LRIT) / 100 M (HRIT) symbols per 2^28 samples -- up to four per CU, one per SIMD: the
-    // passes' latency is a segment's length, and a two-pass plan over 62 k / 97 k-symbol segments has the same exact history
-    // as over 123 k / 195 k (C3: 6.5 instead of 9.6 ms per burst, C1: 5.7 instead of 6.2, profiles/r4_relay_shortcuts.txt))
-    int auto_per_cu = 2;
-    if (j.no_handoff && exact == 0)
-        for (int p = 4; p > 2; --p)
-            if ((long long)j.K * NS / ((long long)p * cu_count) >= auto_long_seg) { auto_per_cu = p; break; }
-    const int per_cu = j.relay_w > 0 ? relay_teams_per_cu : (j.no_handoff && !relay_per_cu_set ? auto_per_cu : relay_per_cu);
-    int cps = relay_window > 0 ? relay_window : (j.K + per_cu * cu_count - 1) / (per_cu * cu_count);
-    // (a call much shorter than the ~1e5 symbols two trajectories need to meet is walked front to back whatever the
-    // cut: segments of at least 2048 symbols then cost the fewest passes -- a pass is a launch)
-    // With a budget of relay passes (cfg.clock_exact = n > 1) what the passes buy is their horizon, n x the segment length
-    // -- a segment is exact once everything within the merge length in front of it is: segments no shorter than the big
-    // bursts' (16 k symbols), whatever the size of the call, so that n means the same parity everywhere.
-    // (without hand-off passes -- the default configuration -- a segment must be long enough for the loop to forget the timing
-    // guess it starts from: never shorter than auto_long_seg / 2, 24.6 k symbols, which three passes go with.  A call of up
-    // to three such segments is ONE segment instead -- one exact walk from the carried state takes no longer than three
-    // passes over a third of it, and it IS the serial trajectory.)
-    int min_syms = j.relay_budget > 0 ? 16384 : 2048;
-    if (j.no_handoff && exact == 0 && !relay_per_cu_set) {
-        const long long all = (long long)j.K * NS;
-        min_syms = all <= one_walk_limit() ? (int)all : auto_long_seg / 2;
-    }
-    if (relay_window <= 0 && cps * NS < min_syms) cps = (min_syms + NS - 1) / NS;
-    if (cps < 1) cps = 1;
-    j.cps = cps;
-    j.G = (j.K + cps - 1) / cps;
-    // (counters for G + 1 passes whatever the budget: the default configuration raises its own, ClockStage::finish)
-    XR_TRY(relay.reserve((size_t)j.G * 3 * sizeof(RelaySeg) + ((size_t)j.G + 1 + 8) * RELAY_STAT * sizeof(unsigned) + 2 * sizeof(unsigned long long) +
-                         RELAY_CLAIM_WORDS * sizeof(unsigned)));
-    if (!relay_no_rec) XR_TRY(relay_rec.reserve(((size_t)j.G * cps * NS + RW_REC_PAD) * sizeof(unsigned)));
-    relay_segments = j.G;
-    relay_seg_chains = cps;
-    return XRIT_OK;
+    return 0;
 }
 
-int ClockStage::relay_limit() const
+// the segments of job.segs become the call's: the relay buffer holds three segment records per segment and four counters
+// per pass
+int ClockStage::relay_cut()
 {
-    // a pass moves the exact front by at least one segment: G + 1 passes always close
-    const int hard = job.G + 1;
-    return job.relay_budget > 0 ? (job.relay_budget < hard ? job.relay_budget : hard) : hard;
+    Job &j = job;
+    j.cps = j.segs.cps;
+    j.G = j.segs.G;
+    // (counters for G + 1 passes whatever the budget: the default configuration raises its own, ClockStage::finish_relay)
+    XR_TRY(relay.reserve((size_t)j.G * 3 * sizeof(RelaySeg) + ((size_t)j.G + 1 + 8) * RELAY_STAT * sizeof(unsigned) + 2 * sizeof(unsigned long long) +
+                         RELAY_CLAIM_WORDS * sizeof(unsigned)));
+    if (!relay_no_rec) XR_TRY(relay_rec.reserve(((size_t)j.G * j.cps * NS + RW_REC_PAD) * sizeof(unsigned)));
+    relay_segments = j.G;
+    relay_seg_chains = j.cps;
+    return XRIT_OK;
 }
 
 // `restart`: first batch of a call (or the tiled evaluation was redone): nothing has been walked.  Every batch ends
@@ -1432,7 +1367,7 @@ int ClockStage::relay_limit() const
 int ClockStage::enqueue_relay(int count, bool restart, hipStream_t s, Profiler *prof)
 {
     Job &j = job;
-    const int limit = relay_limit();
+    const int limit = clock_relay_limit(j.G, j.relay_budget);
     RelaySeg *segs = relay.as<RelaySeg>();
     unsigned *changed = reinterpret_cast<unsigned *>(segs + 3 * (size_t)j.G);
     RelayArgs a{};
@@ -1441,14 +1376,8 @@ int ClockStage::enqueue_relay(int count, bool restart, hipStream_t s, Profiler *
     a.K = j.K; a.cps = j.cps; a.NS = NS; a.G = j.G;
     a.start = segs; a.ends[0] = segs + j.G; a.ends[1] = segs + 2 * (size_t)j.G;
     // steps of the float32 lattice omega and mu + omega live on, in units of 2^-24 sample (the walkers' integer model)
-    {
-        const float om = par.omega_mid, su = par.omega_mid + 0.5f;
-        const double u = 1.0 / 16777216.0;
-        a.q_om = (int)((double)(nextafterf(om, INFINITY) - om) / u);
-        a.q_mu = (int)((double)(nextafterf(su, INFINITY) - su) / u);
-        if (a.q_om < 1) a.q_om = 1;
-        if (a.q_mu < 1) a.q_mu = 1;
-    }
+    const ClockLattice lat = clock_lattice(par.omega_mid);
+    a.q_om = lat.q_om; a.q_mu = lat.q_mu;
     a.soft = j.soft; a.sym = j.sym; a.cap = (unsigned long long)j.cap; a.par = par;
     a.changed = changed; a.ctl = j.relay_force ? nullptr : clock_ctl(counters);
     a.rec = relay_no_rec ? nullptr : relay_rec.as<unsigned>();
@@ -1463,7 +1392,7 @@ int ClockStage::enqueue_relay(int count, bool restart, hipStream_t s, Profiler *
     }
     // samples a block of 64 symbols can cover; the LDS-staged walk takes what fits its refill chunk
     const int span = relay_span(par, 64);
-    const bool lds_walk = span + 8 <= RELAY_RX - RELAY_XCH - 72 && !relay_global;
+    const bool lds_walk = relay_ring_ok(par) && !relay_global;
     {
         ProfScope ps(prof, "clock_relay", s);
         for (int q = 0; q < count && j.relay_enq < limit; ++q, ++j.relay_enq) {
@@ -1619,84 +1548,7 @@ int ClockStage::enqueue_output(hipStream_t s, Profiler *prof, bool again)
     return XRIT_OK;
 }
 
-// Everything of one call is put on the stream without waiting: the carried tail, the timing guess, a batch of
-// ---- overlapping exactly walked blocks: host side (clock_overlap.h) -------------------------------------------------
-bool ClockStage::ov_eligible(size_t n) const
-{
-    if (!ov_enabled || !ov_allow || exact != 0 || relay_quick || serial || relay_global || xbase_fixed) return false;
-    if (relay_no_handoff == 0 || auto_passes <= 0) return false;          // (A/B switches that ask for round 3's / round 2's plans)
-    if (relay_window > 0) return false;                                    // (cfg.clock_exact_window: the caller asks for the relay's segments)
-    if ((size_t)ov_pad_need > xpad) return false;                          // (no LDS-staged walker at this symbol rate)
-    if (n >= ((size_t)1 << 31) - xpad - 4096) return false;
-    return (double)n / (double)par.omega_mid >= (double)ov_min;
-}
-
-// the job's ranges.  `ahead`: the call in front has not finished -- its carry is not known; such a job needs the history.
-int ClockStage::ov_plan(OvJob &j, bool ahead)
-{
-    const double wmax = (double)par.omega_mid + (double)par.omega_lim + 0.004, wmin = (double)par.omega_mid - (double)par.omega_lim;
-    const int cw = (int)ceil(wmax);
-    j.hist = (int)ceil((double)ov_hist * (double)par.omega_mid);
-    j.early = (int)ceil(1.5 * wmax) + 2;
-    // history: the samples the call in front left at the end of its buffer, and the timing curve that covers them
-    const bool have_hist = hist_xb >= 0 && hist_len >= (size_t)ov_pad_need && hist_job >= 0 && ov[hist_job].om_scanned;      // (scanned: the job in front has been launched)
-    if (ahead && !have_hist) { set_error("clock recovery: an overlap job cannot start ahead without the history of the call in front"); return XRIT_E_INVALID; }
-    j.ahead = ahead;
-    if (have_hist) {
-        j.padN = ov_pad_need;
-        j.w0_carried = false;
-        j.w0_ii = ahead ? 0 : j.padN - (int)carry;          // (ahead: the scan kernel is told at the call, ov_finalize)
-        // the carried state reads its next symbol 19 .. 24 + a period samples in front of the new ones (the walk in front stops at
-        // the first read index within 8 + 16 samples of its end): staging starts a period in front of that
-        j.store0 = j.padN - (XR_MM_NTAPS + XR_MM_FUDGE) - cw - 2;
-    } else {
-        if (carry > 1024) { set_error("clock recovery: carry of %zu samples exceeds the hand-over buffer", carry); return XRIT_E_INVALID; }
-        j.padN = (int)carry;
-        j.w0_carried = true;
-        j.w0_ii = 0;
-        j.store0 = 0;
-    }
-    j.N = (long long)j.padN + (long long)j.n;
-    j.ni = j.N - XR_MM_NTAPS - XR_MM_FUDGE;
-    // walkers: ranges about as long as the history in front of them (every symbol is walked twice), at least 240 of them where
-    // the call is long enough for ranges of 8192 symbols (few walkers: their latency is the call's), at most four per CU
-    const double nsym = (double)j.n / (double)par.omega_mid;
-    double gt = nsym / ((double)ov_hist * ov_lratio);
-    if (gt < (double)ov_min_walkers) gt = (double)ov_min_walkers;
-    if (nsym / gt < (double)ov_min_range) gt = nsym / (double)ov_min_range;
-    // (at most 2.5 per CU: bursts at the circuit rate -- 63 M / 100 M symbols -- would take four per CU by the rule above; with 640
-    // walkers of 98 k / 156 k symbols every symbol is walked 1.5 / 1.3 times instead of 1.8 / 1.5: C1 4.8 instead of 5.1 ms per
-    // burst, C3 5.4 instead of 5.55 -- their latency is hidden like any other's)
-    if (gt > 2.5 * cu_count) gt = 2.5 * cu_count;
-    if (gt < 1.0) gt = 1.0;
-    long long Ls = (long long)ceil((double)j.n / gt);
-    Ls = (Ls + 63) & ~63LL;
-    if (Ls < 4096) Ls = 4096;
-    j.Ls = (int)Ls;
-    // range 0 ends where walker 1 has its whole history behind it
-    const long long w0_start = j.w0_carried ? 0 : (long long)j.store0 - j.hist;
-    long long fb = w0_start + j.hist + Ls;
-    if (fb < (long long)j.padN + Ls) fb = (long long)j.padN + Ls;
-    j.first_bound = (int)fb;
-    // (the last range is not shorter than a quarter of the others)
-    const long long lim = j.N - Ls / 4;
-    j.G = fb <= lim ? 2 + (int)((lim - fb) / Ls) : 1;
-    const long long last_start = j.G >= 2 ? fb + (long long)(j.G - 2) * Ls : (long long)j.store0;
-    long long longest = fb - j.store0;
-    if (j.G >= 2 && Ls + j.early > longest) longest = Ls + j.early;
-    if (j.N - last_start + j.early > longest) longest = j.N - last_start + j.early;
-    if (j.G == 1) longest = j.N - j.store0;
-    long long stride = (long long)ceil((double)longest / wmin) + 64;
-    stride = (stride + 63) & ~63LL;
-    if (stride * j.G >= (1LL << 31)) { set_error("clock recovery: call too long for the overlap plan"); return XRIT_E_INVALID; }
-    j.stride = (int)stride;
-    XR_TRY(j.segs.reserve((size_t)j.G * sizeof(OverlapSeg)));
-    XR_TRY(j.S.reserve((size_t)j.G * sizeof(ClockState)));
-    XR_TRY(j.stage.reserve((size_t)j.G * (size_t)j.stride * sizeof(float) + 256));
-    // aux: [0, 8) counters, [8, 12) moments (two 64-bit words), then j0[G] and offs[G] (64-bit, 8-byte aligned)
-    XR_TRY(j.aux.reserve(64 + (size_t)j.G * sizeof(int) + 8 + (size_t)j.G * sizeof(unsigned long long)));
-    return XRIT_OK;
-}
+// ---- overlapping exactly walked blocks: host side (clock_overlap.h) -------------------------------------------------  (the job's ranges: clock_ov_plan, clock_plan.h)
 
 bool ClockStage::ov_can_launch_ahead(int job) const
 {
@@ -1726,14 +1578,19 @@ int ClockStage::ov_launch(int job, hipStream_t sw, bool ahead, Profiler *prof)
         if (front < 0) { set_error("clock recovery: no job in front of a job launched ahead"); return XRIT_E_INVALID; }
         h_xb = front; h_job = front; h_len = (size_t)ov[front].padN + ov[front].n;
         XR_HIP(hipStreamWaitEvent(sw, ov[front].ev_guess, 0));      // (the curve of the job in front is unwrapped on ITS walkers' stream)
-        // (the plan looks at hist_*: described for the duration of the plan)
-        const int k_xb = hist_xb, k_job = hist_job; const size_t k_len = hist_len;
-        hist_xb = h_xb; hist_job = h_job; hist_len = h_len;
-        const int rc = ov_plan(j, true);
-        hist_xb = k_xb; hist_job = k_job; hist_len = k_len;
-        XR_TRY(rc);
-    } else {
-        XR_TRY(ov_plan(j, false));
+    }
+    // history: the samples the call in front left at the end of its buffer, and the timing curve that covers them
+    const bool have_hist = h_xb >= 0 && h_len >= (size_t)ov_pad_need && h_job >= 0 && ov[h_job].om_scanned;      // (scanned: the job in front has been launched)
+    {
+        const ClockOvPlan plan = clock_ov_plan(*this, j.n, carry, have_hist, ahead);
+        if (plan.err[0]) { set_error("%s", plan.err); return XRIT_E_INVALID; }
+        static_cast<ClockOvPlan &>(j) = plan;
+        j.ahead = ahead;
+        XR_TRY(j.segs.reserve((size_t)j.G * sizeof(OverlapSeg)));
+        XR_TRY(j.S.reserve((size_t)j.G * sizeof(ClockState)));
+        XR_TRY(j.stage.reserve((size_t)j.G * (size_t)j.stride * sizeof(float) + 256));
+        // aux: [0, 8) counters, [8, 12) moments (two 64-bit words), then j0[G] and offs[G] (64-bit, 8-byte aligned)
+        XR_TRY(j.aux.reserve(64 + (size_t)j.G * sizeof(int) + 8 + (size_t)j.G * sizeof(unsigned long long)));
     }
     float2 *data = xbuf[job].as<float2>() + xpad;
     float2 *base = data - j.padN;
@@ -1757,15 +1614,10 @@ int ClockStage::ov_launch(int job, hipStream_t sw, bool ahead, Profiler *prof)
                            1.0 / (double)sps);
         j.om_ext = true;
     }
-    if (!j.om_scanned) {
-        const int k_job = ov_job;
-        const int k_state = j.state;
-        ov_job = job; j.state = 1;
-        ov_scan_now = true;
-        const int rc = om_scan(sw);
-        ov_scan_now = false;
-        ov_job = k_job; j.state = k_state;
-        XR_TRY(rc);
+    if (!j.om_scanned && j.nb >= 1) {
+        // (an overlap job's curve is unwrapped here, on its walkers' stream: om_scan)
+        XR_TRY(clock_unwrap(j.om, j.om_work, j.nb, j.BL, (double)sps, sw));
+        j.om_scanned = true;
     }
     const double *cnt = reinterpret_cast<const double *>(j.om.as<char>() + (size_t)j.nb * sizeof(double2));
     const double *cnt_prev = nullptr;
@@ -1780,14 +1632,8 @@ int ClockStage::ov_launch(int job, hipStream_t sw, bool ahead, Profiler *prof)
     a.x = base; a.table = table.as<float>(); a.N = j.N; a.ni = j.ni;
     a.start = j.S.as<ClockState>(); a.G = j.G; a.store0 = j.store0; a.first_bound = j.first_bound; a.Ls = j.Ls; a.early = j.early;
     a.stride = j.stride; a.stage = j.stage.as<float>(); a.segs = j.segs.as<OverlapSeg>(); a.par = par;
-    {
-        const float om = par.omega_mid, su = par.omega_mid + 0.5f;
-        const double u = 1.0 / 16777216.0;
-        a.q_om = (int)((double)(nextafterf(om, INFINITY) - om) / u);
-        a.q_mu = (int)((double)(nextafterf(su, INFINITY) - su) / u);
-        if (a.q_om < 1) a.q_om = 1;
-        if (a.q_mu < 1) a.q_mu = 1;
-    }
+    const ClockLattice lat = clock_lattice(par.omega_mid);
+    a.q_om = lat.q_om; a.q_mu = lat.q_mu;
     a.stat = ov_stat(j); a.moments = ov_moments(j); a.simd_claim = relay_no_claim ? nullptr : ov_claim.as<unsigned>();
     const int span = relay_span(par, 64);
     j.hist_src = j.w0_carried ? -1 : j.hist_src;
@@ -1828,15 +1674,10 @@ int ClockStage::ov_fallback(size_t *n_out, hipStream_t s, Profiler *prof, bool t
     OvJob &j = ov[job];
     ov_cur = -1;
     j.state = 0;
-    const int k_exact = exact;
-    // (no signal -- the walkers of a loop that is not locked do not meet at the joints --: the relay's own default, which does not
-    // pursue a closure on such an input either; ClockStage::finish)
-    exact = to_closure ? 1 : 0;
     xb = job;
-    xbase_fixed = xbuf[job].as<float2>() + xpad - carry;        // (the call's samples lie where they were produced; the tail goes in front)
-    const int rc = run(j.n, ov_soft, nullptr, ov_cap, n_out, s, prof);
-    xbase_fixed = nullptr;
-    exact = k_exact;
+    // the call's samples lie where they were produced; the tail goes in front.  (No signal -- the walkers of a loop that is not
+    // locked do not meet at the joints --: the relay's own default, which does not pursue a closure on such an input either)
+    const int rc = run_chains(xbuf[job].as<float2>() + xpad - carry, to_closure ? 1 : 0, j.n, ov_soft, nullptr, ov_cap, n_out, s, prof);
     if (rc == XRIT_OK) { hist_xb = job; hist_len = (size_t)j.padN + j.n; hist_job = job; }
     ov_fell_back = true;
     return rc;
@@ -1865,9 +1706,10 @@ int ClockStage::ov_finalize(int job, float *soft_out, size_t cap, hipStream_t s,
     return XRIT_OK;
 }
 
-// hand-off passes (no-ops once the device-side test has declared the hand-off closed), the output pass and the
-// copy of the control block.  finish() runs after the caller has synchronised the stream.
-int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hipStream_t s, Profiler *prof)
+// Everything of one call is put on the stream without waiting -- the carried tail, the timing guess, a batch of hand-off
+// passes (no-ops once the device-side test has declared the hand-off closed), the output pass or the relay, and the copy of
+// the control block -- by the plan clock_plan.h makes of it.  finish() runs after the caller has synchronised the stream.
+void ClockStage::call_reset(size_t n)
 {
     passes = 0;
     unconverged = 0;
@@ -1877,129 +1719,102 @@ int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hi
     prev_n = n;
     redo_ok = false;
     ov_fell_back = false;
-    // this call's overlap job, if its samples were produced into one (input_slot): the oldest job that waits for its call
     ov_cur = -1;
-    if (!xbase_fixed) {
-        unsigned long long first = ~0ull;
-        for (int q = 0; q < NXB; ++q)
-            if ((ov[q].state == 1 || ov[q].state == 2) && ov[q].serial < first) { first = ov[q].serial; ov_cur = q; }
-        if (ov_cur >= 0 && (ov[ov_cur].n != n || sym_out != nullptr)) {
-            set_error("clock recovery: the call does not match the overlap job its samples were produced for");
-            return XRIT_E_INVALID;
-        }
+}
+
+int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hipStream_t s, Profiler *prof)
+{
+    call_reset(n);
+    // this call's overlap job, if its samples were produced into one (input_slot): the oldest job that waits for its call
+    unsigned long long first = ~0ull;
+    for (int q = 0; q < NXB; ++q)
+        if ((ov[q].state == 1 || ov[q].state == 2) && ov[q].serial < first) { first = ov[q].serial; ov_cur = q; }
+    if (ov_cur >= 0 && (ov[ov_cur].n != n || sym_out != nullptr)) {
+        set_error("clock recovery: the call does not match the overlap job its samples were produced for");
+        return XRIT_E_INVALID;
     }
-    if (ov_cur >= 0) {
-        job = Job{};
-        job.n = n; job.soft = soft_out; job.cap = cap;
-        xb = ov_cur;
-        x_pending = -1;
-        ov_job = -1;
-        in_flight = true;
-        om_ext = false; om_scanned = false;
-        ov_soft = soft_out; ov_cap = cap;
-        carry_before_fallback = carry;
-        if (ov[ov_cur].state == 1) XR_TRY(ov_launch(ov_cur, s, false, prof));
-        return ov_finalize(ov_cur, soft_out, cap, s, prof);
-    }
+    if (ov_cur >= 0) return begin_overlap(n, soft_out, cap, s, prof);
+    return begin_chains(nullptr, exact, n, soft_out, sym_out, cap, s, prof);
+}
+
+int ClockStage::begin_overlap(size_t n, float *soft_out, size_t cap, hipStream_t s, Profiler *prof)
+{
+    job = Job{};
+    job.n = n; job.soft = soft_out; job.cap = cap; job.exact = exact;
+    xb = ov_cur;
+    x_pending = -1;
+    ov_job = -1;
+    in_flight = true;
+    om_ext = false; om_scanned = false;
+    ov_soft = soft_out; ov_cap = cap;
+    if (ov[ov_cur].state == 1) XR_TRY(ov_launch(ov_cur, s, false, prof));
+    return ov_finalize(ov_cur, soft_out, cap, s, prof);
+}
+
+// the chains of a call whose [carry | new] samples lie at `base` (null: in the call's own buffer), with `exact_` for
+// cfg.clock_exact: guess, hand-off passes or not, relay or output pass
+int ClockStage::begin_chains(float2 *base, int exact_, size_t n, float *soft_out, float2 *sym_out, size_t cap, hipStream_t s, Profiler *prof)
+{
+    ClockKnobs k = *this;
+    k.exact = exact_;
+    const int relay_w = relay_w_plan();
     job = Job{};
     Job &j = job;
-    j.n = n; j.soft = soft_out; j.sym = sym_out; j.cap = cap;
-    j.N = (long long)(carry + n);
-    j.ni = j.N - XR_MM_NTAPS - XR_MM_FUDGE;
-    if (j.N >= (1LL << 31)) { set_error("clock recovery: more than 2^31 samples in one call"); return XRIT_E_INVALID; }
-    if (!xbase_fixed) {
+    static_cast<ClockChainPlan &>(j) = clock_chain_plan(k, n, carry, last_passes, relay_w);
+    j.n = n; j.soft = soft_out; j.sym = sym_out; j.cap = cap; j.base = base; j.exact = exact_; j.relay_w = relay_w;
+    if (j.N >= (1LL << 31)) { set_error("%s", j.err); return XRIT_E_INVALID; }
+    if (!base) {
         if (x_pending >= 0) xb = x_pending;
         x_pending = -1;
         XR_TRY(xbuf[xb].reserve((size_t)(xpad + n + 64 + 16) * sizeof(float2)));
     }
     in_flight = true;
-    float2 *x = xbase();
     if (carry)
-        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, s, tail.as<float2>() + 1024 * cur, x, (int)carry);
+        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, s, tail.as<float2>() + 1024 * cur, xbase(), (int)carry);
     const bool ext = om_ext;          // statistic supplied by the producer of the samples (Costas final pass)
     const bool scanned = ext && om_scanned;       // ... and its count curve too (om_scan)
     om_ext = false;
     om_scanned = false;
-    if (j.ni <= 0) {
-        // not enough samples for a single symbol: everything is carried to the next call
-        j.short_input = true;
-        if (j.N > 1024) { set_error("clock recovery: unread tail exceeds the hand-over buffer"); return XRIT_E_INVALID; }
-        if (j.N > 0)
-            XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * (cur ^ 1), x, (size_t)j.N * sizeof(float2),
-                                  hipMemcpyDeviceToDevice, s));
-        XR_HIP(hipMemcpyAsync(st.as<ClockState>() + (cur ^ 1), st.as<ClockState>() + cur, sizeof(ClockState),
+    if (j.err[0]) { set_error("%s", j.err); return XRIT_E_INVALID; }
+    if (j.short_input) return begin_short(s);
+    if (serial) return begin_serial(s, prof);
+    NS = j.NS;
+    return launch_chains(ext, scanned, s, prof);
+}
+
+// not enough samples for a single symbol: everything is carried to the next call
+int ClockStage::begin_short(hipStream_t s)
+{
+    const Job &j = job;
+    if (j.N > 0)
+        XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * (cur ^ 1), xbase(), (size_t)j.N * sizeof(float2),
                               hipMemcpyDeviceToDevice, s));
-        return XRIT_OK;
+    XR_HIP(hipMemcpyAsync(st.as<ClockState>() + (cur ^ 1), st.as<ClockState>() + cur, sizeof(ClockState),
+                          hipMemcpyDeviceToDevice, s));
+    return XRIT_OK;
+}
+
+int ClockStage::begin_serial(hipStream_t s, Profiler *prof)
+{
+    const Job &j = job;
+    hipLaunchKernelGGL(clock_reset_kernel, dim3(1), dim3(256), 0, s, counters.as<unsigned>(), CLK_CTL_WORDS, (int *)nullptr);
+    {
+        ProfScope ps(prof, "clock_serial", s);
+        hipLaunchKernelGGL(clock_serial_kernel, dim3(1), dim3(64), 0, s, xbase(), table.as<float>(),
+                           st.as<ClockState>() + cur, st.as<ClockState>() + (cur ^ 1), clock_res(counters), j.soft,
+                           j.sym, (unsigned long long)j.cap, j.N, j.ni, par, tail.as<float2>() + 1024 * (cur ^ 1));
     }
-    if (serial) {
-        j.K = 1;
-        hipLaunchKernelGGL(clock_reset_kernel, dim3(1), dim3(256), 0, s, counters.as<unsigned>(), CLK_CTL_WORDS, (int *)nullptr);
-        {
-            ProfScope ps(prof, "clock_serial", s);
-            hipLaunchKernelGGL(clock_serial_kernel, dim3(1), dim3(64), 0, s, x, table.as<float>(),
-                               st.as<ClockState>() + cur, st.as<ClockState>() + (cur ^ 1), clock_res(counters), soft_out,
-                               sym_out, (unsigned long long)cap, j.N, j.ni, par, tail.as<float2>() + 1024 * (cur ^ 1));
-        }
-        XR_HIP(hipGetLastError());
-        XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        return XRIT_OK;
-    }
-    // chain budget: the slowest admissible symbol clock plus slack
-    const double min_omega = (double)par.omega_mid - (double)par.omega_lim;
-    // sample rings (see ClockTile).  Over SS symbols the read index advances by A at most; a ring of R samples
-    // must hold CLK_M below the schedule, CLK_SLACK above it, the advance and the 8 interpolator taps.  SS
-    // divides the output tile (16 symbols).
-    const double max_adv = (double)par.omega_mid + (double)par.omega_lim + 0.004;
-    static const int tries[6][2] = {{32, 4}, {32, 2}, {32, 1}, {64, 4}, {64, 2}, {64, 1}};
-    int SS = 1, A = 0, R = 64;
-    for (int q = 0; q < 6; ++q) {
-        R = tries[q][0];
-        SS = tries[q][1];
-        A = (int)ceil(SS * max_adv) + 1;
-        if (CLK_M + CLK_SLACK + A + XR_MM_NTAPS <= R) break;    // else: very large sps, sub-steps run from global memory
-    }
-    j.wide = R > 32;
-    j.SS = SS; j.W = R; j.A = A;
-    j.STEP = (int)floor((double)SS * (double)par.omega_mid * 65536.0);
-    j.WS = R + CLK_ROW_EXTRA;
-    j.tile_bytes3 = clock_tile_bytes(j.WS, 1, 192);
-    // one-wave groups share the table: as many groups per workgroup as gives the CU the most waves (the rings
-    // fill LDS; two waves per SIMD is what the registers allow)
-    int waves_cu = 0;
-    j.NG = 1;
-    for (int ng = 1; ng <= 8 && ng <= ng_max; ++ng) {
-        const long long need = (long long)clock_tile_bytes(j.WS, ng, 64 * ng);
-        if (need > lds_per_cu) break;
-        long long wv = (long long)ng * (lds_per_cu / need);
-        if (wv > 8) wv = 8;
-        if (wv >= waves_cu) { waves_cu = (int)wv; j.NG = ng; }
-    }
-    if (waves_cu < 1) { set_error("clock recovery: a ring of %d samples per chain does not fit LDS", R); return XRIT_E_INVALID; }
-    j.tile_bytes = clock_tile_bytes(j.WS, j.NG, 64 * j.NG);
-    if (auto_ns) {
-        // One wave = 64 chains, and a wave's time is its chain length times a serial per-symbol latency: a pass
-        // costs (generations of resident waves) x NS.  So the chain length is chosen from what the chip holds --
-        // LDS decides: CUs x floor(LDS / ring tile) waves -- such that the call's waves fill a whole number g of
-        // generations: NS = symbols / (g x resident chains), with the smallest g that keeps NS <= 256 (longer
-        // chains lose more in the passes than their fewer hand-offs gain).  C2: 1792 resident waves, g = 1,
-        // NS = 112 (the former 64 gave 1.66 generations = 2 x 64 symbol times per pass, and 190 k hand-offs
-        // instead of 113 k).
-        const long long resident = (long long)cu_count * waves_cu;   // waves
-        const double symbols = (double)j.N / min_omega;
-        // (calls that do not fill the chip keep 64: 16-symbol chains would make their passes four times shorter,
-        // but the fuzz runs found symbol slips and count mismatches with them at low Es/N0; 32-symbol chains are
-        // clean and 15-25 % quicker per small call, but at Es/N0 < 3.6 dB 4 % of the cases had a hard decision
-        // flipped instead of 2.5 %)
-        NS = 64;
-        for (int g = 1; g <= 64; ++g) {
-            const double chains = (double)(g * resident * 64 - 4);          // K = symbols / NS + 3 must fit
-            int ns = (int)ceil(symbols / chains);
-            ns = (ns + 15) & ~15;                                            // whole output tiles, 64-byte rows
-            if (ns <= 256) { NS = ns < 64 ? 64 : ns; break; }
-        }
-    }
-    const int K = (int)((double)j.N / (min_omega * NS)) + 3;
-    j.K = K;
+    XR_HIP(hipGetLastError());
+    XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    return XRIT_OK;
+}
+
+// ext / scanned: the producer of the samples has left the timing statistic / its count curve too (om_slot, om_scan)
+int ClockStage::launch_chains(bool ext, bool scanned, hipStream_t s, Profiler *prof)
+{
+    Job &j = job;
+    const int K = j.K;
+    float2 *x = xbase();
     const int BL = ext ? om_BL : CLK_OM_BLOCK;
     // (the producer's statistic: block b covers buffer samples [carry + b BL, ...), its phasor counted from the first new sample:
     // the count curve is computed in those coordinates -- same symbol instants, see om_scan -- and placed `carry` samples in)
@@ -2022,57 +1837,7 @@ int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hi
         j.gated = force_gated;
         j.mean_j = jmean_valid && jmean_ns == NS && K >= 256 && !force_gated && !no_meanj;
     }
-    // cfg.clock_exact: 1 -- relayed to closure; n > 1 -- n relay passes; 0 -- auto_passes of them, and on to closure from
-    // finish() when the walks have not settled by then (calls of fewer than auto_min symbols: hand-off passes, relayed from
-    // finish() when they stall high); < 0 -- hand-off passes only
-    j.relay = exact >= 1 || (exact == 0 && auto_passes > 0 && (long long)K * NS >= auto_min);
-    j.relay_budget = exact > 1 ? exact : (exact == 1 ? 0 : auto_passes);
-    // Round 4: the default configuration has NO hand-off passes.  The relay's first pass walks every segment from the timing
-    // guess itself: the loop forgets a start that is 2.6e-2 sample off within ~12 time constants (37 k symbols), so with one
-    // segment per CU (49.6 k symbols at C2) the end states of that pass are as close to the serial trajectory as those of a
-    // walk from a closed hand-off, and the second pass starts from them.  Measured at C2 (steady-state bursts,
-    // profiles/r4_handoff_vs_guess.json): guess + 2 passes over 256 segments 5.3e-5 rms from the serial trajectory, where two
-    // hand-off passes + 3 relay passes over 766 segments had 6.4e-5 -- for two sweeps of the stream instead of five.
-    // (... where the call fills the chip with such segments, or is one segment: in between -- 74 k to 6 M symbols: C5's bursts,
-    // calls of 2^19 .. 2^22 samples -- the walkers are few and it is their latency that counts: two hand-off passes, which
-    // cost such a call 0.1 ms, start them close enough for three passes over segments of 16 k symbols)
-    const long long all_syms = (long long)K * NS;
-    j.no_handoff = j.relay && (relay_no_handoff >= 0 ? relay_no_handoff != 0
-                                                     : exact == 0 && (all_syms <= one_walk_limit() || all_syms >= auto_guess_min));
-    if (j.relay) XR_TRY(relay_plan());
-    if (j.no_handoff && exact == 0) {
-        // passes for the default's parity by segment length (measured, same file: 16.5 k symbols per segment: 3 passes 9.6e-5,
-        // 4 passes 6.2e-5; 24.8 k: ...; 49.6 k: 2 passes 5.3e-5, 3 passes 2.9e-5)
-        const long long L = (long long)j.cps * NS;
-        j.relay_budget = L >= auto_long_seg ? 2 : (L >= auto_long_seg / 2 ? 3 : 4);      // (shorter segments: cfg.clock_exact_window)
-        // cfg.clock_exact = -3, the quick relay: the passes in front of the last are there for their end states and are walked
-        // approximately (clock_relay_kernel's apx) -- the first ones in one guess round, the one before the last in two, leaving
-        // the record of its guesses; no literal verification, no symbols.  Measured at C2 (steady-state bursts, streamed):
-        // 1.92 instead of 2.07 ms per burst, soft symbols 1.15e-4 instead of 5.6e-5 rms from the serial trajectory (which is
-        // itself 1.0e-4 from the oracle); only the first pass approximate: 1.95 ms, 7.5e-5.  (Few segments: a call of up to
-        // `budget` segments closes exactly within its budget if every pass is exact, and stays that way.)
-        // (a plan of two passes -- segments of 49 k symbols and more: C1, C3 -- has one pass in front of its last, and walking that
-        // one in two rounds saves nothing: measured 10.2 against 9.4 ms per C3 burst)
-        if (relay_quick && j.relay_budget >= 3 && j.G > j.relay_budget && j.relay_w == 0) {
-            for (int p = 0; p < 2 && p < j.relay_budget - 1; ++p) j.relay_apx[p] = p == j.relay_budget - 2 ? 2 : 1;
-        }
-    }
-    for (int p = 0; p < 2; ++p) if (relay_apx_cfg[p] >= 0 && j.relay && j.G > 1) j.relay_apx[p] = relay_apx_cfg[p];
-
-    // What the relay passes buy is exact history: after p passes a symbol has between (p - 1) and p segments of exactly
-    // walked trajectory in front of it, and the default's three passes are sized for the segments of the big LRIT bursts
-    // (16.5 k symbols: 33 k .. 50 k symbols of history).  Where a call's segments are three times that long -- bursts at the
-    // circuit rate, 2^28 samples without a decimator: 82 k (LRIT) or 130 k (HRIT) symbols per segment -- two passes leave more
-    // history than that (measured at 49 k symbols per segment: 4.4e-5 rms from the serial trajectory against the three
-    // passes' 6.4e-5, profiles/r3_late_experiments.txt), and the third pass, a third of the relay's time, is not run; nor is the watch on
-    // the segment starts, which compares the starts of the last two passes (here the hand-off's own): the horizon of two
-    // such passes already is that of the seven the watch would ask for.  The look at Es/N0 stays (finish()).
-    j.relay_long = j.relay && !j.no_handoff && exact == 0 && auto_passes >= 3 && (long long)j.cps * NS >= auto_long_seg;
-    if (j.relay_long) j.relay_budget = 2;
-    // (measured at C2: a pass that writes costs ~40 us more than one that does not -- 16-byte stores, 64 lines per wave
-    // instruction --, a call whose last pass did not write pays the output pass, 175 us.  Writing from one pass earlier
-    // than the previous call's last (two writing passes per call) was slower: 2.21 against 2.13 ms per step.)
-    j.write_from = pass_writes ? (last_passes - 1 > 3 ? last_passes - 1 : 3) : 0x7fffffff;
+    if (j.relay) XR_TRY(relay_cut());
     j.dirty = flags.as<int>();
     j.counts = flags.as<int>() + K;
     j.nrun = flags.as<int>() + 2 * K;
@@ -2088,18 +1853,12 @@ int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hi
             if (!ext)
                 hipLaunchKernelGGL(clock_om_kernel, dim3(div_up((size_t)nb, 4)), dim3(256), 0, s, x, X, j.N, nb,
                                    1.0 / (double)sps);
-            if (!scanned) {
-                ClkUnwrapF uf{X, cnt, nb, (double)sps, 0.0, BL, 0.0};
-                hipLaunchKernelGGL(scan_reduce_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb,
-                                   work.as<double>());
-                hipLaunchKernelGGL(scan_apply_lookback_kernel<ClkUnwrapF>, dim3(nbB), dim3(SCAN_BLOCK), 0, s, uf, (long long)nb,
-                                   work.as<double>());
-            }
+            if (!scanned) XR_TRY(clock_unwrap(om, work, nb, BL, (double)sps, s));
             hipLaunchKernelGGL(clock_guess_kernel, dim3(div_up((size_t)K, 256)), dim3(256), 0, s, cnt, nb, (double)sps,
                                S.as<ClockState>(), st_in, K, NS, par.omega_mid, x, table.as<float>(), j.ni, om_off, BL, j.dirty,
                                clock_ctl(counters), (max_passes + 5) * 8, j.terminal, j.written);
         }
-        // (no hand-off passes: the relay's first pass walks from the timing guess itself, see above)
+        // (no hand-off passes: the relay's first pass walks from the timing guess itself, clock_chain_plan)
         if (j.no_handoff) j.relay_force = true;
         else XR_TRY(enqueue_passes(batch < max_passes ? batch : max_passes, s, prof));
     } else {
@@ -2122,7 +1881,7 @@ int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hi
 bool ClockStage::closed() const
 {
     if (job.short_input || job.K <= 1 || job.no_handoff) return true;
-    return reinterpret_cast<const int *>(h_res)[0] != 0;
+    return reinterpret_cast<const int *>(h_res)[CLK_CTL_DONE] != 0;
 }
 
 // After a stream synchronise: continue the passes if the first batch did not close (cold start), commit the
@@ -2131,231 +1890,128 @@ int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
 {
     *n_out = 0;
     in_flight = false;      // (the caller has synchronised: whatever finish() still enqueues it waits for itself)
-    if (ov_cur >= 0) {
-        OvJob &oj = ov[ov_cur];
-        const int *hc = reinterpret_cast<const int *>(h_res);
-        ClockResult r;
-        memcpy(&r, reinterpret_cast<const unsigned *>(h_res) + CLK_RES_WORD, sizeof r);
-        float snr2, far_;
-        memcpy(&snr2, &hc[14], sizeof snr2);
-        memcpy(&far_, &hc[18], sizeof far_);
-        snr_estimate = snr2;
-        ov_walkers = oj.G;
-        ov_joint_max = far_;
-        relay_passes = 1;
-        relay_closed = false;
-        relay_auto = false;
-        relay_segments = oj.G;
-        relay_seg_chains = 0;
-        passes = 0;
-        unconverged = 0; max_residual = 0; large_open = 0;     // (the hand-off's figures: this plan has no hand-off)
-        if (trace_env) {
-            unsigned hs[8];
-            XR_HIP(hipMemcpy(hs, oj.aux.p, sizeof hs, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[xrit] overlap: %d walkers over ranges of %d samples behind %d samples of history (%s), %u steps, %.2f guess rounds per step; "
-                            "joints: %d do not fit, largest distance %.3e sample; 2 Es/N0 = %.1f; %llu symbols%s\n",
-                    oj.G, oj.Ls, oj.hist, oj.w0_carried ? "walker 0 from the carried state" : "walker 0 warms up in the burst before", hs[0],
-                    hs[0] ? (double)hs[1] / hs[0] : 0.0, hc[17], (double)far_, (double)snr2, (unsigned long long)r.n_symbols, r.ok ? "" : " -- NOT taken");
-#ifdef XRIT_RELAY_TIMING
-            // (what the walkers that have finished since the last look spent per step, whichever burst they belong to)
-            unsigned long long hd[16] = {0}, z[16] = {0};
-            XR_HIP(hipMemcpyFromSymbol(hd, HIP_SYMBOL(relay_dbg), sizeof hd));
-            XR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(relay_dbg), z, sizeof z));
-            const double st = hd[6] ? (double)hd[6] : 1.0;
-            fprintf(stderr, "[xrit] overlap walkers, cycles per step: ring wait %.0f, setup %.0f, guess rounds %.0f, literal step + verdict %.0f, "
-                            "stage + commit %.0f, loop %.0f; sum %.0f (%llu steps)\n", hd[0] / st, hd[1] / st, hd[2] / st, hd[3] / st, hd[4] / st,
-                    hd[5] / st, (hd[0] + hd[1] + hd[2] + hd[3] + hd[4] + hd[5]) / st, hd[6]);
-#endif
-        }
-        if (hc[15]) { set_error("clock recovery: a walker gave up waiting for its sample ring (watchdog)"); oj.state = 0; ov_cur = -1; return XRIT_E_HIP; }
-        // The default configuration's two looks at such a call (ClockStage::finish below has them for the relay): Es/N0 below 7 dB
-        // -- walked to closure, the serial trajectory whatever the noise --, and a joint whose two trajectories do not meet within a
-        // quarter symbol -- the timing guess and the loop disagree about a symbol count.
-        const bool signal = snr2 >= auto_snr_floor;
-        if ((signal && !(snr2 >= auto_snr)) || hc[17] > 0) return ov_fallback(n_out, s, prof, signal);
-        oj.state = 0;
-        const int jb = ov_cur;
-        ov_cur = -1;
-        if (!r.ok) {
-            if ((size_t)r.n_symbols > ov_cap) { set_error("clock recovery produced %zu symbols, capacity %zu", (size_t)r.n_symbols, ov_cap); return XRIT_E_CAPACITY; }
-            set_error("clock recovery: the walkers did not reach the end of the input");
-            return XRIT_E_INVALID;
-        }
-        cur ^= 1;
-        carry = (size_t)(oj.N - r.ii_final);
-        if (carry > 1024) { set_error("clock recovery: carry of %zu samples exceeds the hand-over buffer", carry); return XRIT_E_INVALID; }
-        last_symbols = (size_t)r.n_symbols;
-        *n_out = last_symbols;
-        hist_xb = jb; hist_len = (size_t)oj.padN + oj.n; hist_job = jb;
-        redo_ok = true;
-        return XRIT_OK;
-    }
+    if (ov_cur >= 0) return finish_overlap(n_out, s, prof);
     if (job.short_input) {
         carry = (size_t)job.N;
         last_symbols = 0;
         cur ^= 1;
         return XRIT_OK;
     }
+    return finish_chains(n_out, s, prof);
+}
+
+int ClockStage::finish_overlap(size_t *n_out, hipStream_t s, Profiler *prof)
+{
+    OvJob &oj = ov[ov_cur];
+    const int *hc = reinterpret_cast<const int *>(h_res);
+    ClockResult r;
+    memcpy(&r, reinterpret_cast<const unsigned *>(h_res) + CLK_RES_WORD, sizeof r);
+    snr_estimate = clock_ctl_float(hc, CLK_CTL_SNR2);
+    ov_walkers = oj.G;
+    ov_joint_max = clock_ctl_float(hc, CLK_CTL_OV_JOINT_MAX);
+    relay_passes = 1;
+    relay_closed = false;
+    relay_auto = false;
+    relay_segments = oj.G;
+    relay_seg_chains = 0;
+    passes = 0;
+    unconverged = 0; max_residual = 0; large_open = 0;     // (the hand-off's figures: this plan has no hand-off)
+    if (trace_env) XR_TRY(trace_overlap(oj, r));
+    const ClockOvVerdict v = clock_overlap_look(*this, hc);
+    if (v == CLK_OV_WATCHDOG) { set_error("clock recovery: a walker gave up waiting for its sample ring (watchdog)"); oj.state = 0; ov_cur = -1; return XRIT_E_HIP; }
+    if (v != CLK_OV_TAKE) return ov_fallback(n_out, s, prof, v == CLK_OV_FALLBACK_TO_CLOSURE);
+    oj.state = 0;
+    const int jb = ov_cur;
+    ov_cur = -1;
+    if (!r.ok) {
+        if ((size_t)r.n_symbols > ov_cap) { set_error("clock recovery produced %zu symbols, capacity %zu", (size_t)r.n_symbols, ov_cap); return XRIT_E_CAPACITY; }
+        set_error("clock recovery: the walkers did not reach the end of the input");
+        return XRIT_E_INVALID;
+    }
+    cur ^= 1;
+    carry = (size_t)(oj.N - r.ii_final);
+    if (carry > 1024) { set_error("clock recovery: carry of %zu samples exceeds the hand-over buffer", carry); return XRIT_E_INVALID; }
+    last_symbols = (size_t)r.n_symbols;
+    *n_out = last_symbols;
+    hist_xb = jb; hist_len = (size_t)oj.padN + oj.n; hist_job = jb;
+    redo_ok = true;
+    return XRIT_OK;
+}
+
+// the hand-off passes of a call whose first batch did not close, then its relay or output pass
+int ClockStage::finish_handoff(hipStream_t s, Profiler *prof)
+{
     const int *hctl = reinterpret_cast<const int *>(h_res);
-    const bool in_batch = closed();
-    if (!in_batch) {
-        // (past 48 passes a hand-off that is still open is an acquisition that closes a chain or two per pass: unless
-        // the exact closure is switched off the relay takes over -- it walks from whatever start states there are)
-        const int give_up = exact != -1 && max_passes > 48 ? 48 : max_passes;
-        while (hctl[0] == 0 && job.enqueued < give_up) {
-            // a boundary outside the trust region (acquisition, a slip): from here on the gated three-launch solve
-            if (hctl[NEWTON_CTL_TAKEOVER]) job.gated = true;
-            XR_TRY(enqueue_passes(4, s, prof));
-            XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-            XR_HIP(hipStreamSynchronize(s));
-        }
-        // (a hand-off that used up its pass budget without closing -- ctl[0] still 0 -- is relayed all the same: the
-        // walkers need start states, not a closed hand-off)
-        job.relay_force = hctl[0] == 0;
-        if (job.relay && job.K > 1) XR_TRY(enqueue_relay(relay_batch, true, s, prof));
-        else XR_TRY(enqueue_output(s, prof, true));
+    // (past 48 passes a hand-off that is still open is an acquisition that closes a chain or two per pass: unless
+    // the exact closure is switched off the relay takes over -- it walks from whatever start states there are)
+    const int give_up = job.exact != -1 && max_passes > 48 ? 48 : max_passes;
+    while (hctl[CLK_CTL_DONE] == 0 && job.enqueued < give_up) {
+        // a boundary outside the trust region (acquisition, a slip): from here on the gated three-launch solve
+        if (hctl[CLK_CTL_TAKEOVER]) job.gated = true;
+        XR_TRY(enqueue_passes(4, s, prof));
+        XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
         XR_HIP(hipStreamSynchronize(s));
     }
+    // (a hand-off that used up its pass budget without closing -- DONE still 0 -- is relayed all the same: the
+    // walkers need start states, not a closed hand-off)
+    job.relay_force = hctl[CLK_CTL_DONE] == 0;
+    if (job.relay && job.K > 1) XR_TRY(enqueue_relay(relay_batch, true, s, prof));
+    else XR_TRY(enqueue_output(s, prof, true));
+    XR_HIP(hipStreamSynchronize(s));
+    return XRIT_OK;
+}
+
+// the looks at the relay (clock_relay_look), each followed by what it asks for and a wait
+int ClockStage::finish_relay(hipStream_t s, Profiler *prof)
+{
+    const int *hctl = reinterpret_cast<const int *>(h_res);
+    const ClockKnobs k = call_knobs();
+    ClockRelayLook c;
+    c.relay_force = job.relay_force; c.no_handoff = job.no_handoff; c.relay_long = job.relay_long; c.G = job.G;
+    for (;;) {
+        c.relay_auto = relay_auto; c.relay_enq = job.relay_enq; c.relay_budget = job.relay_budget;
+        const ClockRelayStep v = clock_relay_look(k, hctl, c);
+        c.first = false;
+        relay_auto = v.relay_auto;
+        job.relay_budget = v.relay_budget;
+        if (v.snr_seen) snr_estimate = v.snr2;
+        if (v.verdict == CLK_RELAY_TAKE || v.verdict == CLK_RELAY_NO_SIGNAL) break;
+        if (v.verdict == CLK_RELAY_TO_CLOSURE) continue;
+        XR_TRY(enqueue_relay(v.verdict == CLK_RELAY_FOUR_MORE ? 4 : (relay_batch < 32 ? 32 : relay_batch), false, s, prof));
+        XR_HIP(hipStreamSynchronize(s));
+    }
+    relay_passes = hctl[CLK_CTL_RELAY_PASSES];
+    relay_closed = hctl[CLK_CTL_RELAY_CLOSED] != 0;
+    if (trace_env) XR_TRY(trace_relay());
+    relay_batch = clock_next_relay_batch(relay_passes);
+    return XRIT_OK;
+}
+
+int ClockStage::finish_chains(size_t *n_out, hipStream_t s, Profiler *prof)
+{
+    const int *hctl = reinterpret_cast<const int *>(h_res);
+    const bool in_batch = closed();
+    if (!in_batch) XR_TRY(finish_handoff(s, prof));
     relay_passes = 0;
     relay_closed = false;
     relay_auto = false;
-    if ((exact == 0 || exact <= -2) && job.K > 1 && !job.relay) {
-        // (cfg.clock_exact = 0: a call too short for the relay to be planned at its start; -2: the fast configuration)
-        // The hand-off passes normally stall at the recurrence's own floor, an rms residual of ~1e-4 sample (Es/N0 12 dB).
-        // At low Es/N0 they stall at 5e-4 .. 1e-3 instead -- every wrong decision kicks mu by 2e-3 -- and which
-        // near-zero symbols then fall on the other side differs from the serial loop (a third
-        // of the 2..6 dB fuzz cases flip 1..5 decisions).  Such a call is closed exactly: the relay reproduces the
-        // serial trajectory whatever the noise.
-        float q;
-        memcpy(&q, &hctl[4], sizeof q);
-        const int open_ = hctl[6];
-        // (... and a hand-off that never closed at all -- the pass budget ran out on an acquisition -- has every reason
-        // to be walked: the relay needs start states, not a closed hand-off)
-        if (hctl[0] == 0 || (open_ > 0 && q > auto_rms * auto_rms * (float)open_)) {
-            job.relay = relay_auto = true;
-            job.relay_force = hctl[0] == 0;
-            job.relay_budget = 0;
-            XR_TRY(relay_plan());
-            XR_TRY(enqueue_relay(relay_batch, true, s, prof));
-            XR_HIP(hipStreamSynchronize(s));
-        }
+    if (clock_handoff_to_closure(call_knobs(), hctl, job.K, job.relay)) {
+        job.relay = relay_auto = true;
+        job.relay_force = hctl[CLK_CTL_DONE] == 0;
+        job.relay_budget = 0;
+        job.segs = clock_relay_segments(call_knobs(), job.K, NS, job.no_handoff, job.relay_budget, job.relay_w);
+        XR_TRY(relay_cut());
+        XR_TRY(enqueue_relay(relay_batch, true, s, prof));
+        XR_HIP(hipStreamSynchronize(s));
     }
-    if (job.relay && job.K > 1) {
-        if (exact == 0 && !relay_auto && hctl[11] == 0) {
-            // The default: after its three passes the segment starts of a clean signal move by a few 1e-4 sample rms from
-            // pass to pass.  Where they still move by more -- low Es/N0: every decision that differs kicks mu by 2e-3 --,
-            // or the hand-off passes never closed, the call is walked to closure: the serial trajectory whatever the noise.
-            // Not to closure at once: four more passes at a time until the starts have settled too (Es/N0 6 dB: after six
-            // passes, 4.4 ms per 2^28-sample burst; at 3 dB they never do before the relay closes, 40 passes).
-            float shift_sq;
-            memcpy(&shift_sq, &hctl[12], sizeof shift_sq);
-            float snr2;            // 2 Es/N0 as the first pass's soft symbols show it (12 dB: 32, 7 dB: 10)
-            memcpy(&snr2, &hctl[14], sizeof snr2);
-            snr_estimate = snr2;
-            // Below auto_snr the call is walked to closure: the serial trajectory whatever the noise (in a 2..6 dB fuzz
-            // slice of 60 calls up to 350 k symbols the passes-until-settled rule alone left one hard decision different
-            // from the serial trajectory's -- a call of 14 segments whose starts happened to move by 3e-4 -- and the
-            // hand-off passes of rounds 2-3 ten).
-            // (... unless there is no signal to speak of: |noise| alone shows 2 / (pi - 2) = 1.75, BPSK at Es/N0 0 dB 2.4; a
-            // loop that is not locked has no trajectory to close on, the relay would run its G + 1 passes for nothing)
-            const bool signal = snr2 >= auto_snr_floor;
-            if (signal && ((job.relay_force && !job.no_handoff) || !(snr2 >= auto_snr))) {
-                relay_auto = true;
-                job.relay_budget = 0;
-            }
-            if (!signal || relay_auto || job.relay_long || job.no_handoff) shift_sq = 0.0f;
-            // Without hand-off passes nothing has settled symbol slips between the timing guess and the loop: a start that moved
-            // by the better part of a symbol between the first pass (the guess) and a later one (the end state of the segment
-            // in front) means the guess counted a symbol more or less than the loop there, and every segment behind it is one
-            // symbol off until the exact front reaches it -- the call is walked to closure.
-            if (job.no_handoff && signal && !relay_auto) {
-                float mv;
-                memcpy(&mv, &hctl[16], sizeof mv);
-                if (!(mv < 0.25f * sps)) {
-                    relay_auto = true;
-                    job.relay_budget = 0;
-                }
-            }
-            while (!relay_auto && !(shift_sq <= auto_shift * auto_shift) && hctl[11] == 0 && job.relay_enq < job.G + 1) {
-                relay_auto = true;
-                job.relay_budget = job.relay_enq + 4;
-                XR_TRY(enqueue_relay(4, false, s, prof));
-                XR_HIP(hipStreamSynchronize(s));
-                memcpy(&shift_sq, &hctl[12], sizeof shift_sq);
-            }
-        }
-        // the relay goes on until a pass changes nothing (or the pass budget of a partial closure is used up)
-        while (hctl[11] == 0 && job.relay_enq < relay_limit()) {
-            // (a closure nobody asked for -- cfg.clock_exact = 0 / -2 -- is not pursued on an input without a signal: an
-            // unlocked loop has no trajectory to close on and would take all G + 1 passes)
-            float snr2;
-            memcpy(&snr2, &hctl[14], sizeof snr2);
-            if (relay_auto && exact != 1 && !(snr2 >= auto_snr_floor)) break;
-            XR_TRY(enqueue_relay(relay_batch < 32 ? 32 : relay_batch, false, s, prof));
-            XR_HIP(hipStreamSynchronize(s));
-        }
-        relay_passes = hctl[10];
-        relay_closed = hctl[11] != 0;
-        if (trace_env && exact == 0) fprintf(stderr, "[xrit] relay: the first pass's soft symbols show 2 Es/N0 = %.1f (to closure below %.1f)\n", (double)snr_estimate, (double)auto_snr);
-        if (trace_env) {
-            std::vector<unsigned> hc((size_t)relay_passes * RELAY_STAT);
-            const unsigned *changed = reinterpret_cast<const unsigned *>(relay.as<RelaySeg>() + 3 * (size_t)job.G);
-            XR_HIP(hipMemcpy(hc.data(), changed, hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-            for (int p = 0; p < relay_passes; ++p) {
-                const unsigned *c = &hc[(size_t)RELAY_STAT * p];
-                float mv;
-                memcpy(&mv, &c[3], sizeof mv);
-                const unsigned long long sq = (unsigned long long)c[4] | ((unsigned long long)c[5] << 32);
-                fprintf(stderr, "[xrit] relay pass %d: segments walked %u of %d, steps %u, rounds %u (%.2f per step); starts moved by %.3e sample rms, %.3e at most%s\n", p,
-                        c[0], job.G, c[1], c[2], c[1] ? (double)c[2] / c[1] : 0.0,
-                        c[6] ? sqrt((double)sq / 1099511627776.0 / (double)c[6]) : 0.0,
-                        c[3] >= 0x80000000u ? 0.0 : (double)mv, c[3] >= 0x80000000u ? " (watchdog mark)" : "");
-            }
-        }
-#ifdef XRIT_RELAY_TIMING
-        if (trace_env) {
-            unsigned long long hd[16] = {0}, z[16] = {0};
-            XR_HIP(hipMemcpyFromSymbol(hd, HIP_SYMBOL(relay_dbg), sizeof hd));
-            XR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(relay_dbg), z, sizeof z));
-            std::vector<unsigned> wd((size_t)RELAY_WDBG_PASSES * RELAY_WDBG_SEGS * RELAY_WDBG_WORDS);
-            XR_HIP(hipMemcpyFromSymbol(wd.data(), HIP_SYMBOL(relay_wdbg), wd.size() * sizeof(unsigned)));
-            for (int p = 0; p < relay_passes && p < RELAY_WDBG_PASSES && job.relay_w == 0; ++p)
-                for (int g = 0; g < job.G && g < RELAY_WDBG_SEGS; ++g) {
-                    const unsigned *w = &wd[((size_t)p * RELAY_WDBG_SEGS + g) * RELAY_WDBG_WORDS];
-                    fprintf(stderr, "[xrit] walker %d %d %u %u %u %u %u %u\n", p, g, w[0], w[1], w[2], w[3], w[4], w[5]);
-                }
-            if (job.relay_w > 0) {
-                const double st = hd[7] ? (double)hd[7] : 1.0, un = hd[9] ? (double)hd[9] : 1.0;
-                (void)un;
-                fprintf(stderr, "[xrit] relay team (wave 1) cycles per step: rings %.0f, setup %.0f, interpolate..scan %.0f, meeting + sums %.0f, "
-                                "positions..verdict %.0f, meeting + verdicts %.0f, commit + loop %.0f (%llu steps)\n",
-                        hd[0] / st, hd[1] / st, hd[2] / st, hd[3] / st, hd[4] / st, hd[5] / st, hd[6] / st, hd[7]);
-            }
-            for (int o = 0; o < 16 && job.relay_w == 0; o += 8) {
-                const double st = hd[o + 6] ? (double)hd[o + 6] : 1.0;
-                fprintf(stderr, "[xrit] relay walker cycles per step, passes %s: wait %.0f, setup %.0f, rounds %.0f, verify %.0f, commit %.0f, loop head %.0f (%llu steps)\n",
-                        o ? ">= 8" : "< 8", hd[o] / st, hd[o + 1] / st, hd[o + 2] / st, hd[o + 3] / st, hd[o + 4] / st, hd[o + 5] / st, hd[o + 6]);
-            }
-        }
-#endif
-        const int want = relay_passes + relay_passes / 4 + 8;
-        relay_batch = want < 32 ? 32 : (want > 4096 ? 4096 : want);
-    }
-    passes = job.K > 1 ? hctl[1] : 0;
+    if (job.relay && job.K > 1) XR_TRY(finish_relay(s, prof));
+    passes = job.K > 1 ? hctl[CLK_CTL_PASSES] : 0;
     if (job.K > 1) {
-        // one spare pass beyond what this call needed.  Unlike the Costas loop's, it is never dropped: the stall
-        // rule ends the passes one earlier or later from burst to burst (measured: one C2 burst in ten needs six
-        // instead of five), and a call that runs out of enqueued passes costs a host round trip, two more passes
-        // and a second output pass -- 0.5 ms against the 19 us the four idle launches take.
         last_passes = passes;
-        const int want = passes + 1;
-        // (small calls run on while boundaries still freeze: 10..20 passes; a call that hands over to the relay after two
-        // passes does not need five launches enqueued -- the idle ones are 10 us each)
-        const int least = job.relay && passes <= 2 ? 3 : 5;
-        batch = want < least ? least : (want > 32 ? 32 : want);
+        batch = clock_next_batch(passes, job.relay);
     }
     if (job.K > 1) {
-        const bool clean = in_batch && hctl[NEWTON_CTL_TAKEOVER] == 0 && hctl[9] == 0 && passes <= 12;
+        const bool clean = in_batch && hctl[CLK_CTL_TAKEOVER] == 0 && hctl[CLK_CTL_LARGE] == 0 && passes <= 12;
         if (job.mean_j && !clean) jmean_valid = false;           // the stream has changed: measure again
         else if (!job.mean_j && !job.gated && clean && job.K >= 1024 && jac_passes > 0 && !job.no_handoff) {
             hipLaunchKernelGGL(clock_jmean_kernel, dim3(1), dim3(256), 0, s, J.as<float4>(), job.K, jmean.as<float4>());
@@ -2363,23 +2019,10 @@ int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
             jmean_ns = NS;
         }
     }
-    unconverged = job.K > 1 ? (unsigned)hctl[2] : 0;
-    large_open = job.K > 1 ? (unsigned)hctl[9] : 0;
-    memcpy(&max_residual, &hctl[3], sizeof(float));
-    if (trace_env && job.K > 1) {
-        std::vector<unsigned> hc((size_t)passes * 8);
-        XR_HIP(hipMemcpy(hc.data(), clock_cnt(counters, 0), hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        for (int p = 0; p < passes; ++p) {
-            float mr;
-            unsigned long long qf;
-            memcpy(&mr, &hc[(size_t)p * 8 + 2], 4);
-            memcpy(&qf, &hc[(size_t)p * 8 + 4], 8);
-            const float q = (float)((double)qf / 1099511627776.0);
-            fprintf(stderr, "[xrit] clock pass %d: K=%d changed=%u open=%u max_r=%.3e large=%u rms_r=%.3e\n", p, job.K,
-                    hc[(size_t)p * 8], hc[(size_t)p * 8 + 1], mr, hc[(size_t)p * 8 + 3],
-                    hc[(size_t)p * 8 + 1] ? sqrtf(q / hc[(size_t)p * 8 + 1]) : 0.f);
-        }
-    }
+    unconverged = job.K > 1 ? (unsigned)hctl[CLK_CTL_OPEN] : 0;
+    large_open = job.K > 1 ? (unsigned)hctl[CLK_CTL_LARGE] : 0;
+    max_residual = clock_ctl_float(hctl, CLK_CTL_MAX_RESIDUAL);
+    if (trace_env && job.K > 1) XR_TRY(trace_passes());
     ClockResult r;
     memcpy(&r, reinterpret_cast<const unsigned *>(h_res) + CLK_RES_WORD, sizeof r);
     cur ^= 1;
@@ -2387,7 +2030,7 @@ int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
         set_error("clock recovery produced more than the %zu symbols the output holds", job.cap);
         return XRIT_E_CAPACITY;
     }
-    if (!r.ok && job.relay && hctl[15]) {
+    if (!r.ok && job.relay && hctl[CLK_CTL_STUCK]) {
         set_error("clock recovery: a relay walker gave up waiting for its sample ring or its team (watchdog)");
         return XRIT_E_HIP;
     }
@@ -2407,8 +2050,93 @@ int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
         return XRIT_E_CAPACITY;
     }
     redo_ok = true;
-    // (what this call left in its buffer is history for an overlap call behind it only together with a timing curve: none here)
-    hist_xb = xbase_fixed ? hist_xb : xb; hist_len = xbase_fixed ? hist_len : prev_carry + prev_n; hist_job = xbase_fixed ? hist_job : -1;
+    // (what this call left in its buffer is history for an overlap call behind it only together with a timing curve: none here;
+    // a call on samples that lie elsewhere leaves what there was)
+    if (!job.base) { hist_xb = xb; hist_len = prev_carry + prev_n; hist_job = -1; }
+    return XRIT_OK;
+}
+
+// ---- XRIT_TRACE=1: what a call did, on stderr ---------------------------------------------------------------------
+int ClockStage::trace_overlap(const OvJob &oj, const ClockResult &r) const
+{
+    const int *hc = reinterpret_cast<const int *>(h_res);
+    unsigned hs[8];
+    XR_HIP(hipMemcpy(hs, oj.aux.p, sizeof hs, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[xrit] overlap: %d walkers over ranges of %d samples behind %d samples of history (%s), %u steps, %.2f guess rounds per step; "
+                    "joints: %d do not fit, largest distance %.3e sample; 2 Es/N0 = %.1f; %llu symbols%s\n",
+            oj.G, oj.Ls, oj.hist, oj.w0_carried ? "walker 0 from the carried state" : "walker 0 warms up in the burst before", hs[0],
+            hs[0] ? (double)hs[1] / hs[0] : 0.0, hc[CLK_CTL_OV_BAD_JOINTS], (double)ov_joint_max, (double)snr_estimate, (unsigned long long)r.n_symbols, r.ok ? "" : " -- NOT taken");
+#ifdef XRIT_RELAY_TIMING
+    // (what the walkers that have finished since the last look spent per step, whichever burst they belong to)
+    unsigned long long hd[16] = {0}, z[16] = {0};
+    XR_HIP(hipMemcpyFromSymbol(hd, HIP_SYMBOL(relay_dbg), sizeof hd));
+    XR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(relay_dbg), z, sizeof z));
+    const double st = hd[6] ? (double)hd[6] : 1.0;
+    fprintf(stderr, "[xrit] overlap walkers, cycles per step: ring wait %.0f, setup %.0f, guess rounds %.0f, literal step + verdict %.0f, "
+                    "stage + commit %.0f, loop %.0f; sum %.0f (%llu steps)\n", hd[0] / st, hd[1] / st, hd[2] / st, hd[3] / st, hd[4] / st,
+            hd[5] / st, (hd[0] + hd[1] + hd[2] + hd[3] + hd[4] + hd[5]) / st, hd[6]);
+#endif
+    return XRIT_OK;
+}
+
+int ClockStage::trace_relay() const
+{
+    if (job.exact == 0) fprintf(stderr, "[xrit] relay: the first pass's soft symbols show 2 Es/N0 = %.1f (to closure below %.1f)\n", (double)snr_estimate, (double)auto_snr);
+    std::vector<unsigned> hc((size_t)relay_passes * RELAY_STAT);
+    const unsigned *changed = reinterpret_cast<const unsigned *>(relay.as<RelaySeg>() + 3 * (size_t)job.G);
+    XR_HIP(hipMemcpy(hc.data(), changed, hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int p = 0; p < relay_passes; ++p) {
+        const unsigned *c = &hc[(size_t)RELAY_STAT * p];
+        float mv;
+        memcpy(&mv, &c[RELAY_STAT_MOVE_MAX], sizeof mv);
+        const unsigned long long sq = (unsigned long long)c[RELAY_STAT_MOVE_SQ] | ((unsigned long long)c[RELAY_STAT_MOVE_SQ + 1] << 32);
+        const bool mark = c[RELAY_STAT_MOVE_MAX] >= 0x80000000u;
+        fprintf(stderr, "[xrit] relay pass %d: segments walked %u of %d, steps %u, rounds %u (%.2f per step); starts moved by %.3e sample rms, %.3e at most%s\n", p,
+                c[RELAY_STAT_CHANGED], job.G, c[RELAY_STAT_STEPS], c[RELAY_STAT_ROUNDS], c[RELAY_STAT_STEPS] ? (double)c[RELAY_STAT_ROUNDS] / c[RELAY_STAT_STEPS] : 0.0,
+                c[RELAY_STAT_MOVED] ? sqrt((double)sq / 1099511627776.0 / (double)c[RELAY_STAT_MOVED]) : 0.0,
+                mark ? 0.0 : (double)mv, mark ? " (watchdog mark)" : "");
+    }
+#ifdef XRIT_RELAY_TIMING
+    unsigned long long hd[16] = {0}, z[16] = {0};
+    XR_HIP(hipMemcpyFromSymbol(hd, HIP_SYMBOL(relay_dbg), sizeof hd));
+    XR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(relay_dbg), z, sizeof z));
+    std::vector<unsigned> wd((size_t)RELAY_WDBG_PASSES * RELAY_WDBG_SEGS * RELAY_WDBG_WORDS);
+    XR_HIP(hipMemcpyFromSymbol(wd.data(), HIP_SYMBOL(relay_wdbg), wd.size() * sizeof(unsigned)));
+    for (int p = 0; p < relay_passes && p < RELAY_WDBG_PASSES && job.relay_w == 0; ++p)
+        for (int g = 0; g < job.G && g < RELAY_WDBG_SEGS; ++g) {
+            const unsigned *w = &wd[((size_t)p * RELAY_WDBG_SEGS + g) * RELAY_WDBG_WORDS];
+            fprintf(stderr, "[xrit] walker %d %d %u %u %u %u %u %u\n", p, g, w[0], w[1], w[2], w[3], w[4], w[5]);
+        }
+    if (job.relay_w > 0) {
+        const double st = hd[7] ? (double)hd[7] : 1.0, un = hd[9] ? (double)hd[9] : 1.0;
+        (void)un;
+        fprintf(stderr, "[xrit] relay team (wave 1) cycles per step: rings %.0f, setup %.0f, interpolate..scan %.0f, meeting + sums %.0f, "
+                        "positions..verdict %.0f, meeting + verdicts %.0f, commit + loop %.0f (%llu steps)\n",
+                hd[0] / st, hd[1] / st, hd[2] / st, hd[3] / st, hd[4] / st, hd[5] / st, hd[6] / st, hd[7]);
+    }
+    for (int o = 0; o < 16 && job.relay_w == 0; o += 8) {
+        const double st = hd[o + 6] ? (double)hd[o + 6] : 1.0;
+        fprintf(stderr, "[xrit] relay walker cycles per step, passes %s: wait %.0f, setup %.0f, rounds %.0f, verify %.0f, commit %.0f, loop head %.0f (%llu steps)\n",
+                o ? ">= 8" : "< 8", hd[o] / st, hd[o + 1] / st, hd[o + 2] / st, hd[o + 3] / st, hd[o + 4] / st, hd[o + 5] / st, hd[o + 6]);
+    }
+#endif
+    return XRIT_OK;
+}
+
+int ClockStage::trace_passes() const
+{
+    std::vector<unsigned> hc((size_t)passes * CLK_CNT_WORDS);
+    XR_HIP(hipMemcpy(hc.data(), clock_cnt(counters, 0), hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int p = 0; p < passes; ++p) {
+        const unsigned *c = &hc[(size_t)p * CLK_CNT_WORDS];
+        float mr;
+        unsigned long long qf;
+        memcpy(&mr, &c[CLK_CNT_MAX_R], 4);
+        memcpy(&qf, &c[CLK_CNT_SUM_SQ], 8);
+        const float q = (float)((double)qf / 1099511627776.0);
+        fprintf(stderr, "[xrit] clock pass %d: K=%d changed=%u open=%u max_r=%.3e large=%u rms_r=%.3e\n", p, job.K,
+                c[CLK_CNT_CHANGED], c[CLK_CNT_OPEN], mr, c[CLK_CNT_LARGE], c[CLK_CNT_OPEN] ? sqrtf(q / c[CLK_CNT_OPEN]) : 0.f);
+    }
     return XRIT_OK;
 }
 
@@ -2438,6 +2166,17 @@ int ClockStage::run(size_t n, float *soft_out, float2 *sym_out, size_t cap, size
     return finish(n_out, s, prof);
 }
 
+// the chains once more, or instead of the overlap plan: on samples that lie at `base`, with `exact_` for cfg.clock_exact
+int ClockStage::run_chains(float2 *base, int exact_, size_t n, float *soft_out, float2 *sym_out, size_t cap, size_t *n_out, hipStream_t s, Profiler *prof)
+{
+    call_reset(n);
+    XR_TRY(begin_chains(base, exact_, n, soft_out, sym_out, cap, s, prof));
+    XR_HIP(hipStreamSynchronize(s));
+    const int rc = finish(n_out, s, prof);
+    job.base = nullptr;
+    return rc;
+}
+
 static constexpr size_t CLK_ALT_SLOT = sizeof(ClockState) + 1024 * sizeof(float2);
 
 int ClockStage::redo_flipped(float *soft_out, float2 *sym_out, size_t cap, size_t *n_out, hipStream_t s, Profiler *prof)
@@ -2464,10 +2203,8 @@ int ClockStage::redo_flipped(float *soft_out, float2 *sym_out, size_t cap, size_
     // (the samples kept as the NEXT call's history are negated now: walkers of an overlap job must not warm up over them)
     hist_xb = -1; hist_len = 0; hist_job = -1;
     XR_HIP(hipGetLastError());
-    xbase_fixed = data - carry;             // (carry <= 1024 <= xpad: never in front of the buffer)
-    const int rc = run(n, soft_out, sym_out, cap, n_out, s, prof);
-    xbase_fixed = nullptr;
-    return rc;
+    // (the input lies where it was; carry <= 1024 <= xpad: never in front of the buffer)
+    return run_chains(data - carry, exact, n, soft_out, sym_out, cap, n_out, s, prof);
 }
 
 __global__ void __launch_bounds__(1024) clock_carry_pack_kernel(unsigned char *__restrict__ rec, const ClockState *__restrict__ st,
@@ -2525,10 +2262,8 @@ int ClockStage::redo_from(const void *d_rec, size_t carry_rec, float *soft_out, 
     carry = carry_rec;
     alt_valid = false;
     hist_xb = -1; hist_len = 0; hist_job = -1;      // (what lies in front of the input now is another handle's tail: no history for walkers)
-    xbase_fixed = data - carry;             // (carry <= 1024 <= xpad: never in front of the buffer)
-    const int rc = run(n, soft_out, sym_out, cap, n_out, s, prof);
-    xbase_fixed = nullptr;
-    return rc;
+    // (the input lies where it was; carry <= 1024 <= xpad: never in front of the buffer)
+    return run_chains(data - carry, exact, n, soft_out, sym_out, cap, n_out, s, prof);
 }
 
 int ClockStage::make_alt(hipStream_t s, Profiler *prof)

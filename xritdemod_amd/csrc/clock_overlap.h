@@ -382,8 +382,8 @@ __global__ void clock_overlap_guess_kernel(const double *__restrict__ cnt, int n
 // front (the carried state, for walker 0) -- the staged symbol nearest to where that walker's end state reads next --, how
 // many symbols it contributes and where they go; then the call's result as clock_relay_finalize_kernel leaves it (symbol
 // count, carried state, unread tail, the look at the signal-to-noise ratio).
-// ctl[10] = 1 (passes), [11] = 0, [14] = 2 Es/N0 (float bits), [15] = stuck, [17] = joints that do not fit, [18] = largest
-// distance between a joint's two trajectories (float bits, samples), [19] = walkers
+// Control words (clock_ctl.h): RELAY_PASSES = 1, RELAY_CLOSED = 0, SNR2 = 2 Es/N0 (float bits), STUCK, OV_BAD_JOINTS = joints that do
+// not fit, OV_JOINT_MAX = largest distance between a joint's two trajectories (float bits, samples), WALKERS
 __global__ void __launch_bounds__(256) clock_overlap_scan_kernel(const OverlapSeg *__restrict__ segs, int G, int stride,
                                                                   const ClockState *__restrict__ carried_in, int w0_ii,
                                                                   int w0_carried, float omega_mid, int *__restrict__ j0,
@@ -454,14 +454,14 @@ __global__ void __launch_bounds__(256) clock_overlap_scan_kernel(const OverlapSe
     __syncthreads();
     if (threadIdx.x == 0) {
         ClockState st;
-        ctl[10] = 1;
-        ctl[11] = 0;
-        ctl[12] = 0;
-        ctl[15] = s_stuck;
-        ctl[16] = 0;
-        ctl[17] = s_bad;
-        ctl[18] = (int)s_far;
-        ctl[19] = G;
+        ctl[CLK_CTL_RELAY_PASSES] = 1;
+        ctl[CLK_CTL_RELAY_CLOSED] = 0;
+        ctl[CLK_CTL_RELAY_SHIFT_SQ] = 0;
+        ctl[CLK_CTL_STUCK] = s_stuck;
+        ctl[CLK_CTL_RELAY_MOVE_MAX] = 0;
+        ctl[CLK_CTL_OV_BAD_JOINTS] = s_bad;
+        ctl[CLK_CTL_OV_JOINT_MAX] = (int)s_far;
+        ctl[CLK_CTL_WALKERS] = G;
         const bool ok = term < G && !s_stuck && s_bad == 0 && run <= cap;
         if (!ok) {
             res->ok = 0;
@@ -479,7 +479,7 @@ __global__ void __launch_bounds__(256) clock_overlap_scan_kernel(const OverlapSe
             const double nsym = (double)run;
             const double a1 = nsym > 0 ? (double)moments[0] / 1048576.0 / nsym : 0.0, a2 = nsym > 0 ? (double)moments[1] / 1048576.0 / nsym : 0.0;
             const double var = a2 - a1 * a1;
-            ctl[14] = __float_as_int(nsym > 0 && var > 0 ? (float)(a1 * a1 / var) : 1e30f);
+            ctl[CLK_CTL_SNR2] = __float_as_int(nsym > 0 && var > 0 ? (float)(a1 * a1 / var) : 1e30f);
         }
         long long ii = st.ii;
         if (ii > N) ii = N;

@@ -40,14 +40,14 @@
 
 namespace xrit {
 
-constexpr int RELAY_STAT = 8;        // counters per relay pass (RelayArgs::changed)
+// (RELAY_STAT counters per relay pass, RelayArgs::changed, by name: clock_ctl.h)
 constexpr int RELAY_WALKED = 1;      // start[]: the segment has been walked exactly from start[].s
 constexpr int RELAY_EXHAUSTED = 2;   // ends[]: the input ran out inside this segment (n_done symbols exist)
 constexpr int RELAY_DEAD = 4;        // the input ran out before this segment
 constexpr int RELAY_STUCK = 8;       // ends[]: a watchdog ended the walk (a ring or a mailbox never filled): the call fails
 constexpr int RELAY_APPROX = 16;     // start[]: the segment has been walked from start[].s by an approximate pass (apx > 0): not exactly
 constexpr int RELAY_REC = 32;        // start[]: ... which left the record of its (index, arm) guesses
-constexpr int RELAY_CLAIM_WORDS = 2048;   // one word per CU, indexed by (XCC_ID, SE_ID, SH_ID, CU_ID)
+// (RELAY_CLAIM_WORDS: one word per CU, indexed by (XCC_ID, SE_ID, SH_ID, CU_ID); clock_plan.h)
 
 struct RelaySeg {
     ClockState s;
@@ -74,7 +74,7 @@ struct RelayArgs {
     unsigned *changed;            // [RELAY_STAT * pass] segments whose start changed in that pass, [+1] steps, [+2] guess rounds,
                                   // [+3] largest move of a start against the walk before (float bits) or a watchdog mark,
                                   // [+4, +5] sum of the squared moves (64 bits, 2^-40 sample^2), [+6] moves summed
-    const int *ctl;               // clock control block: ctl[0] != 0 once the tiled hand-off has closed (null: do not ask)
+    const int *ctl;               // clock control block: ctl[CLK_CTL_DONE] != 0 once the tiled hand-off has closed (null: do not ask)
     unsigned long long *moments;  // [2] sum |s| and sum s^2 over the soft symbols of the first relay pass, units of 2^-20 (the
                                   // default configuration's look at the signal-to-noise ratio: ClockStage::finish)
     unsigned *rec;                // [G * cps * NS] the advance behind every symbol as last walked (one-wave walker: difference from the
@@ -157,11 +157,11 @@ __device__ unsigned relay_wdbg[RELAY_WDBG_PASSES * RELAY_WDBG_SEGS * RELAY_WDBG_
 #define RELAY_TICK(i) do { } while (0)
 #endif
 
-constexpr int RELAY_RX = 2048;       // sample ring (RING): about five steps of lead for the prefetching wave.  (Twice the size is as fast for the
-                                     // walk, but three workgroups then hold 135 KB of a CU's LDS and the front end of the next burst, started in
-                                     // front of the relay -- xrit_demod_prefetch_device --, cannot move in next to them: 2.65 against 2.33 ms per
-                                     // burst in the three-pass configuration; half the size again costs the walk 6 %.)
-constexpr int RELAY_XCH = 512;       // samples per refill (8 per lane)
+// RELAY_RX = 2048 (clock_plan.h): sample ring (RING): about five steps of lead for the prefetching wave.  (Twice the size is as fast for the
+// walk, but three workgroups then hold 135 KB of a CU's LDS and the front end of the next burst, started in
+// front of the relay -- xrit_demod_prefetch_device --, cannot move in next to them: 2.65 against 2.33 ms per
+// burst in the three-pass configuration; half the size again costs the walk 6 %.)
+// RELAY_XCH = 512 (clock_plan.h): samples per refill (8 per lane)
 constexpr int RELAY_ROUNDS = 4;      // guess rounds per step at most
 constexpr int RELAY_XMIR = 8;        // the ring's first samples again behind its end: a window never wraps
 constexpr int RELAY_GR = 1024;       // ring of first guesses (symbols), refilled RELAY_GCH at a time
@@ -184,9 +184,9 @@ constexpr int RELAY_REF_MARGIN = 1 << 20;     // a segment's reference index sit
 template <bool SYM, bool RING>
 __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs a, int pass, int span, int apx)
 {
-    if (a.ctl && !a.ctl[0]) return;                              // the tiled hand-off has not closed: nothing to refine yet
+    if (a.ctl && !a.ctl[CLK_CTL_DONE]) return;                              // the tiled hand-off has not closed: nothing to refine yet
                                                                  // (null: it never will -- pass budget used up -- go anyway)
-    if (pass > 0 && a.changed[RELAY_STAT * (pass - 1)] == 0) return;      // closed in an earlier pass
+    if (pass > 0 && a.changed[RELAY_STAT * (pass - 1) + RELAY_STAT_CHANGED] == 0) return;      // closed in an earlier pass
     __shared__ float table[(XR_MM_NSTEPS + 1) * XR_MM_NTAPS];
     __shared__ cf32 xr[RING ? RELAY_RX + RELAY_XMIR : 1];
     __shared__ unsigned gr[RING ? RELAY_GR : 1];
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs 
             e.flags = RELAY_DEAD;
             eout[s] = e;
             a.start[s] = e;
-            atomicAdd(&a.changed[RELAY_STAT * pass], 1u);
+            atomicAdd(&a.changed[RELAY_STAT * pass + RELAY_STAT_CHANGED], 1u);
         }
         return;
     }
@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs 
         int x_hi = x_lo, g_hi = 0;
         unsigned rounds = 0;
         while (!relay_ld(&sh_done)) {
-            if (++rounds > (1u << 24)) { if (lane == 0) a.changed[RELAY_STAT * pass + 3] = 0xc0000000u | (unsigned)s; break; }   // watchdog
+            if (++rounds > (1u << 24)) { if (lane == 0) a.changed[RELAY_STAT * pass + RELAY_STAT_MOVE_MAX] = 0xc0000000u | (unsigned)s; break; }   // watchdog
             const int pii = relay_ld(&sh_pos_ii);
             // (... and not beyond what a walker standing on the last sample can ask for: its block's span)
             const bool fx = x_hi + RELAY_XCH - RELAY_RX <= pii && (long long)x_hi <= nlast + span + 16;
@@ -316,17 +316,17 @@ __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs 
 
     // ---- the walker
     if (lane == 0) {
-        atomicAdd(&a.changed[RELAY_STAT * pass], 1u);
+        atomicAdd(&a.changed[RELAY_STAT * pass + RELAY_STAT_CHANGED], 1u);
         // how far this start is from the one the segment was last walked from (samples): what the automatic closure
         // looks at (ClockStage::finish).  Non-negative floats order like their bits; watchdog marks stay on top.
         if (pass > 0 && (prev.flags & (RELAY_WALKED | RELAY_APPROX))) {
             const float mv = fabsf(clock_tdiff(prev.s, T));
-            atomicMax(&a.changed[RELAY_STAT * pass + 3], __float_as_uint(mv));
+            atomicMax(&a.changed[RELAY_STAT * pass + RELAY_STAT_MOVE_MAX], __float_as_uint(mv));
             // (sum of squares in units of 2^-40 sample^2, moves beyond a sample count as one)
             const float m1 = fminf(mv, 1.0f);
-            atomicAdd(reinterpret_cast<unsigned long long *>(&a.changed[RELAY_STAT * pass + 4]),
+            atomicAdd(reinterpret_cast<unsigned long long *>(&a.changed[RELAY_STAT * pass + RELAY_STAT_MOVE_SQ]),
                       (unsigned long long)(m1 * m1 * 1099511627776.0f));
-            atomicAdd(&a.changed[RELAY_STAT * pass + 6], 1u);
+            atomicAdd(&a.changed[RELAY_STAT * pass + RELAY_STAT_MOVED], 1u);
         }
     }
     const bool quiet = a.sym_skip != 0 && s > 0;
@@ -372,14 +372,14 @@ __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs 
                 x_hi = relay_ld(&sh_xhi);
                 if (x_hi >= need_x) break;
                 __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 22)) { if (lane == 0) a.changed[RELAY_STAT * pass + 3] = 0x80000000u | (unsigned)s; stuck = true; break; }
+                if (++spins > (1 << 22)) { if (lane == 0) a.changed[RELAY_STAT * pass + RELAY_STAT_MOVE_MAX] = 0x80000000u | (unsigned)s; stuck = true; break; }
             }
 #pragma nounroll
             while (use_rec && !stuck && g_hi < need_g) {
                 g_hi = relay_ld(&sh_ghi);
                 if (g_hi >= need_g) break;
                 __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 22)) { if (lane == 0) a.changed[RELAY_STAT * pass + 3] = 0x90000000u | (unsigned)s; stuck = true; break; }
+                if (++spins > (1 << 22)) { if (lane == 0) a.changed[RELAY_STAT * pass + RELAY_STAT_MOVE_MAX] = 0x90000000u | (unsigned)s; stuck = true; break; }
             }
             if (stuck) break;
         }
@@ -553,8 +553,8 @@ __global__ void __launch_bounds__(RING ? 128 : 64) clock_relay_kernel(RelayArgs 
     if (lane == 0) {
         if (RING) relay_st(&sh_done, 1);
         if (RING && claim && sh_claim >= 0) atomicAnd(claim, ~(1u << sh_claim));      // (the next pass finds the CU's word clear)
-        atomicAdd(&a.changed[RELAY_STAT * pass + 1], steps);
-        atomicAdd(&a.changed[RELAY_STAT * pass + 2], rounds_total);
+        atomicAdd(&a.changed[RELAY_STAT * pass + RELAY_STAT_STEPS], steps);
+        atomicAdd(&a.changed[RELAY_STAT * pass + RELAY_STAT_ROUNDS], rounds_total);
         RelaySeg st0{};
         st0.s = T0;
         st0.n_done = n;                 // symbols the record holds
@@ -577,7 +577,7 @@ __global__ void __launch_bounds__(256) clock_relay_init_kernel(RelaySeg *start, 
     if (simd_claim && i < RELAY_CLAIM_WORDS) simd_claim[i] = 0u;
     if (i < G) start[i].flags = 0;
     if (i < RELAY_STAT * npass) changed[i] = 0u;
-    if (i == 0) { ctl[10] = 0; ctl[11] = 0; ctl[12] = 0; ctl[14] = 0; ctl[15] = 0; moments[0] = 0ull; moments[1] = 0ull; }
+    if (i == 0) { ctl[CLK_CTL_RELAY_PASSES] = 0; ctl[CLK_CTL_RELAY_CLOSED] = 0; ctl[CLK_CTL_RELAY_SHIFT_SQ] = 0; ctl[CLK_CTL_SNR2] = 0; ctl[CLK_CTL_STUCK] = 0; moments[0] = 0ull; moments[1] = 0ull; }
 }
 
 }  // namespace xrit

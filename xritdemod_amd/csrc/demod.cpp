@@ -45,6 +45,16 @@ int select_device(int device)
 
 using namespace xrit;
 
+// what a front end leaves for the loops behind it
+struct SliceIO {
+    size_t length = 0;          // circuit-rate samples
+    const float2 *rrc = nullptr;
+    bool stat_ready = false;
+    int set = 0;                // which set of front-end buffers
+    const float *agc_flag = nullptr;    // the AGC guard flag of THIS front end (the stage's slot moves on with the next)
+    bool exact = false;         // this call's front end is the bit-exact one (cfg.front_exact = 2, or 0 on a call below the big-burst size)
+};
+
 struct xrit_demod {
     xrit_demod_config cfg{};
     int device = 0;
@@ -78,9 +88,8 @@ struct xrit_demod {
     bool costas_idle = false;   // the current call's Costas loop was finished before its clock recovery began: the stage is free
     int last_fe_set = -1;       // set of the front end that ran last (its event orders the next one behind it)
     struct Prefetched {
-        const void *samples = nullptr; size_t n = 0; int type = 0; int set = 0;
-        size_t length = 0; const float2 *rrc = nullptr; bool stat_ready = false; const float *agc_flag = nullptr;
-        bool exact = false;             // its front end was the bit-exact one (front_exact_call)
+        const void *samples = nullptr; size_t n = 0; int type = 0;
+        SliceIO io;                     // what its front end left (launch_prefetched)
         bool costas_begun = false;      // the Costas loop of this input has been started too (on stream2, behind its front end)
         float2 *slot = nullptr;         // ... writing here (the clock recovery's next input buffer)
         // round 5, bursts whose clock recovery walks overlapping blocks (clock_overlap.h): everything up to the walkers runs ahead
@@ -454,15 +463,6 @@ static int keep_stage(xrit_demod *d, int idx, const void *src, size_t n, hipStre
 // front_end(): ingest conversion, decimator, AGC, RRC (demodulator.cpp:54-74,136-149) into buffer set `set`;
 // loops(): Costas and clock recovery (:152-157) on what front_end() left.  Split so that the front end of the
 // next slice can run on a second stream while the feedback loops of this one iterate.
-struct SliceIO {
-    size_t length = 0;          // circuit-rate samples
-    const float2 *rrc = nullptr;
-    bool stat_ready = false;
-    int set = 0;                // which set of front-end buffers
-    const float *agc_flag = nullptr;    // the AGC guard flag of THIS front end (the stage's slot moves on with the next)
-    bool exact = false;         // this call's front end is the bit-exact one (cfg.front_exact = 2, or 0 on a call below the big-burst size)
-};
-
 // Which front end a call of n input samples takes.  cfg.front_exact = 2: the bit-exact one, always; 0 (default, round 6): the
 // bit-exact one for calls below the big-burst size -- the reference's own chunk sizes (32 Ki .. 512 Ki samples) and everything
 // up to a million symbols, where a call is launch latency and not throughput: the soft symbols of a call of up to 74 k symbols
@@ -565,17 +565,14 @@ static int launch_prefetched(xrit_demod *d, xrit_demod::Prefetched &f, hipEvent_
     if (d->last_fe_set >= 0) XR_HIP(hipStreamWaitEvent(d->stream2, d->ev_fe[d->last_fe_set], 0));
     const int set = d->next_set;
     d->next_set ^= 1;
-    SliceIO io;
     Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
     // (the filters' waves in front of the walkers at issue -- where the walkers' latency is hidden: bursts that walk overlapping blocks)
     d->dec.prio = d->rrc.prio = ov_call(d, f.n) ? 1 : 0;
-    int rc = front_end(d, f.samples, f.n, f.type, set, d->stream2, prof, &io);
+    int rc = front_end(d, f.samples, f.n, f.type, set, d->stream2, prof, &f.io);
     d->dec.prio = d->rrc.prio = 0;
     if (rc != XRIT_OK) { d->poisoned = true; return rc; }
     XR_HIP(hipEventRecord(d->ev_fe[set], d->stream2));
     d->last_fe_set = set;
-    f.set = set;
-    f.length = io.length; f.rrc = io.rrc; f.stat_ready = io.stat_ready; f.agc_flag = io.agc_flag; f.exact = io.exact;
     f.launched = true;
     return XRIT_OK;
 }
@@ -614,9 +611,7 @@ static void set_relay_hook(xrit_demod *d, hipStream_t s)
             XR_TRY(launch_prefetched(d, d->pf[0], d->ev_relay));
             if (d->costas_idle) {
                 xrit_demod::Prefetched &f = d->pf[0];
-                SliceIO io;
-                io.length = f.length; io.rrc = f.rrc; io.stat_ready = f.stat_ready; io.set = f.set; io.agc_flag = f.agc_flag; io.exact = f.exact;
-                int rc = costas_enqueue(d, io, d->stream2, d->prof.enabled ? &d->prof : nullptr, &f.slot);
+                int rc = costas_enqueue(d, f.io, d->stream2, d->prof.enabled ? &d->prof : nullptr, &f.slot);
                 if (rc != XRIT_OK) { d->poisoned = true; return rc; }
                 XR_HIP(hipEventRecord(d->ev_costas, d->stream2));
                 f.costas_begun = true;
@@ -636,6 +631,51 @@ static void costas_note(xrit_demod *d)
     d->costas_seen.walked = d->costas.job.rescued && d->costas.walked;
 }
 
+// the host looks at the Costas loop's stop test (and continues its passes on s where the batch did not close) and notes
+// what the loop and the AGC's guard reported for this call
+static int costas_look(xrit_demod *d, size_t length, hipStream_t s, Profiler *prof, bool *redone)
+{
+    if (length && d->agc.requested_flag() == 2.0f) d->agc_fallback_seen = true;
+    const int rc = d->costas.finish(s, prof, redone);
+    if (rc == XRIT_OK) costas_note(d);
+    return rc;
+}
+
+// a process call takes the oldest registered input, and no other
+static int pf_check_front(xrit_demod *d, const void *d_samples, size_t n, int type)
+{
+    if (d->pf[0].samples == d_samples && d->pf[0].n == n && d->pf[0].type == type) return XRIT_OK;
+    set_error("process calls must take the prefetched inputs in the order they were prefetched");
+    d->poisoned = true;
+    return XRIT_E_INVALID;
+}
+static void pf_pop(xrit_demod *d)
+{
+    for (int i = 1; i < d->pf_count; ++i) d->pf[i - 1] = d->pf[i];
+    --d->pf_count;
+}
+
+// a finished call's statistics, from what the stages and the call's look at its Costas loop hold
+static void fill_stats(xrit_demod *d, size_t n, size_t length, size_t nsym, int relay_segments)
+{
+    d->stage_n[4] = nsym;
+    d->stats.samples_in = n;
+    d->stats.circuit_samples = length;
+    d->stats.symbols_out = nsym;
+    d->stats.costas_passes = d->costas_seen.passes;
+    d->stats.clock_passes = d->clock.passes;
+    d->stats.costas_unconverged = d->costas_seen.unconverged;
+    d->stats.clock_unconverged = d->clock.unconverged;
+    d->stats.costas_max_residual = d->costas_seen.max_residual;
+    d->stats.clock_max_residual = d->clock.max_residual;
+    d->stats.agc_serial_fallback = d->agc_fallback_seen;
+    d->stats.clock_open_large = d->clock.large_open;
+    d->stats.costas_serial_walk = d->costas_seen.walked ? 1 : 0;
+    d->stats.clock_relay_passes = d->clock.relay_passes;
+    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
+    d->stats.clock_relay_segments = relay_segments;
+}
+
 static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, size_t *nsym, hipStream_t s, Profiler *prof,
                  bool costas_done = false, float2 *slot_done = nullptr)
 {
@@ -651,10 +691,8 @@ static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, si
         // call on that is how every Costas loop of the stream runs and the extra wait is gone.
         XR_HIP(hipEventRecord(d->ev_costas, s));
         XR_HIP(hipEventSynchronize(d->ev_costas));
-        if (length && d->agc.requested_flag() == 2.0f) d->agc_fallback_seen = true;
         bool redone = false;
-        XR_TRY(d->costas.finish(s, prof, &redone));
-        costas_note(d);
+        XR_TRY(costas_look(d, length, s, prof, &redone));
         if (redone) d->clock.om_scanned = false;     // (the final pass ran again: the statistic is new, begin() unwraps it itself)
         costas_done = true;
     }
@@ -671,10 +709,8 @@ static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, si
     XR_TRY(rc_begin);
     XR_HIP(hipStreamSynchronize(s));
     if (!costas_done) {
-        if (length && d->agc.requested_flag() == 2.0f) d->agc_fallback_seen = true;
         bool redone = false;
-        XR_TRY(d->costas.finish(s, prof, &redone));
-        costas_note(d);
+        XR_TRY(costas_look(d, length, s, prof, &redone));
         if (redone) {
             // the Costas output was rewritten after more passes: the clock recovery starts over on it
             const int L = d->costas.L;
@@ -722,7 +758,7 @@ static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
         if (!f.launched) break;
         if (f.costas_begun && !f.costas_finished) {
             if (hipEventQuery(d->ev_costas) != hipSuccess) { costas_busy = true; continue; }
-            if (f.length && d->agc.requested_flag() == 2.0f) f.agc_fallback = true;
+            if (f.io.length && d->agc.requested_flag() == 2.0f) f.agc_fallback = true;
             bool redone = false;
             int rc = d->costas.finish(f.c_stream ? f.c_stream : d->stream2, prof, &redone);
             if (rc != XRIT_OK) { d->poisoned = true; return rc; }
@@ -739,8 +775,6 @@ static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
             if (progress) *progress = true;
         }
         if (!f.costas_begun && !costas_busy) {
-            SliceIO io;
-            io.length = f.length; io.rrc = f.rrc; io.stat_ready = f.stat_ready; io.set = f.set; io.agc_flag = f.agc_flag; io.exact = f.exact;
             // (on a stream of its own behind this input's front end: the front end of the input behind it runs beside this loop)
             // (on the front ends' stream, behind this input's: measured with every stream on a hardware queue of its own
             // -- GPU_MAX_HW_QUEUES=8 -- a Costas stream beside the front ends' costs 10 %, 2.05 against 1.85 ms per C2 burst: the
@@ -754,11 +788,11 @@ static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
             // (round 6, cfg.front_exact = 2: the exact AGC chains and the exact Costas walkers are a wave per SIMD or less for
             // milliseconds -- latency, not work --, so the Costas loop of burst b runs on a stream of its own beside the front end
             // of burst b + 1 instead of in front of it)
-            f.costas_stream = d->stream_c ? 2 : (f.length < d->costas_own_stream_below ? 1 : 0);
+            f.costas_stream = d->stream_c ? 2 : (f.io.length < d->costas_own_stream_below ? 1 : 0);
             hipStream_t sc = f.costas_stream == 2 ? d->stream_c : f.costas_stream ? d->stream3[(d->clock.ov_serial + 1) % XRIT_WALK_STREAMS] : d->stream2;
             f.c_stream = sc;
-            if (f.costas_stream) XR_HIP(hipStreamWaitEvent(sc, d->ev_fe[f.set], 0));
-            int rc = costas_enqueue(d, io, sc, prof, &f.slot);
+            if (f.costas_stream) XR_HIP(hipStreamWaitEvent(sc, d->ev_fe[f.io.set], 0));
+            int rc = costas_enqueue(d, f.io, sc, prof, &f.slot);
             if (rc != XRIT_OK) { d->poisoned = true; return rc; }
             XR_HIP(hipEventRecord(d->ev_costas, sc));
             f.costas_begun = true;
@@ -786,11 +820,7 @@ static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int t
 {
     // the call's own input goes through the same queue: registered now if it was not registered ahead
     if (d->pf_count > 0) {
-        if (d->pf[0].samples != d_samples || d->pf[0].n != n || d->pf[0].type != type) {
-            set_error("process calls must take the prefetched inputs in the order they were prefetched");
-            d->poisoned = true;
-            return XRIT_E_INVALID;
-        }
+        XR_TRY(pf_check_front(d, d_samples, n, type));
     } else {
         XR_HIP(hipEventRecord(d->ev_ready, s));
         xrit_demod::Prefetched &f = d->pf[0];
@@ -816,7 +846,7 @@ static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int t
     // joints, output and result behind this call's walkers (started here if they did not run ahead), on the call's stream.
     // (the host has SEEN the end of everything stream2 did for this input -- the Costas loop's event, a continued loop's
     // synchronise --, so s needs no event of stream2's; the finalize kernels wait for the walkers' event)
-    rc = d->clock.begin(f0.length, d_soft, nullptr, cap, s, prof);
+    rc = d->clock.begin(f0.io.length, d_soft, nullptr, cap, s, prof);
     if (rc != XRIT_OK) return fail(rc);
     if (hipEventRecord(d->ev_done, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(XRIT_E_HIP); }
     if ((rc = ov_service(d, nullptr)) != XRIT_OK) return fail(rc);
@@ -832,27 +862,11 @@ static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int t
     }
     size_t nsym = 0;
     rc = d->clock.finish(&nsym, s, prof);
-    const size_t length = f0.length;
-    for (int i = 1; i < d->pf_count; ++i) d->pf[i - 1] = d->pf[i];
-    --d->pf_count;
+    const size_t length = f0.io.length;
+    pf_pop(d);
     if (rc != XRIT_OK) return fail(rc);
     if (prof) d->prof.collect();
-    d->stage_n[4] = nsym;
-    d->stats.samples_in = n;
-    d->stats.circuit_samples = length;
-    d->stats.symbols_out = nsym;
-    d->stats.costas_passes = d->costas_seen.passes;
-    d->stats.clock_passes = d->clock.passes;
-    d->stats.costas_unconverged = d->costas_seen.unconverged;
-    d->stats.clock_unconverged = d->clock.unconverged;
-    d->stats.costas_max_residual = d->costas_seen.max_residual;
-    d->stats.clock_max_residual = d->clock.max_residual;
-    d->stats.agc_serial_fallback = d->agc_fallback_seen;
-    d->stats.clock_open_large = d->clock.large_open;
-    d->stats.costas_serial_walk = d->costas_seen.walked ? 1 : 0;
-    d->stats.clock_relay_passes = d->clock.relay_passes;
-    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
-    d->stats.clock_relay_segments = d->clock.relay_segments;
+    fill_stats(d, n, length, nsym, d->clock.relay_segments);       // (the walkers count as the call's segments)
     *n_out = nsym;
     if (d->cfg.strict && d->costas_seen.unconverged) {
         set_error("Costas hand-off did not close: %u boundaries above tolerance", d->costas_seen.unconverged);
@@ -897,17 +911,12 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
     bool costas_ahead = false;
     if (d->pf_count > 0) {
         // the front end of this call ran ahead (xrit_demod_prefetch_device): the loops wait for it, nothing else
-        if (d->pf[0].samples != d_samples || d->pf[0].n != n || d->pf[0].type != type) {
-            set_error("process calls must take the prefetched inputs in the order they were prefetched");
-            d->poisoned = true;
-            return XRIT_E_INVALID;
-        }
+        XR_TRY(pf_check_front(d, d_samples, n, type));
         // (registered only: the call before had no relay phase to put it in front of)
         if (!d->pf[0].launched) XR_TRY(launch_prefetched(d, d->pf[0], nullptr));
         const xrit_demod::Prefetched f = d->pf[0];
-        for (int i = 1; i < d->pf_count; ++i) d->pf[i - 1] = d->pf[i];
-        --d->pf_count;
-        io.length = f.length; io.rrc = f.rrc; io.stat_ready = f.stat_ready; io.set = f.set; io.agc_flag = f.agc_flag; io.exact = f.exact;
+        pf_pop(d);
+        io = f.io;
         if (f.costas_begun) {
             // its Costas loop ran ahead as well (under the relay of the call before): the host looks at its stop test now
             // (continuing the passes on stream2 in the rare case the batch did not close), the clock recovery follows on s.
@@ -918,15 +927,13 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
             // tail + guess + relay kernels, of which the device spends 20 in the first two).
             // (from here on the registered input has been consumed: a failure poisons the handle below, no early return)
             if (hipEventSynchronize(d->ev_costas) != hipSuccess) { set_error("hipEventSynchronize failed"); rc = XRIT_E_HIP; }
-            if (io.length && d->agc.requested_flag() == 2.0f) d->agc_fallback_seen = true;
             bool redone = false;
-            if (rc == XRIT_OK) rc = d->costas.finish(d->stream2, prof, &redone);
-            costas_note(d);
+            if (rc == XRIT_OK) rc = costas_look(d, io.length, d->stream2, prof, &redone);
             if (redone) d->clock.om_scanned = false;
             if (rc == XRIT_OK) rc = loops(d, io, d_soft, cap, &total_sym, s, prof, true, f.slot);
             costas_ahead = true;
         } else {
-            if (hipStreamWaitEvent(s, d->ev_fe[f.set], 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); rc = XRIT_E_HIP; }
+            if (hipStreamWaitEvent(s, d->ev_fe[f.io.set], 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); rc = XRIT_E_HIP; }
         }
     } else {
         const int set = d->next_set;
@@ -944,26 +951,9 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
         return rc;
     }
     total_len = io.length;
-    const int worst_cp = d->costas_seen.passes, worst_kp = d->clock.passes;
-    const unsigned unc_c = d->costas_seen.unconverged, unc_k = d->clock.unconverged, large_k = d->clock.large_open;
-    const float res_c = d->costas_seen.max_residual, res_k = d->clock.max_residual;
+    const unsigned unc_c = d->costas_seen.unconverged, large_k = d->clock.large_open;
     if (prof) d->prof.collect();
-    d->stage_n[4] = total_sym;
-    d->stats.samples_in = n;
-    d->stats.circuit_samples = total_len;
-    d->stats.symbols_out = total_sym;
-    d->stats.costas_passes = worst_cp;
-    d->stats.clock_passes = worst_kp;
-    d->stats.costas_unconverged = unc_c;
-    d->stats.clock_unconverged = unc_k;
-    d->stats.costas_max_residual = res_c;
-    d->stats.clock_max_residual = res_k;
-    d->stats.agc_serial_fallback = d->agc_fallback_seen;
-    d->stats.clock_open_large = large_k;
-    d->stats.costas_serial_walk = d->costas_seen.walked ? 1 : 0;
-    d->stats.clock_relay_passes = d->clock.relay_passes;
-    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
-    d->stats.clock_relay_segments = d->clock.job.relay ? d->clock.relay_segments : 0;
+    fill_stats(d, n, total_len, total_sym, d->clock.job.relay ? d->clock.relay_segments : 0);
     *n_out = total_sym;
     if (d->cfg.strict && unc_c) {
         set_error("Costas hand-off did not close: %u boundaries above tolerance", unc_c);

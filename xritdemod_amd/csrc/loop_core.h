@@ -10,6 +10,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "clock_plan.h"
+
 #if defined(__HIPCC__)
 #define XR_HD __host__ __device__ __forceinline__
 #else
@@ -166,11 +168,7 @@ XR_HD float costas_prewrap(float phase)
 }
 
 // ---------------------------------------------------- Mueller & Mueller ----
-#define XR_MM_NTAPS  8
-#define XR_MM_NSTEPS 128
-#define XR_MM_FUDGE  16
-
-struct ClockPar { float omega_mid, omega_lim, gain_omega, gain_mu; };
+// (XR_MM_NTAPS, XR_MM_NSTEPS, XR_MM_FUDGE and ClockPar: clock_plan.h, which the host's plan shares)
 
 // state between symbols.  ii is the absolute read index into the call's
 // [carry | new] sample buffer.

@@ -44,6 +44,10 @@ constexpr int NEWTON_BLOCK = 256;
 constexpr int NEWTON_IPT = 4;
 constexpr int NEWTON_TILE = NEWTON_BLOCK * NEWTON_IPT;
 constexpr int NEWTON_MAX_BLOCKS = 4096;
+// the control words the solve shares with its caller's stage (the clock recovery's block names them all, clock_ctl.h)
+constexpr int NEWTON_CTL_DONE = 0;       // the hand-off has closed: every later pass and solve of the call is a no-op
+constexpr int NEWTON_CTL_GATED = 5;      // the trust gate scan runs (residuals are still large)
+constexpr int NEWTON_CTL_TAKEOVER = 8;   // the wave-aligned path met a boundary outside the trust region
 
 struct AffMap { float a11, a12, a21, a22, b1, b2; int aux; };
 
@@ -141,7 +145,7 @@ __device__ __forceinline__ void newton_fetch(const P &p, long long i0, long long
 template <typename P>
 __global__ void __launch_bounds__(NEWTON_BLOCK) newton_reduce_kernel(P p, long long n, AffMap *agg0, const int *ctl)
 {
-    if (ctl[0]) return;
+    if (ctl[NEWTON_CTL_DONE]) return;
     __shared__ AffMap buf[NEWTON_BLOCK];
     const long long i0 = (long long)blockIdx.x * NEWTON_TILE + (long long)threadIdx.x * NEWTON_IPT;
     typename P::Elem el[NEWTON_IPT];
@@ -158,7 +162,7 @@ template <typename P>
 __global__ void __launch_bounds__(NEWTON_BLOCK) newton_gate_kernel(P p, long long n, const AffMap *agg0, AffMap *agg1,
                                                                    float2 *dlin, const int *ctl)
 {
-    if (ctl[0] || !ctl[5]) return;
+    if (ctl[NEWTON_CTL_DONE] || !ctl[NEWTON_CTL_GATED]) return;
     __shared__ AffMap buf[NEWTON_BLOCK];
     const long long i0 = (long long)blockIdx.x * NEWTON_TILE + (long long)threadIdx.x * NEWTON_IPT;
     typename P::Elem el[NEWTON_IPT];
@@ -196,10 +200,10 @@ __global__ void __launch_bounds__(NEWTON_BLOCK) newton_apply_kernel(P p, long lo
                                                                     const AffMap *agg1, const float2 *dlin, int *ctl,
                                                                     NewtonStat *slots)
 {
-    if (ctl[0]) return;
+    if (ctl[NEWTON_CTL_DONE]) return;
     __shared__ AffMap buf[NEWTON_BLOCK];
     const long long i0 = (long long)blockIdx.x * NEWTON_TILE + (long long)threadIdx.x * NEWTON_IPT;
-    const bool gated = ctl[5] != 0;
+    const bool gated = ctl[NEWTON_CTL_GATED] != 0;
     typename P::Elem el[NEWTON_IPT];
     newton_fetch(p, i0, n, el);
     float2 dl[NEWTON_IPT];
@@ -306,11 +310,11 @@ constexpr int NEWTON_SMALL_MAX = NEWTON_SMALL_BLOCK * NEWTON_IPT;
 template <typename P>
 __global__ void __launch_bounds__(NEWTON_SMALL_BLOCK) newton_small_kernel(P p, long long n, int *ctl)
 {
-    if (ctl[0]) return;
+    if (ctl[NEWTON_CTL_DONE]) return;
     __shared__ AffMap buf[NEWTON_SMALL_BLOCK];
     __shared__ NewtonStat wst[NEWTON_SMALL_BLOCK / 64];
     const long long i0 = (long long)threadIdx.x * NEWTON_IPT;
-    const bool gated = ctl[5] != 0;
+    const bool gated = ctl[NEWTON_CTL_GATED] != 0;
     typename P::Elem el[NEWTON_IPT];
     newton_fetch(p, i0, n, el);
     AffMap e[NEWTON_IPT];
@@ -393,7 +397,6 @@ __global__ void __launch_bounds__(NEWTON_SMALL_BLOCK) newton_small_kernel(P p, l
 // wave that finds a boundary outside the trust region raises ctl[NEWTON_CTL_TAKEOVER] and the host continues with
 // the gated three-launch solve (acquisition, cold starts: the calls that need a host round trip per batch anyway).
 // Boundary k sits between chains k and k + 1; wave w covers boundaries [64 w, 64 w + 64).
-constexpr int NEWTON_CTL_TAKEOVER = 8;   // control word: the wave-aligned path met a boundary outside the trust region
 constexpr int NEWTON_WAVES_BLOCK = 1024;
 constexpr int NEWTON_WAVES_PER_BLOCK = NEWTON_WAVES_BLOCK / 64;
 
@@ -459,7 +462,7 @@ __global__ void __launch_bounds__(NEWTON_WAVES_BLOCK) newton_wave_prefix_kernel(
 {
     __shared__ AffMap buf[NEWTON_WAVES_BLOCK];
     __shared__ int skip;
-    if (threadIdx.x == 0) skip = ctl[0] || ctl[NEWTON_CTL_TAKEOVER];
+    if (threadIdx.x == 0) skip = ctl[NEWTON_CTL_DONE] || ctl[NEWTON_CTL_TAKEOVER];
     __syncthreads();
     if (skip) return;
     const int run = (nw + NEWTON_WAVES_BLOCK - 1) / NEWTON_WAVES_BLOCK;
@@ -490,7 +493,7 @@ __global__ void __launch_bounds__(NEWTON_WAVES_BLOCK) newton_apply_waves_kernel(
     // of one workgroup that disagree about it would leave the block scan below with missing inputs.  (A workgroup that
     // saw the flag too late still takes part in the count of finished workgroups; the host goes over to the gated
     // solve either way.)
-    if (threadIdx.x == 0) skip = ctl[0] || ctl[NEWTON_CTL_TAKEOVER];
+    if (threadIdx.x == 0) skip = ctl[NEWTON_CTL_DONE] || ctl[NEWTON_CTL_TAKEOVER];
     __syncthreads();
     if (skip) return;
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
