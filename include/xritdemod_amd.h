@@ -836,6 +836,105 @@ int xrit_rice_decode(const uint8_t *bytes, size_t n_bytes, const void *desc, siz
                      int bits_per_sample, int block, int samples, void *out, uint8_t *status, int device);
 
 /* ------------------------------------------------------------------------
+ * Image lines: every Rice-coded line of every image file in one files call,
+ * decoded in one pass (tests/image_spec.py is the serial
+ * statement).  Input: a files call's bytes, pieces, records and summary; the
+ * true counts are read from the summary on the device.
+ *  - key = (vcid, apid); per key, carried across calls until reset: whether a
+ *    rice-coded image is open, its key_serial, its lines and faults so far.
+ *  - a record with BEGINS is rice iff the link rule of section 16 holds
+ *    (header_state 2, file_type 0, compression 1, bits_per_pixel 1 .. 16,
+ *    columns >= 1, pixels_per_block 8 / 16 / 32 / 64, header_length == the first
+ *    piece's length); its lines are its pieces behind the first.  A record
+ *    without BEGINS is rice iff the key's state is open with the record's
+ *    key_serial (and the record's parameters are in those ranges); its lines are
+ *    all its pieces.  A line is one piece: row = index_in_file - 1, decoded as
+ *    xrit_rice_decode does with (bits_per_pixel, pixels_per_block, columns) of
+ *    the record, status 0 / 1 / 2 as there.  The record's `lines` field is never
+ *    used to cut; lines behind a fault are still decoded.
+ *  - after the call the key's state is that of its last record in the call: open
+ *    iff it is rice and carries neither ENDS nor ABORTED.
+ *  - outputs in piece order: the samples (uint8 for bits <= 8, else little-endian
+ *    uint16) back to back, every line padded with zeros to a multiple of 4
+ *    bytes; one xrit_image_line per line; one xrit_image_file per files record
+ *    (same index; all zero where the record is not rice).
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_images xrit_images;
+typedef struct xrit_image_line {
+    uint64_t offset;                 /* of the line's first sample in the call's image bytes (a multiple of 4) */
+    uint32_t length;                 /* samples * (1 or 2) bytes, unpadded */
+    uint32_t row;                    /* in its image: index_in_file - 1 */
+    uint32_t file;                   /* index into the call's records */
+    uint32_t piece;                  /* index into the call's pieces */
+    uint16_t samples;                /* the record's columns */
+    uint8_t  bits;                   /* the record's bits_per_pixel */
+    uint8_t  status;                 /* 0; 1: a fault, the blocks in front of it kept, the rest 0; 2: the piece lies outside the bytes, all 0 */
+    uint8_t  reserved[4];
+} xrit_image_line;                   /* 32 bytes; begins {offset, length} like xrit_packet and xrit_file_piece */
+typedef struct xrit_image_file {
+    uint64_t offset, length;         /* the record's lines of this call in the image bytes: contiguous, padded lines */
+    uint32_t first_line, n_lines;    /* ... and among the call's xrit_image_line */
+    uint32_t first_row;              /* the row of the first of them (with no line: the image's lines before this call) */
+    uint32_t faults;                 /* lines of this call with status != 0 */
+    uint32_t lines_total, faults_total;  /* of the image after this call */
+    uint16_t columns;
+    uint8_t  bits;
+    uint8_t  rice;                   /* 1: the record is a rice-coded image's; 0: every field is 0 */
+    uint8_t  reserved[4];
+} xrit_image_file;                   /* 48 bytes */
+typedef struct xrit_images_counters {
+    uint64_t images_begun, images_completed, images_aborted, total_lines, total_faults, total_bytes;
+} xrit_images_counters;              /* 48 bytes */
+typedef struct xrit_images_summary {
+    uint64_t lines, bytes, images;   /* of this call: lines, padded bytes, rice records -- the true counts, whatever the capacities */
+    uint64_t images_begun, images_completed, images_aborted, total_lines, total_faults, total_bytes;   /* the handle's counters after it */
+    uint32_t overflow;               /* 0; 1: a capacity too small; 2: the files summary has overflow != 0 or counts beyond the host's bounds */
+    uint32_t reserved;
+} xrit_images_summary;               /* 80 bytes */
+/* what one key carries (xrit_images_key) */
+typedef struct xrit_image_key {
+    uint32_t key_serial, lines, faults;
+    uint8_t  open;
+    uint8_t  reserved[3];
+} xrit_image_key;                    /* 16 bytes */
+#define XRIT_IMAGES_MAX_PIECES ((size_t)1 << 24)            /* bounds on a call's pieces ... */
+#define XRIT_IMAGES_MAX_FILES  ((size_t)1 << 25)            /* ... and records */
+/* a call on p pieces emits at most p lines; a line is at most 65535 samples of 2 bytes, padded: 131072 bytes */
+#define XRIT_IMAGES_MAX_LINES(p) ((size_t)(p))
+#define XRIT_IMAGES_MAX_BYTES(p) ((size_t)131072 * (p))
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_images_create(xrit_images **im, int device);
+int xrit_images_destroy(xrit_images *im);
+/* every key closed, counters zero; waits for the handle's last call */
+int xrit_images_reset(xrit_images *im);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_files_process_device, whose d_bytes (n_bytes: its max_bytes), d_pieces (max_pieces_in: its max_pieces),
+ * d_files (max_files_in: its max_files) and d_summary it takes.  If that summary has overflow != 0 or counts beyond
+ * these bounds, only d_summary is written, with overflow = 2, and the state is unchanged.  d_image_files has
+ * max_files_in entries.  d_out, d_pieces, d_files, d_lines, d_image_files and both summaries 8-byte aligned.  Capacity:
+ * line k is written iff k < max_lines, its samples iff offset + padded length <= max_bytes; the summary carries the
+ * true counts and overflow = 1, and the handle's state advances as if everything had fitted.  Calls on one handle
+ * share its state and scratch: keep them in order. */
+int xrit_images_process_device(xrit_images *im, const uint8_t *d_bytes, size_t n_bytes, const xrit_file_piece *d_pieces,
+                               size_t max_pieces_in, const xrit_file_record *d_files, size_t max_files_in,
+                               const xrit_files_summary *d_files_summary, uint8_t *d_out, size_t max_bytes,
+                               xrit_image_line *d_lines, size_t max_lines, xrit_image_file *d_image_files,
+                               xrit_images_summary *d_summary, void *stream);
+/* host buffers (one upload, one download): what xrit_files_process returned; n_pieces_in and n_files_in are the lengths
+ * of the arrays handed over (the device's bounds).  image_files has n_files_in entries.  XRIT_E_CAPACITY when a
+ * capacity was too small: the prefix that fits is written, the summary is the true one, the state has advanced.
+ * XRIT_E_ARG with summary->overflow = 2 when the call was refused (nothing else written). */
+int xrit_images_process(xrit_images *im, const uint8_t *bytes, size_t n_bytes, const xrit_file_piece *pieces, size_t n_pieces_in,
+                        const xrit_file_record *files, size_t n_files_in, const xrit_files_summary *files_summary,
+                        uint8_t *out, size_t max_bytes, xrit_image_line *lines, size_t max_lines, xrit_image_file *image_files,
+                        xrit_images_summary *summary);
+/* the counters after the handle's last call (waits for it) */
+int xrit_images_stats(xrit_images *im, xrit_images_counters *out);
+/* what key (vcid < 64, apid < 2048) carries after the handle's last call (waits for it) */
+int xrit_images_key(xrit_images *im, unsigned vcid, unsigned apid, xrit_image_key *out);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

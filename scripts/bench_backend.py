@@ -22,9 +22,14 @@ lock     xrit_lock_push_device (the frame lock: framer and decoder as the refere
          framer leg's two streams, at recheck 4 and at recheck 1, next to xrit_framer_push_device +
          xrit_decoder_decode_device queued on one stream: ms per call, rounds, sensitive chunks, chunks kept and missed in
          the short range.
-all      the seven, in this order.
+images   xrit_images_process_device on one files call that holds --images rice-coded images of mixed (bits, block, columns,
+         rows) and half as many files that are no images, next to what it replaces in the same process on the same
+         device-resident bytes: one xrit_rice_decode_device per rice record (the records read back beforehand, which the
+         loop needs and the stage does not; that read-back and its synchronisation are outside the timed region).  Then
+         packets + files on one stream with and without the stage behind them.
+all      the seven in front of images, in this order (images is asked for by name).
 
-    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,lock,all} [--frames N] [--reps R] [--warmup W]
+    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,lock,images,all} [--frames N] [--images I] [--reps R] [--warmup W]
                                     [--lines L] [--samples S] [--no-cpu]"""
 import argparse
 import json
@@ -43,7 +48,8 @@ import packet_spec as ps
 import rice_spec as rs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "lock", "all"])
+ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "lock", "images", "all"])
+ap.add_argument("--images", type=int, default=96)
 ap.add_argument("--frames", type=int, default=1 << 16)
 ap.add_argument("--reps", type=int, default=None, help="timed calls per case (decode: 5, the others: 20)")
 ap.add_argument("--warmup", type=int, default=None, help="calls before them (decode: 2, the others: 3)")
@@ -427,6 +433,105 @@ def bench_lock():
         h.close()
 
 
+def bench_images():
+    import file_spec as fs
+    import image_spec as isp
+    rng = np.random.default_rng(3)
+    keys = [(v, a) for v in (0, 5, 31) for a in (10, 11, 700, 2046)]
+    items, sources, serial = [], {}, {}
+    order = ["image"] * args.images + ["other"] * (args.images // 2)
+    rng.shuffle(order)
+    for what in order:
+        key = keys[int(rng.integers(0, len(keys)))]
+        k = serial.get(key, 0)
+        serial[key] = k + 1
+        if what == "image":
+            n, J = int(rng.choice([4, 8, 8, 10, 12, 16])), int(rng.choice(rs.BLOCK_SIZES))
+            img, data, cuts = isp.image_file(rng, n, J, int(rng.integers(256, 2049)), int(rng.integers(16, 49)))
+            sources[key + (k,)] = img
+            items.append((key, data, cuts, 8190))
+        else:
+            items.append((key, fs.random_file(rng, 20000), None, int(rng.choice([1000, 8190]))))
+    stream = isp.stream_of(rng, items)
+    by_vc = {}
+    for v, pkt, _ in stream:
+        by_vc.setdefault(v, []).append(pkt)
+    vcdu, offsets = ps.group({v: s.rows for v, s in ps.build_streams([(v, p) for v, p, _ in stream], rng, fill=0.0, idle=0.0).items()})
+    rows = len(vcdu)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    d_vcdu, d_off = up(vcdu), up(offsets)
+    mb, mp = xa.packets_max_bytes(rows), len(stream) + 64 * 3
+    p_bytes, p_desc, p_off, p_sum = u8(mb), u8(mp * 32), u8(65 * 4), u8(xa.PACKETS_SUMMARY_DTYPE.itemsize)
+    f_bytes, f_pieces, f_recs, f_sum = u8(mb), u8(mp * 32), u8(2 * mp * 80), u8(xa.FILES_SUMMARY_DTYPE.itemsize)
+    pa, fa, im = xa.PacketAssembler(), xa.FileAssembler(), xa.ImageDecoder()
+
+    def packets():
+        pa.process_device(d_vcdu.data_ptr(), d_off.data_ptr(), rows, p_bytes.data_ptr(), mb, p_desc.data_ptr(), mp, p_off.data_ptr(),
+                          p_sum.data_ptr(), stream=st)
+
+    def files():
+        fa.process_device(p_bytes.data_ptr(), mb, p_desc.data_ptr(), p_off.data_ptr(), mp, f_bytes.data_ptr(), mb, f_pieces.data_ptr(), mp,
+                          f_recs.data_ptr(), 2 * mp, f_sum.data_ptr(), stream=st)
+
+    packets()
+    files()
+    torch.cuda.synchronize()
+    fsum = f_sum.cpu().numpy().view(xa.FILES_SUMMARY_DTYPE)[0]
+    assert int(fsum["overflow"]) == 0
+    pieces = f_pieces.cpu().numpy().view(xa.FILE_PIECE_DTYPE)[:int(fsum["pieces"])]
+    recs = f_recs.cpu().numpy().view(xa.FILE_RECORD_DTYPE)[:int(fsum["files"])]
+    max_out = xa.images_max_bytes(recs)
+    o_bytes, o_lines, o_files, o_sum = u8(max_out + 8), u8(mp * 32), u8(2 * mp * 48), u8(xa.IMAGES_SUMMARY_DTYPE.itemsize)
+
+    def images():
+        im.process_device(f_bytes.data_ptr(), mb, f_pieces.data_ptr(), mp, f_recs.data_ptr(), 2 * mp, f_sum.data_ptr(), o_bytes.data_ptr(),
+                          max_out, o_lines.data_ptr(), mp, o_files.data_ptr(), o_sum.data_ptr(), stream=st)
+
+    # what the stage replaces: the host walks the records it read back and launches one decode per rice record
+    loop, at = [], 0
+    l_out, l_status = u8(max_out + 8), u8(len(pieces) + 1)
+    decoders = {}
+    for r in recs:
+        first, count = int(r["first_piece"]), int(r["n_pieces"])
+        if not (int(r["flags"]) & xa.FILE_BEGINS) or count < 2 or not xa.is_rice_coded(r, pieces[first]["length"]):
+            continue
+        par = (int(r["bits_per_pixel"]), int(r["pixels_per_block"]), int(r["columns"]))
+        rd = decoders.setdefault(par, xa.RiceDecoder(*par))
+        loop.append((rd, f_pieces.data_ptr() + 32 * (first + 1), count - 1, l_out.data_ptr() + at, l_status.data_ptr() + first + 1))
+        at += (count - 1) * ((par[2] * (1 if par[0] <= 8 else 2) + 3) & ~3)
+
+    def per_record():
+        for rd, desc, count, out, status in loop:
+            rd.decode_device(f_bytes.data_ptr(), mb, desc, 32, count, out, status, stream=st)
+
+    reps, warm = args.reps or 20, 3 if args.warmup is None else args.warmup
+    res = {"images": timed(images, reps, warm), "per-record loop": timed(per_record, reps, warm), "files": timed(files, reps, warm),
+           "packets+files": timed(lambda: (packets(), files()), reps, warm),
+           "packets+files+images": timed(lambda: (packets(), files(), images()), reps, warm)}
+    for name, (ms, mn) in res.items():
+        emit(case=name, rows=rows, ms_median=round(ms, 4), ms_min=round(mn, 4))
+    # the stage's lines are the generated images
+    torch.cuda.synchronize()
+    s = o_sum.cpu().numpy().view(xa.IMAGES_SUMMARY_DTYPE)[0]
+    lines = o_lines.cpu().numpy().view(xa.IMAGE_LINE_DTYPE)[:int(s["lines"])]
+    recs = f_recs.cpu().numpy().view(xa.FILE_RECORD_DTYPE)[:int(f_sum.cpu().numpy().view(xa.FILES_SUMMARY_DTYPE)[0]["files"])]
+    got = isp.Rows()
+    got.add(o_bytes.cpu().numpy(), lines, recs)
+    first_serial = {}
+    for r in recs:
+        k = (int(r["vcid"]), int(r["apid"]))
+        first_serial[k] = min(first_serial.get(k, 1 << 32), int(r["key_serial"]))
+    equal = all(np.array_equal(got.image(v, a, first_serial[(v, a)] + k)[0], img) for (v, a, k), img in sources.items())
+    moved = int(fsum["bytes"]) + int(s["bytes"]) + int(s["lines"]) * 64
+    emit(case="images check", images=int(s["images"]), records=len(recs), launches_replaced=len(loop), lines=int(s["lines"]),
+         faults=int(s["total_faults"]) , bytes_in=int(fsum["bytes"]), bytes_out=int(s["bytes"]), overflow=int(s["overflow"]),
+         parameter_sets=len(decoders), lines_equal_sources=bool(equal), Msamples_per_s=round(int(lines["samples"].astype(np.int64).sum()) / res["images"][0] / 1e3, 1),
+         GB_per_s_in_plus_out=round(moved / res["images"][0] / 1e6, 2), stage_over_loop=round(res["images"][0] / res["per-record loop"][0], 4),
+         chain_difference_ms=round(res["packets+files+images"][0] - res["packets+files"][0], 4))
+    for h in (pa, fa, im):
+        h.close()
+
+
 shared = []                                     # the packets and the files cases run on one stream of frames
 
 
@@ -437,5 +542,5 @@ def packet_chain():
 
 
 for what in ["decode", "demux", "packets", "files", "rice", "framer", "lock"] if args.what == "all" else [args.what]:
-    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "lock": bench_lock, "packets": lambda: bench_packets(packet_chain()),
+    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "lock": bench_lock, "images": bench_images, "packets": lambda: bench_packets(packet_chain()),
      "files": lambda: bench_files(packet_chain())}[what]()

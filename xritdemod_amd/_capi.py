@@ -137,6 +137,13 @@ _SIGNATURES = {
     "xrit_rice_decode_device": (C.c_int, [_vp, _sz, _vp, _sz, _sz, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "xrit_rice_form": (C.c_int, [C.c_int]),
     "xrit_rice_decode": (C.c_int, [_vp, _sz, _vp, _sz, _sz, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int]),
+    "xrit_images_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_images_destroy": (C.c_int, [_vp]),
+    "xrit_images_reset": (C.c_int, [_vp]),
+    "xrit_images_process_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "xrit_images_process": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "xrit_images_stats": (C.c_int, [_vp, _vp]),
+    "xrit_images_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -1316,3 +1323,130 @@ def decode_file_lines(record, pieces, data, device=0):
         return None
     dec = RiceDecoder(int(record["bits_per_pixel"]), int(record["pixels_per_block"]), int(record["columns"]), device)
     return dec.decode(data, mine[1:])
+
+
+# ---- image lines ---------------------------------------------------------------------------------
+# xrit_image_line: one per decoded line (offset and length lie as in xrit_packet)
+IMAGE_LINE_DTYPE = np.dtype([
+    ("offset", np.uint64), ("length", np.uint32), ("row", np.uint32), ("file", np.uint32), ("piece", np.uint32),
+    ("samples", np.uint16), ("bits", np.uint8), ("status", np.uint8), ("reserved", np.uint8, (4,))])
+assert IMAGE_LINE_DTYPE.itemsize == 32
+# xrit_image_file: one per files record, all zero where the record is not a rice-coded image's
+IMAGE_FILE_DTYPE = np.dtype([
+    ("offset", np.uint64), ("length", np.uint64), ("first_line", np.uint32), ("n_lines", np.uint32), ("first_row", np.uint32),
+    ("faults", np.uint32), ("lines_total", np.uint32), ("faults_total", np.uint32), ("columns", np.uint16), ("bits", np.uint8),
+    ("rice", np.uint8), ("reserved", np.uint8, (4,))])
+assert IMAGE_FILE_DTYPE.itemsize == 48
+_IMAGES_COUNTERS = [(k, np.uint64) for k in ("images_begun", "images_completed", "images_aborted", "total_lines", "total_faults",
+                                             "total_bytes")]
+# xrit_images_summary: a call's true counts and the handle's counters after it
+IMAGES_SUMMARY_DTYPE = np.dtype([("lines", np.uint64), ("bytes", np.uint64), ("images", np.uint64)] + _IMAGES_COUNTERS +
+                                [("overflow", np.uint32), ("reserved", np.uint32)])
+assert IMAGES_SUMMARY_DTYPE.itemsize == 80
+# xrit_images_counters
+IMAGES_STATS_DTYPE = np.dtype(_IMAGES_COUNTERS)
+assert IMAGES_STATS_DTYPE.itemsize == 48
+# xrit_image_key: what one (vcid, apid) carries
+IMAGE_KEY_DTYPE = np.dtype([("key_serial", np.uint32), ("lines", np.uint32), ("faults", np.uint32), ("open", np.uint8),
+                            ("reserved", np.uint8, (3,))])
+assert IMAGE_KEY_DTYPE.itemsize == 16
+
+
+def images_max_bytes(files):
+    """A bound on the image bytes of a call from its records (FILE_RECORD_DTYPE, on the host): every piece of a record a
+    line of the record's width, padded to a multiple of 4."""
+    files = np.asarray(files)
+    width = np.where(files["bits_per_pixel"] <= 8, 1, 2).astype(np.int64)
+    line = (files["columns"].astype(np.int64) * width + 3) & ~3
+    return int((files["n_pieces"].astype(np.int64) * line).sum())
+
+
+class ImageDecoder(_Handle):
+    """Every Rice-coded line of every image file of one FileAssembler call, decoded in one pass: the images may differ
+    in bits per pixel, block size and width.  Which images are open, with their lines and faults so far, is carried per
+    (vcid, apid) across calls until reset(), so an image whose packets arrive over many calls needs nothing from the
+    host but appending rows."""
+    _destroy = "xrit_images_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_images_create(C.byref(self._h), device))
+
+    def process(self, data, pieces, files, summary, max_lines=None, max_bytes=None):
+        """data, pieces, files and summary as FileAssembler.process returned them.  -> (bytes uint8: the lines' samples
+        back to back, uint8 or little-endian uint16, every line padded to a multiple of 4 bytes; lines IMAGE_LINE_DTYPE;
+        image_files IMAGE_FILE_DTYPE, one per record of `files`; summary, an IMAGES_SUMMARY_DTYPE record).  With
+        capacities that turn out too small XritError -5 is raised; its `partial` holds the same four with the prefix
+        that fitted (the handle's state has advanced all the same).  A files summary with overflow != 0, or with counts
+        beyond len(pieces) / len(files), is refused: XritError -1, `partial` with the summary (overflow 2) alone, the
+        state unchanged."""
+        data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        pieces = np.ascontiguousarray(pieces, FILE_PIECE_DTYPE).reshape(-1)
+        files = np.ascontiguousarray(files, FILE_RECORD_DTYPE).reshape(-1)
+        fsum = np.ascontiguousarray(np.asarray(summary, FILES_SUMMARY_DTYPE).reshape(1))
+        cap_l = len(pieces) if max_lines is None else int(max_lines)
+        cap_b = images_max_bytes(files) if max_bytes is None else int(max_bytes)
+        buf = np.empty(max(cap_b, 1), np.uint8)
+        lines = np.empty(max(cap_l, 1), IMAGE_LINE_DTYPE)
+        ifiles = np.empty(max(len(files), 1), IMAGE_FILE_DTYPE)
+        out_sum = np.zeros(1, IMAGES_SUMMARY_DTYPE)
+        rc = lib().xrit_images_process(self._h, _p(data), len(data), _p(pieces), len(pieces), _p(files), len(files), _p(fsum),
+                                       _p(buf), cap_b, _p(lines), cap_l, _p(ifiles), _p(out_sum))
+        if rc != 0 and int(out_sum[0]["overflow"]) == 2:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            err.partial = (buf[:0].copy(), lines[:0].copy(), ifiles[:0].copy(), out_sum[0])
+            raise err
+        if rc not in (0, -5):
+            _check(rc)
+        lines = lines[:min(int(out_sum[0]["lines"]), cap_l)].copy()
+        ifiles = ifiles[:len(files)].copy()
+        if int(out_sum[0]["bytes"]) <= cap_b:
+            nb = int(out_sum[0]["bytes"])
+        else:                                                # whole lines only: up to the end of the last one that fits
+            ends = lines["offset"] + ((lines["length"].astype(np.uint64) + 3) & ~np.uint64(3))
+            ends = ends[ends <= cap_b]
+            nb = int(ends.max()) if len(ends) else 0
+        out = (buf[:nb].copy(), lines, ifiles, out_sum[0])
+        if rc != 0:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            err.partial = out
+            raise err
+        return out
+
+    def process_device(self, d_bytes_ptr, n_bytes, d_pieces_ptr, max_pieces_in, d_files_ptr, max_files_in, d_files_summary_ptr,
+                       d_out_ptr, max_bytes, d_lines_ptr, max_lines, d_image_files_ptr, d_summary_ptr, stream=None):
+        """Device pointers (bytes of n_bytes, pieces max_pieces_in x 32, files max_files_in x 80 and the 104-byte summary
+        as FileAssembler.process_device wrote them; out max_bytes, lines max_lines x 32, image files max_files_in x 48,
+        summary 80 bytes), asynchronous on stream; may be queued behind FileAssembler.process_device: the counts are
+        read from its summary on the device."""
+        _check(lib().xrit_images_process_device(self._h, C.c_void_p(d_bytes_ptr), n_bytes, C.c_void_p(d_pieces_ptr), max_pieces_in,
+                                                C.c_void_p(d_files_ptr), max_files_in, C.c_void_p(d_files_summary_ptr),
+                                                C.c_void_p(d_out_ptr), max_bytes, C.c_void_p(d_lines_ptr), max_lines,
+                                                C.c_void_p(d_image_files_ptr), C.c_void_p(d_summary_ptr),
+                                                C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def rows(data, lines):
+        """The lines' samples: a list of (uint8 or uint16 array of `samples` entries) per IMAGE_LINE_DTYPE record."""
+        raw = np.asarray(data, np.uint8)
+        out = []
+        for ln in lines:
+            a = raw[int(ln["offset"]):int(ln["offset"]) + int(ln["length"])]
+            out.append(a.copy() if ln["bits"] <= 8 else a.view("<u2").copy())
+        return out
+
+    def stats(self):
+        """The counters after the last call (an IMAGES_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, IMAGES_STATS_DTYPE)
+        _check(lib().xrit_images_stats(self._h, _p(out)))
+        return out[0]
+
+    def key(self, vcid, apid):
+        """What (vcid, apid) carries after the last call (an IMAGE_KEY_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, IMAGE_KEY_DTYPE)
+        _check(lib().xrit_images_key(self._h, vcid, apid, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Every key closed, counters zero."""
+        _check(lib().xrit_images_reset(self._h))

@@ -532,6 +532,25 @@ int launch_files(const unsigned char *in_bytes, size_t n_in_bytes, const xrit_pa
 constexpr int RICE_FORM_LANE = 1, RICE_FORM_WAVE = 2;
 int launch_rice(const unsigned char *bytes, size_t n_bytes, const void *desc, size_t stride, size_t n_lines, int n, int J, int S,
                 void *out, unsigned char *status, int form, hipStream_t s);
+// image stage (images.hip): the handle's state is FILES_KEYS xrit_image_key records and one xrit_images_counters; the
+// per-call scratch for R = max(max_files_in, 1) records and P = max(max_pieces_in, 1) pieces
+constexpr unsigned IMAGES_TILE = 1024;              // records per tile of the scan
+constexpr unsigned IMAGES_TSUM = 6;                 // words of a tile's sums: lines, bytes, images, begun, completed, aborted
+struct ImageMark;                                   // image_rule.h
+struct ImagesScratch {
+    ImageMark *mark;                // [R] the rule's decision per record
+    unsigned *rlines;               // [R] the record's lines; after the scan: their exclusive prefix inside the tile
+    unsigned long long *rbytes;     // [R] ... and padded bytes
+    unsigned *rfaults;              // [R] lines of the record with status != 0
+    unsigned long long *tsum, *tbase;   // [T][IMAGES_TSUM] a tile's sums; [T][2] its first line index and byte offset
+    unsigned long long *call;       // [IMAGES_TSUM] the call's sums
+    unsigned char *lstatus;         // [P] per piece that is a line: its status
+};
+size_t images_scratch_carve(void *p, size_t max_files_in, size_t max_pieces_in, ImagesScratch &sc);
+int launch_images(const unsigned char *bytes, size_t n_bytes, const xrit_file_piece *pieces, size_t max_pieces_in,
+                  const xrit_file_record *files, size_t max_files_in, const xrit_files_summary *fsum, xrit_image_key *keys,
+                  xrit_images_counters *counters, ImagesScratch &sc, unsigned char *out, size_t max_bytes, xrit_image_line *lines,
+                  size_t max_lines, xrit_image_file *image_files, xrit_images_summary *summary, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

@@ -1,4 +1,4 @@
-// stage_handle.h -- what the stateful handles (framer, lock, decoder, demux, packets, files; the first three through
+// stage_handle.h -- what the stateful handles (framer, lock, decoder, demux, packets, files, images; the first three through
 // frame_cores.h) share on the host: the device, the
 // host-buffer path's own stream, the stream of the most recent call, and the "summary, written prefixes, XRIT_E_CAPACITY"
 // tail of a host-buffer call with capacities.  Host only.

@@ -215,7 +215,7 @@ bool parse(int argc, char **argv, Options &o)
 // --channels / --decoder-stats add the channel demultiplexer behind the decoder (:309-395): ChannelWriter's files and
 // the Statistics_st stream, from the correlator's hits as it returned them.  --packets adds the packet assembler behind
 // the demultiplexer: the channels' rows go back to the device and come out as CRC-checked space packets.  --files adds
-// the file assembler behind that (and, with --files-decompress, the Rice decoder on the lines of rice-coded image files).
+// the file assembler behind that (and, with --files-decompress, the image stage: the lines of rice-coded image files).
 struct FrameDecode {
     static constexpr size_t FRAME = 16384, VCDU = 892;
     static constexpr uint32_t MIN_CORRELATION = 46;     // MINCORRELATIONBITS (parameters.h:31)
@@ -241,9 +241,11 @@ struct FrameDecode {
     std::vector<uint8_t> f_bytes, img;
     std::vector<xrit_file_piece> f_pieces;
     std::vector<xrit_file_record> f_recs;
-    std::vector<uint8_t> line_status;
     xrit_files_summary f_summary{};
-    std::map<std::string, bool> rice_files;       // the open files that are rice-coded, by their path stem
+    xrit_images *im = nullptr;      // --files-decompress
+    std::vector<xrit_image_line> im_lines;
+    std::vector<xrit_image_file> im_files;
+    xrit_images_summary im_summary{};
     size_t rice_lines = 0, rice_faults = 0;
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
@@ -312,6 +314,10 @@ struct FrameDecode {
             if (::mkdir(files.c_str(), 0755) != 0 && errno != EEXIST) { std::perror("--files"); return false; }
             file_dir = files;
             decompress = files_decompress;
+            if (decompress && xrit_images_create(&im, device) != XRIT_OK) {
+                std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                return false;
+            }
         }
         return true;
     }
@@ -469,6 +475,7 @@ struct FrameDecode {
         if (xrit_files_process(fa, pk_bytes.get(), pk_summary.bytes, pk_desc.get(), pkt_off, f_bytes.data(), f_bytes.size(), f_pieces.data(),
                                f_pieces.size(), f_recs.data(), f_recs.size(), &f_summary) != XRIT_OK)
             return fail("files");
+        if (decompress && !decode_images()) return false;
         for (size_t i = 0; i < f_summary.files; ++i) {
             const xrit_file_record &r = f_recs[i];
             const std::string stem = file_dir + "/vc" + std::to_string(r.vcid) + "_apid" + std::to_string(r.apid) + "_" +
@@ -481,45 +488,49 @@ struct FrameDecode {
                 if (f) std::fclose(f);
                 if (!ok) { std::perror(part.c_str()); return false; }
             }
-            // the link rule: an image file, Rice compression, the first packet the headers alone
-            if (decompress && begins) {
-                const bool rice = r.header_state == 2 && r.file_type == 0 && r.compression == 1 && r.bits_per_pixel >= 1 &&
-                                  r.bits_per_pixel <= 16 && r.columns >= 1 &&
-                                  (r.pixels_per_block == 8 || r.pixels_per_block == 16 || r.pixels_per_block == 32 || r.pixels_per_block == 64) &&
-                                  r.header_length == f_pieces[r.first_piece].length;
-                if (rice) {
-                    rice_files[stem] = true;
-                    FILE *f = std::fopen(img_part.c_str(), "wb");
-                    if (!f) { std::perror(img_part.c_str()); return false; }
-                    std::fclose(f);
-                }
+            // the image stage's verdict: a rice-coded image's record (begun in this round, or open since an earlier one)
+            const bool rice = decompress && im_files[i].rice;
+            if (rice && begins) {
+                FILE *f = std::fopen(img_part.c_str(), "wb");
+                if (!f) { std::perror(img_part.c_str()); return false; }
+                std::fclose(f);
             }
-            const bool rice = decompress && rice_files.count(stem);
-            const size_t first = r.first_piece + (begins ? 1 : 0), lines = r.n_pieces - (begins ? 1 : 0);
-            if (rice && r.n_pieces && lines) {
-                const size_t width = r.bits_per_pixel <= 8 ? 1 : 2;
-                img.resize(lines * r.columns * width);
-                line_status.resize(lines);
-                if (xrit_rice_decode(f_bytes.data(), f_summary.bytes, &f_pieces[first], sizeof(xrit_file_piece), lines, r.bits_per_pixel,
-                                     r.pixels_per_block, r.columns, img.data(), line_status.data(), device) != XRIT_OK)
-                    return fail("rice");
-                rice_lines += lines;
-                for (size_t k = 0; k < lines; ++k) rice_faults += line_status[k] != 0;
+            if (rice && im_files[i].n_lines) {
+                const xrit_image_file &g = im_files[i];
+                rice_lines += g.n_lines;
+                rice_faults += g.faults;
+                // (the stage pads every line to a multiple of 4 bytes; the .img holds them back to back)
                 FILE *f = std::fopen(img_part.c_str(), "ab");
-                const bool ok = f && std::fwrite(img.data(), 1, img.size(), f) == img.size();
+                bool ok = f != nullptr;
+                for (size_t k = 0; ok && k < g.n_lines; ++k) {
+                    const xrit_image_line &ln = im_lines[g.first_line + k];
+                    ok = std::fwrite(img.data() + ln.offset, 1, ln.length, f) == ln.length;
+                }
                 if (f) std::fclose(f);
                 if (!ok) { std::perror(img_part.c_str()); return false; }
             }
             if (r.flags & XRIT_FILE_ABORTED) {
                 std::remove(part.c_str());
                 if (rice) std::remove(img_part.c_str());
-                rice_files.erase(stem);
             } else if (r.flags & XRIT_FILE_ENDS) {
                 if (std::rename(part.c_str(), (stem + ".lrit").c_str()) != 0) { std::perror(part.c_str()); return false; }
                 if (rice && std::rename(img_part.c_str(), (stem + ".img").c_str()) != 0) { std::perror(img_part.c_str()); return false; }
-                rice_files.erase(stem);
             }
         }
+        return true;
+    }
+    // --files-decompress: every Rice-coded line of this round's records in one call; which images are open waits on the device
+    bool decode_images()
+    {
+        size_t bound = 0;           // every piece of a record a line of the record's width, padded
+        for (size_t i = 0; i < f_summary.files; ++i)
+            bound += (size_t)f_recs[i].n_pieces * (((size_t)f_recs[i].columns * (f_recs[i].bits_per_pixel <= 8 ? 1 : 2) + 3) & ~(size_t)3);
+        img.resize(bound + 1);
+        im_lines.resize(f_summary.pieces + 1);
+        im_files.resize(f_summary.files + 1);
+        if (xrit_images_process(im, f_bytes.data(), f_summary.bytes, f_pieces.data(), f_summary.pieces, f_recs.data(), f_summary.files,
+                                &f_summary, img.data(), bound, im_lines.data(), f_summary.pieces, im_files.data(), &im_summary) != XRIT_OK)
+            return fail("images");
         return true;
     }
     void close_packet_files()
@@ -587,6 +598,8 @@ struct FrameDecode {
             if (decompress) std::fprintf(stderr, "rice: %zu lines decoded, %zu faulted\n", rice_lines, rice_faults);
             xrit_files_destroy(fa);
             fa = nullptr;
+            if (im) xrit_images_destroy(im);
+            im = nullptr;
         }
         if (pk) {
             std::fprintf(stderr, "packets: %llu emitted, %llu CRC failures, %llu discarded, %llu fill\n",
