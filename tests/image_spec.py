@@ -174,11 +174,12 @@ class Rows:
 
 
 # ---- generator ------------------------------------------------------------------------------------------------------
-def image_file(rng, n, J, cols, rows, kinds=rs.KINDS, spoil=None):
+def image_file(rng, n, J, cols, rows, kinds=rs.KINDS, spoil=None, force=None):
     """A rice-coded image file -> (samples (rows, cols), file bytes, cuts): the cuts put the headers alone into the first
-    packet and one coded line into each one behind it.  spoil(rng, line) damages a coded line before it is packed."""
+    packet and one coded line into each one behind it.  spoil(rng, line) damages a coded line before it is packed;
+    force is rs.encode's."""
     img = np.stack([rs.samples(rng, kinds[int(rng.integers(0, len(kinds)))], n, J, cols) for _ in range(rows)])
-    coded = [rs.encode(row, n, J) for row in img]
+    coded = [rs.encode(row, n, J, force=force) for row in img]
     if spoil is not None:
         coded = [spoil(rng, c) for c in coded]
     head = fs.lrit_file(b"", image=(n, cols, rows, 1), rice=(int(rng.integers(0, 65536)), J, 1),
@@ -231,3 +232,58 @@ def random_stream(rng, n_images, keys, n_other=0, max_cols=400, max_rows=12, spo
 def run_files(state, part):
     """The specification's files call on a piece of stream -> (bytes, pieces, files, summary dict)."""
     return fs.process(state, *fs.stage_input(part))
+
+
+# ---- large calls from small ones ------------------------------------------------------------------------------------
+def tiling_base(seed=50):
+    """A small stream on one key, (0, 0), made to be tiled: a file that is no image, an 8-bit image (J = 8, 11 columns,
+    2 rows, the second one truncated) and a 12-bit image (J = 16, 12 columns, 3 rows, the first one truncated) ->
+    (stream, cut, images by serial): stream[:cut] ends inside the last image, two packets before its end, so a first
+    call leaves it open with one line and one fault, and a second call holds nothing but its continuation."""
+    rng = np.random.default_rng(seed)
+    row = [0]
+
+    def spoil(r, line):
+        row[0] += 1
+        return rs.truncate(r, line) if row[0] in (2, 3) else line
+
+    plain = fs.lrit_file(rng.integers(0, 256, 50, dtype=np.uint8).tobytes(), file_type=2)
+    img8, d8, c8 = image_file(rng, 8, 8, 11, 2, kinds=("uniform", "walk3"), spoil=spoil)
+    img12, d12, c12 = image_file(rng, 12, 16, 12, 3, kinds=("uniform", "walk3"), spoil=spoil)
+    stream = stream_of(rng, [((0, 0), plain, None, 40), ((0, 0), d8, c8, 8190), ((0, 0), d12, c12, 8190)])
+    return stream, len(stream) - 2, {1: img8, 2: img12}
+
+
+
+def tile_call(files_out, copies):
+    """A files call (bytes, pieces, records, summary) whose records all sit on one key, repeated over `copies` distinct
+    keys: copy c on (c // 2048, c % 2048), its bytes, pieces and records behind those of copy c - 1.  The result is
+    ordered by (vcid, apid, stream order) like every files call; every count of the summary is the base's times
+    `copies` (the counters too: what a stream with that many keys leaves when every call of it is tiled alike)."""
+    data, pieces, files, summ = files_out
+    data, pieces, files = np.asarray(data, np.uint8), np.asarray(pieces), np.asarray(files)
+    assert 1 <= copies <= fs.N_VC * fs.N_APID
+    assert len({(int(r["vcid"]), int(r["apid"])) for r in files}) <= 1 and int(summ["files"]) == len(files)
+    assert int(summ["pieces"]) == len(pieces) and int(summ["bytes"]) == len(data)
+    c = np.arange(copies, dtype=np.uint64)
+    per_piece, per_file = np.repeat(c, len(pieces)), np.repeat(c, len(files))
+    out_p, out_f = np.tile(pieces, copies), np.tile(files, copies)
+    out_p["offset"] += per_piece * np.uint64(len(data))
+    out_p["file"] += (per_piece * np.uint64(len(files))).astype(np.uint32)
+    out_f["offset"] += per_file * np.uint64(len(data))
+    out_f["first_piece"] += (per_file * np.uint64(len(pieces))).astype(np.uint32)
+    for a, per in ((out_p, per_piece), (out_f, per_file)):
+        a["vcid"], a["apid"] = per // np.uint64(fs.N_APID), per % np.uint64(fs.N_APID)
+    return np.tile(data, copies), out_p, out_f, {k: int(v) * copies for k, v in summ.items()}
+
+
+def head_of_call(call, n_records):
+    """The first n_records records of a files call with exactly their pieces and bytes (records, pieces and bytes lie in
+    the same order, so each is a prefix) -> (bytes, pieces, records, summary: the three counts of the call alone)."""
+    data, pieces, files, _ = call
+    assert 0 <= n_records <= len(files)
+    head = files[:n_records]
+    n_pieces = int(head[-1]["first_piece"]) + int(head[-1]["n_pieces"]) if n_records else 0
+    n_bytes = int(head[-1]["offset"]) + int(head[-1]["length"]) if n_records else 0
+    assert n_pieces <= len(pieces) and n_bytes <= len(data)
+    return data[:n_bytes], pieces[:n_pieces], head, {"files": n_records, "pieces": n_pieces, "bytes": n_bytes}

@@ -153,7 +153,9 @@ def map_residuals(x, n):
     return np.concatenate([[0], m])
 
 
-class _Writer:
+class Writer:
+    """MSB-first bit writer: fixed fields, fundamental-sequence codes; bytes() pads the last byte with zeros."""
+
     def __init__(self):
         self.parts = []
 
@@ -191,7 +193,7 @@ def encode(x, n, J, force=None, stats=None):
     cost_raw = np.full(B, n * J)
     cost_raw[0] -= n
     zero = ~d.any(1)
-    w = _Writer()
+    w = Writer()
 
     def count(key):
         if stats is not None:
@@ -298,6 +300,121 @@ def flip(rng, line, count=1):
     for _ in range(count if a else 0):
         a[int(rng.integers(0, len(a)))] ^= 1 << int(rng.integers(0, 8))
     return bytes(a)
+
+
+# ---- lines made by hand: long codes, chunk edges, limits -------------------------------------------------------------
+def samples_of(ref, deltas, n):
+    """The samples behind the reference `ref` whose mapped residuals are `deltas`, each found by a search through the
+    encoder's mapper (the mapper is a bijection on 0 .. 2^n - 1 for every predecessor; the decoder is not consulted)."""
+    cand = np.arange(1 << n)
+    out, prev = [int(ref)], int(ref)
+    for v in deltas:
+        pairs = np.empty(2 * len(cand), np.int64)
+        pairs[0::2], pairs[1::2] = prev, cand
+        hit = np.flatnonzero(map_residuals(pairs, n)[1::2] == int(v))
+        assert len(hit) == 1, (prev, v)
+        prev = int(hit[0])
+        out.append(prev)
+    return np.array(out, np.int64)
+
+
+def split_line(n, J, k, ref, deltas, pad=True):
+    """A one-block line (S = J) under the split-sample option k, written by hand from the J - 1 mapped residuals behind
+    the reference -> (bytes, bits written).  pad = False: the bits must fill whole bytes."""
+    assert len(deltas) == J - 1
+    w = Writer()
+    w.put(k + 1, id_bits(n))
+    w.put(ref, n)
+    for v in deltas:
+        w.fs(int(v) >> k)
+    for v in deltas:
+        w.put(int(v) & ((1 << k) - 1), k)
+    bits = sum(len(p) for p in w.parts)
+    assert pad or bits % 8 == 0
+    return w.bytes(), bits
+
+
+def se_line(n, J, ref, gammas):
+    """A one-block line (S = J) under the second extension, from its J / 2 codes -> bytes."""
+    assert len(gammas) == J // 2
+    w = Writer()
+    w.put(1, id_bits(n) + 1)
+    w.put(ref, n)
+    for g in gammas:
+        w.fs(g)
+    return w.bytes()
+
+
+def longest_zero_run(line):
+    """The longest run of zero bits in front of a one."""
+    ones = np.flatnonzero(np.unpackbits(np.frombuffer(bytes(line), np.uint8)))
+    return int((np.diff(ones, prepend=-1) - 1).max()) if len(ones) else 0
+
+
+# (n, J, S, k, the zero run the case is for): uniform samples under a forced low k.  Codes across the wave form's 64-bit
+# windows (> 64); one block's codes across its 4096-bit chunks (more than 4096 bits of codes in a block of zero runs
+# > 64); single codes longer than a chunk, with chunks that hold no one in the middle (> 4096; > 2 * 4096)
+FORCED_LOW_K = ((8, 64, 192, 0, 64), (12, 16, 48, 0, 64), (16, 8, 16, 3, 4096), (16, 8, 16, 0, 2 * 4096), (16, 64, 128, 2, 2 * 4096))
+
+
+def forced_low_k_line(case, seed=11):
+    """-> (samples, bytes) of one FORCED_LOW_K case."""
+    n, J, S, k, _ = case
+    x = samples(np.random.default_rng(seed + n * J + k), "uniform", n, J, S)
+    return x, encode(x, n, J, force=k)
+
+
+CHUNK_EDGES = (4095, 4096, 4097, 8191, 8192, 8193)
+
+
+def chunk_edge_lines():
+    """Split-sample blocks (n = 16, J = 8, k = 2) in which a code's terminating one lies on bit 4095, 4096, 4097, 8191,
+    8192, 8193 counted from the start of the codes: once the first code's (its value is measured from the bit in front
+    of the section), once the second's (from the first's one) -> [(bytes, samples, bit of the one)]."""
+    out = []
+    for at in CHUNK_EDGES:
+        for lead in ((), (3,)):
+            hs = list(lead) + [at - sum(h + 1 for h in lead)] + [1, 0, 2, 0, 5, 0][:6 - len(lead)]
+            deltas = [(h << 2) | (i + 1 & 3) for i, h in enumerate(hs)]
+            ones = np.cumsum([h + 1 for h in hs]) - 1
+            assert at in ones and max(deltas) <= 65535
+            line, _ = split_line(16, 8, 2, 40000, deltas)
+            out.append((line, samples_of(40000, deltas, 16), at))
+    return out
+
+
+def limit_lines():
+    """-> [(n, J, bytes, samples, status)]: a line whose last code ends on its last bit (8 bits, J = 8, k = 0, seven codes
+    of value 2: 32 bits, no padding); a split-sample value at the limit h == xmax >> k (n = 12, k = 2, h = 1023: valid);
+    h one beyond it (a fault, the line all zero)."""
+    line, bits = split_line(8, 8, 0, 0x55, [2] * 7, pad=False)
+    assert bits == 32 and len(line) == 4 and line[-1] & 1
+    out = [(8, 8, line, samples_of(0x55, [2] * 7, 8), 0)]
+    for h, status in ((1023, 0), (1024, 1)):
+        deltas = [5, (h << 2) | 3, 0, 9, 1, 0, 2]
+        line, _ = split_line(12, 8, 2, 100, deltas)
+        out.append((12, 8, line, samples_of(100, deltas, 12) if status == 0 else np.zeros(8, np.int64), status))
+    return out
+
+
+SE_BETAS = (1, 2, 63, 64, 1000, 2895, 2896, 4094)
+
+
+def se_long_lines():
+    """Second-extension blocks (n = 16, J = 8) with the codes 0, g, 3, 0 behind the reference, g = T(beta) -- the pair
+    (beta, 0) -- and T(beta) + beta -- the pair (0, beta) --, T(beta) = beta (beta + 1) / 2: from beta = 2896 on
+    8 g + 1 is beyond 2^24 and a float32 root of it is only a start -> [(bytes, samples, g)].  The longest line,
+    beta = 4094, has 1 048 324 bytes."""
+    out = []
+    for beta in SE_BETAS:
+        t = beta * (beta + 1) // 2
+        for g, pair in ((t, (beta, 0)), (t + beta, (0, beta))):
+            deltas = [0, pair[0], pair[1], 2, 0, 0, 0]                 # (the first code's own first half stands in for the reference)
+            out.append((se_line(16, 8, 12345, [0, g, 3, 0]), samples_of(12345, deltas, 16), g))
+    return out
+
+
+MAX_LINE = 1 << 20                # bytes: the device refuses longer lines (status 2, all zero)
 
 
 def pack(lines):

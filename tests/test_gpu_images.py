@@ -2,8 +2,13 @@
 mixed (bits, block, columns) in one call, streams cut into small calls with the state compared after every call, two
 files on one key in one call, damaged streams and lines, every capacity, the refused call, reset, two handles, the device
 path behind lock, demultiplexer, packet and file assembler on one stream, the per-record decode that existed before, and
-pieces that lie outside the bytes.
+pieces that lie outside the bytes; calls tiled over up to 65 537 keys (image_spec.tile_call) with 63 to 524 289
+records -- full waves and tiles, second tiles, every kernel's grid cap and the stride behind it, a second round of the
+scan over the tiles --, two such calls on one handle, the device-pointer path with bounds four times the counts,
+capacities that cut in a later tile, and lines with long codes.
 Every comparison is exact."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -457,4 +462,245 @@ def test_pieces_outside_the_bytes_are_status_2(xa, mixed):
     assert (status == 2).sum() > 5 and (status == 0).sum() > 5 and want[3]["total_faults"] == int((status == 2).sum())
     im = xa.ImageDecoder()
     same(im.process(data[:cut], pieces, files, files_summary(xa, summ)), want)
+    im.close()
+
+
+# ---- calls beyond one tile ---------------------------------------------------------------------------------------------
+# Record indices at which the device's work changes hands: the waves of a tile (64), the tiles (IMAGES_TILE = 1024), the
+# records kernel's grid (4096 workgroups of 4 waves: 16384 records, a stride behind them), the rounds of 64 tiles in the
+# scan over the tiles (65536), the grids of the mark kernel (1024 x 256 records) and of the tile kernel (512 tiles).
+BOUNDARIES = (64, 1024, 16384, 65536, 262144, 524288)
+DECODE_GRID = 8192 * 4            # pieces: the decode kernel strides behind them
+
+
+@functools.lru_cache(maxsize=None)
+def tiling():
+    """The files calls that the large calls are tiled from (image_spec.tiling_base and one more image on its key):
+    first -- a file that is no image, an 8-bit image with a truncated line, a 12-bit image left open --, second -- the
+    rest of that image, nothing else --, third -- a 10-bit image left open after two lines --, fourth -- its rest."""
+    stream, cut, _ = isp.tiling_base()
+    rng = np.random.default_rng(52)
+    _, data, cuts = isp.image_file(rng, 10, 32, 7, 4, kinds=("uniform", "sparse"))
+    more = isp.stream_of(rng, [((0, 0), data, cuts, 8190)])
+    fst = fs.State()
+    return tuple(isp.run_files(fst, part) for part in (stream[:cut], stream[cut:], more[:3], more[3:]))
+
+
+@functools.lru_cache(maxsize=None)
+def large_call(records):
+    """`records` records of the tiled first call -> (files call, the specification's outputs, its state behind the
+    call); shared, never changed."""
+    first = tiling()[0]
+    call = isp.head_of_call(isp.tile_call(first, -(-records // len(first[2]))), records)
+    st = isp.State()
+    return call, isp.process(st, *call[:3]), st
+
+
+def holds_what_it_is_for(call, want):
+    """From the specification alone: faults, records that are rice-coded images and records that are not, and at every
+    boundary inside the call both kinds among the three records in front of it, a rice-coded record with lines ON it
+    (its first line and offset are sums over everything in front) and, where the call goes on, both kinds behind it."""
+    rice = want[2]["rice"].astype(bool)
+    n = len(rice)
+    assert want[3]["total_faults"] > 0 and rice.any() and not rice.all() and want[3]["lines"] > 0
+    inside = [b for b in BOUNDARIES if b < n]
+    for b in inside:
+        assert rice[b - 3:b].any() and not rice[b - 3:b].all(), b
+        assert rice[b] and int(want[2]["n_lines"][b]) > 0 and int(want[2]["first_line"][b]) > 0 and int(want[2]["offset"][b]) > 0, b
+        if n >= b + 3:
+            assert not rice[b:b + 3].all(), b
+    return inside
+
+
+def sampled_keys(files, seed=0):
+    """The first and the last key, the keys of the records on both sides of every boundary, and fifty drawn."""
+    n = len(files)
+    idx = {0, n - 1} | {i for b in BOUNDARIES for i in (b - 1, b) if i < n}
+    idx |= {int(i) for i in np.random.default_rng(seed).integers(0, n, 50)}
+    return sorted({(int(files[i]["vcid"]), int(files[i]["apid"])) for i in idx})
+
+
+def same_state_sampled(im, st, keys):
+    """same_state with the keys read back a sample (every key read waits for the device once)."""
+    s = im.stats()
+    for c in isp.COUNTERS:
+        assert int(s[c]) == getattr(st, c), c
+    for v, a in keys:
+        d = im.key(v, a)
+        assert (int(d["open"]), int(d["key_serial"]), int(d["lines"]), int(d["faults"])) == st.keys[(v, a)].as_tuple(), (v, a)
+        assert not d["reserved"].any()
+
+
+@pytest.mark.parametrize("records", [63, 64, 65, 1023, 1024, 1025, 2049, 16383, 16385, 65537, "pieces"])
+def test_one_call_matches_spec(xa, records):
+    """One call of that many records, tiled from the small one; "pieces": the smallest whole number of copies with more
+    pieces than the decode kernel's grid has waves."""
+    if records == "pieces":
+        first = tiling()[0]
+        records = len(first[2]) * (DECODE_GRID // len(first[1]) + 1)
+    (data, pieces, files, summ), want, st = large_call(records)
+    assert len(files) == records == summ["files"]
+    inside = holds_what_it_is_for((data, pieces, files, summ), want)
+    assert inside == [b for b in BOUNDARIES if b < records]
+    if len(pieces) > DECODE_GRID:
+        assert int(want[1]["piece"].max()) > DECODE_GRID and int(want[1]["piece"].min()) < DECODE_GRID
+    keys = sampled_keys(files, records)
+    assert (keys[0], keys[-1]) == ((0, 0), ((records - 1) // 3 // 2048, (records - 1) // 3 % 2048))
+    assert any(st.keys[k].open and st.keys[k].faults for k in keys)
+    im = xa.ImageDecoder()
+    same(im.process(data, pieces, files, files_summary(xa, summ)), want)
+    same_state_sampled(im, st, keys)
+    im.close()
+
+
+def test_two_calls_at_scale_and_the_state_is_usable(xa):
+    """51 000 records on 17 000 keys, then 17 000 records that are all continuations of the images the first call left
+    open (image_mark's `continued` branch for every key), then two small ordinary calls on five of those keys."""
+    copies = 17000
+    first, second, third, fourth = tiling()
+    calls = [isp.tile_call(first, copies), isp.tile_call(second, copies), isp.tile_call(third, 5), isp.tile_call(fourth, 5)]
+    assert len(calls[0][2]) > 16384 and len(calls[1][2]) > 16384
+    ist, im = isp.State(), xa.ImageDecoder()
+    for i, (data, pieces, files, summ) in enumerate(calls):
+        want = isp.process(ist, data, pieces, files)
+        if i == 0:
+            assert all(k.open for k in ist.keys.values()) and len(ist.keys) == copies
+        if i == 1:
+            assert not (files["flags"] & fs.BEGINS).any() and want[2]["rice"].all() and (want[2]["first_row"] == 1).all()
+            assert (want[2]["lines_total"] == 3).all() and not any(k.open for k in ist.keys.values())
+            assert ist.total_faults == 2 * copies and (want[2]['faults_total'] == 1).all() and want[3]["lines"] == 2 * copies
+        if i == 2:
+            assert (files["flags"] == fs.BEGINS).all() and want[3]["lines"] == 10
+        if i == 3:
+            assert (want[2]["first_row"] == 2).all() and (want[2]["lines_total"] == 4).all() and ist.images_completed == 2 * copies + 5
+        same(im.process(data, pieces, files, files_summary(xa, summ)), want)
+        same_state_sampled(im, ist, sampled_keys(calls[0][2], i))
+    im.close()
+
+
+def test_device_pointers_with_bounds_four_times_the_counts(xa):
+    """The 65 537-record call through process_device: bounds equal to the counts, then four times the counts (grids
+    sized by the bounds, most workgroups find nothing); the same bytes as the host-buffer call, nothing written
+    beyond the true counts."""
+    torch = pytest.importorskip("torch")
+    (data, pieces, files, summ), want, st = large_call(65537)
+    host = xa.ImageDecoder()
+    got = host.process(data, pieces, files, files_summary(xa, summ))
+    same(got, want)
+    host.close()
+    dev = torch.device("cuda:0")
+    nb, nl, nf = len(want[0]), len(want[1]), len(files)
+    cap_b = xa.images_max_bytes(files) + 4096
+    assert cap_b > nb + 1024
+    keys = sampled_keys(files)
+    for times in (1, 4):
+        def up(a, room):
+            t = torch.full((room,), 0xA5, dtype=torch.uint8, device=dev)
+            raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            t[:len(raw)] = torch.from_numpy(raw.copy()).to(dev)
+            return t
+        bp, bf = times * len(pieces), times * nf
+        d_data, d_pieces, d_files = up(data, len(data) + 8), up(pieces, bp * 32), up(files, bf * 80)
+        d_fsum = up(files_summary(xa, summ), 104)
+        d_out, d_lines, d_ifiles, d_sum = (torch.full((n,), 0xA5, dtype=torch.uint8, device=dev) for n in (cap_b, bp * 32, bf * 48, 80))
+        im = xa.ImageDecoder()
+        im.process_device(d_data.data_ptr(), len(data), d_pieces.data_ptr(), bp, d_files.data_ptr(), bf, d_fsum.data_ptr(),
+                          d_out.data_ptr(), cap_b, d_lines.data_ptr(), bp, d_ifiles.data_ptr(), d_sum.data_ptr())
+        torch.cuda.synchronize()
+        out, lines, ifiles, s = (t.cpu().numpy() for t in (d_out, d_lines, d_ifiles, d_sum))
+        assert s.tobytes() == got[3].tobytes(), times
+        assert np.array_equal(out[:nb], got[0]) and (out[nb:] == 0xA5).all(), times
+        assert lines[:nl * 32].tobytes() == got[1].tobytes() and (lines[nl * 32:] == 0xA5).all(), times
+        assert ifiles[:nf * 48].tobytes() == got[2].tobytes() and (ifiles[nf * 48:] == 0xA5).all(), times
+        same_state_sampled(im, st, keys)
+        im.close()
+    torch.cuda.empty_cache()
+
+
+def test_capacity_cut_in_a_later_tile(xa):
+    """test_each_capacity's rules with the cut far from the start: inside the second tile of records, behind line 1024,
+    and inside a record's lines."""
+    copies = 683                                                    # 2049 records
+    first, second = tiling()[:2]
+    f1, f2 = isp.tile_call(first, copies), isp.tile_call(second, copies)
+    ist = isp.State()
+    w1 = isp.process(ist, *f1[:3])
+    w2 = isp.process(ist, *f2[:3])
+    nb, nl = len(w1[0]), len(w1[1])
+    assert nl == 3 * copies and nb == 48 * copies
+    ends = (w1[1]["offset"] + ((w1[1]["length"].astype(np.uint64) + 3) & ~np.uint64(3))).astype(np.int64)
+    keys = sampled_keys(f1[2])
+    for cap in ({"max_lines": 1501}, {"max_bytes": 48 * 520 + 17}, {"max_lines": 1700, "max_bytes": 48 * 400 + 30}):
+        kl, cb = cap.get("max_lines", nl), cap.get("max_bytes", nb)
+        # (the cut lies behind line 1024, inside a record's lines or inside a line, in a record of the second tile)
+        cut_line = min(kl, int(np.searchsorted(ends, cb, side="right")))
+        assert cut_line > 1024 and int(w1[1]["file"][cut_line]) > 1024
+        assert cb not in ends if cut_line < kl else w1[1]["file"][cut_line - 1] == w1[1]["file"][cut_line]
+        im = xa.ImageDecoder()
+        with pytest.raises(xa.XritError) as ei:
+            im.process(f1[0], f1[1], f1[2], files_summary(xa, f1[3]), **cap)
+        assert ei.value.code == -5
+        data, lines, ifiles, summary = ei.value.partial
+        assert (int(summary["lines"]), int(summary["bytes"]), int(summary["images"]), int(summary["overflow"])) == \
+               (nl, nb, w1[3]["images"], 1)
+        for k in isp.COUNTERS:
+            assert int(summary[k]) == w1[3][k], k
+        assert lines.tobytes() == w1[1][:kl].tobytes() and ifiles.tobytes() == w1[2].tobytes()
+        # a line's samples are written iff it fits whole, padding included
+        fit = ends[:kl][ends[:kl] <= cb]
+        assert len(data) == (nb if cb >= nb else int(fit.max()))
+        assert np.array_equal(data, w1[0][:len(data)])
+        same(im.process(f2[0], f2[1], f2[2], files_summary(xa, f2[3])), w2)          # the state advanced as if everything had fitted
+        same_state_sampled(im, ist, keys)
+        im.close()
+
+
+def test_strides_of_the_mark_and_tile_kernels(xa):
+    """524 289 records: beyond the mark kernel's grid (262 144 records) and the tile kernel's (512 tiles), nine rounds of
+    the scan over the tiles.  Sixteen records a key, fourteen of them one-packet files that are no images (the
+    specification's time goes with the lines; most of this test's seconds are the specification's)."""
+    rng = np.random.default_rng(51)
+    plain = lambda: ((0, 0), fs.lrit_file(rng.integers(0, 256, 20, dtype=np.uint8).tobytes(), file_type=2), None, 8190)
+    good = isp.image_file(rng, 10, 8, 9, 1, kinds=("uniform",))
+    bad = isp.image_file(rng, 8, 16, 7, 1, kinds=("uniform",), spoil=rs.truncate)
+    items = [((0, 0), good[1], good[2], 8190)] + [plain() for _ in range(13)] + [((0, 0), bad[1], bad[2], 8190), plain()]
+    base = isp.run_files(fs.State(), isp.stream_of(rng, items))
+    assert len(base[2]) == 16 and len(base[1]) == 18
+    records = 524289
+    data, pieces, files, summ = call = isp.head_of_call(isp.tile_call(base, -(-records // 16)), records)
+    st = isp.State()
+    want = isp.process(st, data, pieces, files)
+    assert holds_what_it_is_for(call, want) == list(BOUNDARIES) and want[3]["lines"] == 65537 == 2 * want[3]["total_faults"] + 1
+    im = xa.ImageDecoder()
+    same(im.process(data, pieces, files, files_summary(xa, summ)), want)
+    same_state_sampled(im, st, sampled_keys(files))
+    im.close()
+
+
+def test_long_codes_through_the_image_stage(xa):
+    """decode_line_wave as this stage instantiates it, for uint8 and for uint16, on lines of uniform samples under a
+    forced k: zero runs across the 64-bit windows (8 bits, J = 64, k = 0) and single codes longer than a 4096-bit chunk
+    (16 bits, J = 8, k = 3).  Every line fits a packet."""
+    for seed in range(53, 73):                                      # (the first seed whose 16-bit lines all fit a packet)
+        rng = np.random.default_rng(seed)
+        img8, d8, c8 = isp.image_file(rng, 8, 64, 192, 3, kinds=("uniform",), force=0)
+        img16, d16, c16 = isp.image_file(rng, 16, 8, 16, 3, kinds=("uniform",), force=3)
+        if max(np.diff(c16 + [len(d16)])) <= 8190:
+            break
+    stream = isp.stream_of(rng, [((1, 8), d8, c8, 8190), ((1, 16), d16, c16, 8190)])
+    data, pieces, files, summ = isp.run_files(fs.State(), stream)
+    st = isp.State()
+    want = isp.process(st, data, pieces, files)
+    assert want[3]["lines"] == 6 and not want[1]["status"].any() and int(pieces["length"].max()) <= 8190
+    for ln in want[1]:
+        pc = pieces[int(ln["piece"])]
+        run = rs.longest_zero_run(data[int(pc["offset"]):int(pc["offset"]) + int(pc["length"])].tobytes())
+        print("bits", int(ln["bits"]), "bytes", int(pc["length"]), "longest zero run", run)
+        assert run > (64 if ln["bits"] == 8 else 4096)
+    im = xa.ImageDecoder()
+    got = im.process(data, pieces, files, files_summary(xa, summ))
+    same(got, want)
+    same_state(im, st)
+    assert np.array_equal(np.stack(xa.ImageDecoder.rows(got[0], got[1][:3])), img8)
+    assert np.array_equal(np.stack(xa.ImageDecoder.rows(got[0], got[1][3:])), img16)
     im.close()

@@ -1,8 +1,10 @@
 """GPU tier: the Rice decoder (xrit_rice_*, RiceDecoder) against the specification of tests/rice_spec.py -- batches that
 mix every option at both ID lengths, on both kernel forms (one lane per line, one wave per line), forced options, the shortest and longest lines, a stated share of truncated and
 damaged lines (status and kept prefix), descriptors outside the bytes, the stride form fed with file-piece and packet
-descriptor arrays, the device-pointer path, and decode_file_lines on the file assembler's output.  Every comparison is
-exact."""
+descriptor arrays, the device-pointer path, and decode_file_lines on the file assembler's output; valid lines with long
+codes (uniform samples under a forced low k: zero runs across 64-bit windows, 4096-bit chunks and many chunks; codes
+that end on a chunk's edge and on the line's last bit; values at the limit; second-extension codes up to 2^23) and the
+line limit of 2^20 bytes.  Every comparison is exact."""
 import numpy as np
 import pytest
 
@@ -195,3 +197,64 @@ def test_decode_file_lines_on_the_assembler_s_output(xa):
         seen += 1
     assert seen == 3
     fa.close()
+
+
+# ---- long codes: valid lines that the generators' cheapest options never produce --------------------------------------
+@pytest.mark.parametrize("case", rs.FORCED_LOW_K, ids=lambda c: "n%d-J%d-S%d-k%d" % c[:4])
+def test_forced_low_k_on_uniform_samples(xa, case):
+    """Codes across the wave form's 64-bit windows, a block's codes across its 4096-bit chunks, single codes across many
+    chunks with chunks that hold no one (the lane form: zero runs longer than its 64-bit buffer)."""
+    n, J, S, k, run = case
+    x, line = rs.forced_low_k_line(case)
+    y, status = rs.decode(line, n, J, S)
+    zeros = rs.longest_zero_run(line)
+    print("bytes", len(line), "longest zero run", zeros)
+    assert status == 0 and np.array_equal(x, y) and zeros > run     # from the specification, before the device is compared
+    # the line, the line with bytes behind it (ignored) and the line without its last byte (a fault: whole blocks kept)
+    status = check(xa, [line, line + b"\xa5\xff\x01", line[:-1]], n, J, S)
+    assert list(status[:2]) == [0, 0]
+
+
+def test_codes_that_end_on_chunk_edges_and_values_at_the_limit(xa):
+    edges = rs.chunk_edge_lines()
+    for line, x, at in edges:
+        y, status = rs.decode(line, 16, 8, 8)
+        assert status == 0 and np.array_equal(x, y) and rs.longest_zero_run(line) >= at - 4, at
+    assert not check(xa, [line for line, _, _ in edges], 16, 8, 8).any()
+    (n, J, line, x, status), at_limit, beyond = rs.limit_lines()
+    # a line whose last code ends on its last bit: alone, and with a line of ones behind it (reading on would go unnoticed); without its last bit
+    assert 8 * len(line) == 32 and rs.decode(line, n, J, 8)[1] == 0 and rs.decode(line[:3] + bytes([line[3] & 0xFE]), n, J, 8)[1] == 1
+    assert list(check(xa, [line, b"\xff" * 8, line, line[:3] + bytes([line[3] & 0xFE]), line], n, J, 8)[[0, 2, 3, 4]]) == [0, 0, 1, 0]
+    assert list(check(xa, [at_limit[2], beyond[2], at_limit[2]], 12, 8, 8)) == [0, 1, 0]
+    out, _ = xa.RiceDecoder(12, 8, 8).decode(*rs.pack([beyond[2]]))
+    assert not out.any()
+
+
+def test_second_extension_with_large_codes(xa):
+    """beta up to 4094: from 2896 on 8 g + 1 is beyond 2^24 and the float root is only a guess.  (With a correctly rounded
+    float32 square root the guess is right for every g below 2^23 -- checked exhaustively on the host --, so the two
+    fix-up loops behind it never act and no line can tell whether they are there.)  One batch, so that the megabyte
+    lines are decoded once per form."""
+    lines = rs.se_long_lines()
+    for line, x, g in lines:
+        y, status = rs.decode(line, 16, 8, 8)
+        assert status == 0 and np.array_equal(x, y) and rs.longest_zero_run(line) == max(g, 6), g
+    assert max(g for _, _, g in lines) > (1 << 23) - 4096 and max(len(ln) for ln, _, _ in lines) < rs.MAX_LINE
+    assert not check(xa, [line for line, _, _ in lines], 16, 8, 8).any()
+    out, _ = xa.RiceDecoder(16, 8, 8).decode(*rs.pack([line for line, _, _ in lines]))
+    assert np.array_equal(out, np.stack([x for _, x, _ in lines]))
+
+
+def test_the_line_limit(xa):
+    """A descriptor of exactly 2^20 bytes is decoded (here: a valid line that needs 1 048 324 of them, and the same bytes
+    from one byte on, whatever the specification says to those); one byte more is refused, status 2 and zeros."""
+    line, x, g = rs.se_long_lines()[-1]
+    data = np.frombuffer(line + b"\xa5" * (rs.MAX_LINE + 1 - len(line)), np.uint8)
+    assert len(data) == rs.MAX_LINE + 1
+    desc = rs.pack([b""] * 3)[1]
+    desc["offset"], desc["length"] = [0, 0, 1], [rs.MAX_LINE, rs.MAX_LINE + 1, rs.MAX_LINE]
+    want = [rs.decode(data[o:o + rs.MAX_LINE].tobytes(), 16, 8, 8) for o in (0, 1)]
+    assert want[0][1] == 0 and np.array_equal(want[0][0], x)
+    out, status = xa.RiceDecoder(16, 8, 8).decode(data, desc)
+    assert list(status) == [0, 2, want[1][1]]
+    assert np.array_equal(out[0], x) and not out[1].any() and np.array_equal(out[2], want[1][0])

@@ -80,6 +80,63 @@ def test_state_inside_an_image_and_after_an_abort():
     assert [int(x) for x in out[2]["rice"]] == [0, 1] and out[3]["lines"] == 6
 
 
+def test_a_tiled_call_is_well_formed_and_every_copy_is_the_base():
+    stream, cut, images = isp.tiling_base()
+    fst, base_state = fs.State(), isp.State()
+    base = [isp.run_files(fst, stream[:cut]), isp.run_files(fst, stream[cut:])]
+    base_out, base_key = [], []
+    for b in base:
+        base_out.append(isp.process(base_state, *b[:3]))
+        base_key.append(base_state.keys[(0, 0)].as_tuple())
+    assert [int(x) for x in base_out[0][2]["rice"]] == [0, 1, 1] and [int(x) for x in base_out[1][2]["rice"]] == [1]
+    assert base_key == [(1, 2, 1, 1), (0, 2, 3, 1)] and base_state.total_faults == 2
+    copies = 3
+    ist, rows = isp.State(), isp.Rows()
+    for b, want, key_after in zip(base, base_out, base_key):
+        data, pieces, files, summ = call = isp.tile_call(b, copies)
+        assert (summ["files"], summ["pieces"], summ["bytes"]) == (len(files), len(pieces), len(data)) == \
+               (copies * len(b[2]), copies * len(b[1]), copies * len(b[0]))
+        # ordered by key; every record's pieces contiguous, its own, inside the pieces; every piece inside the bytes
+        keys = files["vcid"].astype(np.int64) * 2048 + files["apid"]
+        assert (np.diff(keys) >= 0).all() and sorted(set(keys)) == list(range(copies))
+        assert np.array_equal(files["first_piece"][1:], (files["first_piece"] + files["n_pieces"])[:-1])
+        assert int(files["first_piece"][0]) == 0 and int(files["first_piece"][-1]) + int(files["n_pieces"][-1]) == len(pieces)
+        assert np.array_equal(pieces["file"], np.repeat(np.arange(len(files)), files["n_pieces"]))
+        assert np.array_equal(pieces["offset"][1:], (pieces["offset"] + pieces["length"])[:-1]) and int(pieces["offset"][0]) == 0
+        assert int(pieces["offset"][-1]) + int(pieces["length"][-1]) == len(data)
+        for r in files:
+            mine = pieces[int(r["first_piece"]):int(r["first_piece"]) + int(r["n_pieces"])]
+            assert (mine["vcid"] == r["vcid"]).all() and (mine["apid"] == r["apid"]).all()
+            assert int(mine["length"].sum()) == int(r["length"]) and (not len(mine) or int(mine[0]["offset"]) == int(r["offset"]))
+        out = isp.process(ist, data, pieces, files)
+        rows.add(out[0], out[1], files)
+        # every copy: the base's outputs, moved; the base's state on its key
+        nl, nb = len(want[1]), len(want[0])
+        assert np.array_equal(out[0], np.tile(want[0], copies)) and len(out[1]) == copies * nl
+        for c in range(copies):
+            mine = out[1][c * nl:(c + 1) * nl]
+            for f in ("length", "row", "samples", "bits", "status"):
+                assert np.array_equal(mine[f], want[1][f]), f
+            assert np.array_equal(mine["offset"], want[1]["offset"] + np.uint64(c * nb))
+            assert np.array_equal(mine["file"], want[1]["file"] + c * len(b[2])) and np.array_equal(mine["piece"], want[1]["piece"] + c * len(b[1]))
+        assert all(ist.keys[(0, c)].as_tuple() == key_after for c in range(copies))
+        # the head of a call: exactly its records' pieces and bytes
+        for n in (0, 1, len(b[2]), len(files) - 1, len(files)):
+            hd, hp, hf, hs = isp.head_of_call(call, n)
+            assert (hs["files"], hs["pieces"], hs["bytes"]) == (len(hf), len(hp), len(hd)) == \
+                   (n, int(files["n_pieces"][:n].sum()), int(files["length"][:n].sum()))
+            assert hf.tobytes() == files[:n].tobytes() and (not n or int(hp["file"].max()) == n - 1)
+    for c in isp.COUNTERS:
+        assert getattr(ist, c) == copies * getattr(base_state, c), c
+    for c in range(copies):
+        for serial, img in images.items():
+            x, status = rows.image(0, c, serial)
+            assert np.array_equal(x[status == 0], img[status == 0]) and list(status) == ([0, 1] if serial == 1 else [1, 0, 0])
+    # a copy beyond apid 2047 goes to the next channel
+    files = isp.tile_call(base[0], 2050)[2]
+    assert (int(files[-1]["vcid"]), int(files[-1]["apid"])) == (1, 1) and (int(files[2047 * 3]["vcid"]), int(files[2047 * 3]["apid"])) == (0, 2047)
+
+
 def test_the_link_rule_and_the_padding():
     rng = np.random.default_rng(5)
     img, data, cuts = isp.image_file(rng, 8, 8, 5, 3)

@@ -134,3 +134,50 @@ def test_batch_types_and_bad_parameters():
     for bad in ((0, 8, 1), (17, 8, 1), (8, 12, 1), (8, 8, 0), (8, 8, 65536)):
         with pytest.raises(ValueError):
             rs.decode(b"\x00", *bad)
+
+
+def test_forced_low_k_lines_hold_the_long_codes_they_are_for():
+    """Uniform samples under a forced low k: valid lines with zero runs longer than the wave form's 64-bit windows, with
+    a block's codes longer than its 4096-bit chunks, and with single codes longer than one and than two chunks."""
+    for case in rs.FORCED_LOW_K:
+        n, J, S, k, run = case
+        x, line = rs.forced_low_k_line(case)
+        stats = {}
+        assert rs.encode(x, n, J, force=k, stats=stats) == line and set(stats) == {k}
+        y, status = rs.decode(line, n, J, S)
+        assert status == 0 and np.array_equal(x, y), case
+        assert rs.longest_zero_run(line) > run, case
+        assert 8 * len(line) > 4096 * (S // J), case               # every case: more than a chunk of codes per block on average
+    assert rs.longest_zero_run(b"\x00\x80\x00\x01") == 22 and rs.longest_zero_run(bytes(3)) == 0
+
+
+def test_hand_made_lines_decode_to_what_they_were_built_from():
+    edges = rs.chunk_edge_lines()
+    assert sorted({at for _, _, at in edges}) == list(rs.CHUNK_EDGES) and len(edges) == 12
+    for line, x, at in edges:
+        # (the codes begin behind the 4-bit ID and the 16-bit reference)
+        assert np.unpackbits(np.frombuffer(line, np.uint8))[20 + at] == 1 and rs.longest_zero_run(line) >= at - 4
+        y, status = rs.decode(line, 16, 8, 8)
+        assert status == 0 and np.array_equal(x, y), at
+        assert x.min() >= 0 and x.max() <= 65535 and len(set(x.tolist())) > 4
+    (n, J, line, x, status), at_limit, beyond = rs.limit_lines()
+    assert len(line) == 4 and rs.decode(line, n, J, 8)[1] == 0 and np.array_equal(rs.decode(line, n, J, 8)[0], x)
+    assert rs.decode(line[:3], n, J, 8)[1] == 1                     # (its last bit is needed)
+    for n, J, line, x, status in (at_limit, beyond):
+        y, got = rs.decode(line, n, J, 8)
+        assert got == status and np.array_equal(x, y)
+    assert at_limit[4] == 0 and at_limit[3].any() and beyond[4] == 1 and not beyond[3].any()
+    # the mapper's inverse by search is the decoder's on a line the encoder wrote
+    rng = np.random.default_rng(8)
+    x = rs.samples(rng, "uniform", 12, 8, 8)
+    assert np.array_equal(rs.samples_of(x[0], rs.map_residuals(x, 12)[1:], 12), x)
+
+
+def test_second_extension_with_large_codes():
+    lines = rs.se_long_lines()
+    assert len(lines) == 2 * len(rs.SE_BETAS) and max(len(ln) for ln, _, _ in lines) == 1048324 < rs.MAX_LINE
+    assert sum(8 * g + 1 > 1 << 24 for _, _, g in lines) == 6      # where a float32 root of 8 g + 1 is only a start
+    for (line, x, g), beta in zip(lines, np.repeat(rs.SE_BETAS, 2)):
+        assert rs.longest_zero_run(line) == max(g, 6) and g - beta * (beta + 1) // 2 in (0, beta)
+        y, status = rs.decode(line, 16, 8, 8)
+        assert status == 0 and np.array_equal(x, y), g
