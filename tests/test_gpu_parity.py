@@ -1074,6 +1074,37 @@ def test_big_calls_walk_overlapping_blocks(xa, oracle_mod):
     assert [s_.costas_passes for s_ in st] == [s_.costas_passes for s_ in st2]
 
 
+@pytest.mark.parametrize("order", ["big_small", "small_big"])
+def test_a_queue_that_mixes_the_two_paths_gives_the_plain_words(xa, order):
+    """Two inputs registered ahead, one whose clock recovery walks overlapping blocks (2^23 samples at D = 1: everything up to its
+    walkers may run ahead) and one that takes the chains path (2^19 samples: started by its own call, or under the relay of the call
+    in front), in both orders: nothing is started for the input behind one of the other path (csrc/chain_pipeline.h, chain_next and
+    the chains path's moments), and the words are those of plain consecutive calls."""
+    import torch
+    nbig, nsmall, fs = 1 << 23, 1 << 19, 1.25e6
+    buf = _device_bursts(dict(fs_in=fs), nbig, 2)
+    sizes = [nbig, nsmall] if order == "big_small" else [nsmall, nbig]
+    cap = int(nbig / 4.2) + 4096
+    soft = torch.empty(cap, dtype=torch.float32, device=buf.device)
+
+    def run(ahead):
+        dem = xa.Demodulator(xa.Demodulator.config("lrit", fs, 1))
+        if ahead:
+            assert dem.prefetch_depth(sizes[0]) >= 1
+            for b in range(2):
+                dem.prefetch_device(buf[b].data_ptr(), sizes[b])
+        out = []
+        for b in range(2):
+            k = dem.process_device(buf[b].data_ptr(), sizes[b], soft.data_ptr(), cap)
+            out.append(soft[:k].cpu().numpy())
+        return out
+
+    plain, queued = run(False), run(True)
+    for b in range(2):
+        assert len(plain[b]) > sizes[b] / 4.3
+        assert np.array_equal(plain[b].view(np.uint32), queued[b].view(np.uint32)), (order, b, len(plain[b]), len(queued[b]))
+
+
 # (clock_passes, clock_relay_passes, clock_relay_closed, clock_relay_segments) per call size in symbols.  Recorded from the library
 # of commit a85a4d7 -- before the call's plan moved into csrc/clock_plan.h -- on an MI355X, together with the soft symbols the
 # two libraries were compared by (profiles/clock_plan_identity.txt): LRIT at 1.25 Msps, decimation 1, the device generator at

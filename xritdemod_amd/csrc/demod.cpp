@@ -1,12 +1,15 @@
-// demod.cpp -- the chain object and the C ABI (include/xritdemod_amd.h).
+// demod.cpp -- the chain handle of the C ABI (include/xritdemod_amd.h): errors and device selection, the configurations,
+// xrit_demod.  What the handle decides about its inputs in flight is chain_pipeline.h's; this file performs it with HIP.
+// (The stage objects and the one-shot wrappers: stages_abi.cpp; the handle's streams: stream_pool.cpp.)
 // Stage order, buffer hand-over and parameter defaults follow
 // /root/reference/demodulator/src/demodulator.cpp:100-168 (processSamples) and
 // :436-450 (construction); constants from Parameters.h:16-37.
 #include "kernels.h"
+#include "chain_pipeline.h"
+#include "stream_pool.h"
 
 #include <chrono>
 #include <cmath>
-#include <mutex>
 #include <new>
 #include <thread>
 #include <vector>
@@ -45,66 +48,39 @@ int select_device(int device)
 
 using namespace xrit;
 
-// what a front end leaves for the loops behind it
-struct SliceIO {
-    size_t length = 0;          // circuit-rate samples
-    const float2 *rrc = nullptr;
-    bool stat_ready = false;
-    int set = 0;                // which set of front-end buffers
-    const float *agc_flag = nullptr;    // the AGC guard flag of THIS front end (the stage's slot moves on with the next)
-    bool exact = false;         // this call's front end is the bit-exact one (cfg.front_exact = 2, or 0 on a call below the big-burst size)
+typedef ChainSlice SliceIO;
+
+static_assert(CHAIN_WALK_STREAMS == XRIT_WALK_STREAMS, "chain_pipeline.h names the walker streams one by one");
+constexpr int CHAIN_STREAMS = CHAIN_WALK1 + 1;
+// the handle's events, all without timing
+enum ChainEvent {
+    EV_DONE,            // the current call's clock recovery has left its result
+    EV_READY,           // input ready on the caller's stream
+    EV_FE0, EV_FE1,     // front end of a set done
+    EV_RELAY,           // the relay kernels of the current call come next
+    EV_COSTAS,          // the Costas loop started last has run its batch (ChainQueue::costas_event_of: whose)
+    CHAIN_EVENTS
 };
 
 struct xrit_demod {
     xrit_demod_config cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;
+    // by ChainStream (chain_pipeline.h: what runs on which).  own[CHAIN_CALLER]: where calls without a stream of the
+    // caller's run; own[CHAIN_COSTAS] is used with cfg.front_exact = 2 only (q.has_costas_stream)
+    hipStream_t own[CHAIN_STREAMS] = {};
+    bool pooled = false;        // the streams go back to the process's pool when the handle is destroyed
+    hipEvent_t ev[CHAIN_EVENTS] = {};
+    ChainQueue q;               // the inputs registered ahead and what has been started for them
+    bool costas_idle = false;   // the current call's Costas loop was finished before its clock recovery began: the stage is free
     float sps = 0, circuit_rate = 0;
     int dec_ntaps = 0;
     FirStage dec, rrc;
     AgcStage agc;
     CostasStage costas;
     ClockStage clock;
-    // Two sets of front-end buffers: the front end of the NEXT burst (xrit_demod_prefetch_device, on stream2) fills one
+    // Two sets of front-end buffers: the front end of the NEXT burst (xrit_demod_prefetch_device, on the front ends' stream) fills one
     // while the feedback loops of the current burst read the other.
     DevBuf bufA[2], bufB[2], bufC[2], bufR[2], stat[2], in_dev, soft_dev, q_in, q_out;
-    int next_set = 0;
-    hipStream_t stream2 = nullptr;
-    hipStream_t stream_c_pool = nullptr;    // the set's Costas stream (used by cfg.front_exact = 2 only)
-    bool pooled = false;                    // the streams go back to the process's pool when the handle is destroyed
-    hipStream_t stream_c = nullptr;     // cfg.front_exact = 2: the Costas loops (their exact walkers are latency, not work) beside the next front end
-    // bursts whose Costas loop is a handful of small kernels (few circuit-rate samples: large decimations) run that loop on the
-    // walker stream their own walkers will take, beside the next burst's decimator instead of behind it (ov_service)
-    size_t costas_own_stream_below = 16u << 20;                     // circuit-rate samples per burst (XRIT_OV_CSTREAM_BELOW)
-#ifndef XRIT_WALK_STREAMS
-#define XRIT_WALK_STREAMS 2
-#endif
-    hipStream_t stream3[XRIT_WALK_STREAMS] = {};                    // the clock recovery's walkers of bursts started ahead (round 5):
-                                                                    // two streams, so that two bursts' walkers run side by side
-    hipEvent_t ev_done = nullptr;                                   // the current call's clock recovery has left its result
-    hipEvent_t ev_ready = nullptr, ev_fe[2] = {nullptr, nullptr};   // input ready on the caller's stream / front end of a set done
-    hipEvent_t ev_relay = nullptr;                                  // the relay kernels of the current call come next
-    hipEvent_t ev_costas = nullptr;                                 // the Costas loop started ahead on stream2 has run its batch
-    bool costas_idle = false;   // the current call's Costas loop was finished before its clock recovery began: the stage is free
-    int last_fe_set = -1;       // set of the front end that ran last (its event orders the next one behind it)
-    struct Prefetched {
-        const void *samples = nullptr; size_t n = 0; int type = 0;
-        SliceIO io;                     // what its front end left (launch_prefetched)
-        bool costas_begun = false;      // the Costas loop of this input has been started too (on stream2, behind its front end)
-        float2 *slot = nullptr;         // ... writing here (the clock recovery's next input buffer)
-        // round 5, bursts whose clock recovery walks overlapping blocks (clock_overlap.h): everything up to the walkers runs ahead
-        bool costas_finished = false;   // the host has looked at the loop's stop test (and continued it where it had not closed)
-        int ov_job = -1;                // the clock stage's job of this input
-        bool walk_launched = false;     // its walkers have been enqueued (stream3)
-        int costas_stream = 0;          // 1: its Costas loop runs on the walker stream its own walkers will take (c_stream)
-        hipStream_t c_stream = nullptr; // the stream its Costas loop was enqueued on
-        bool agc_fallback = false;      // what the AGC's guard and the Costas loop reported for this input
-        int c_passes = 0; unsigned c_unconverged = 0; float c_max_residual = 0; bool c_walked = false;
-        bool launched = true;   // false: registered only -- a handle whose clock recovery is relayed (cfg.clock_exact >= 1)
-                                // starts the front end of the next burst in front of the relay kernels of the current one,
-                                // which leave most of the chip idle, instead of under the loops that fill it
-    } pf[XRIT_AHEAD + 1];                    // inputs registered ahead, oldest first: the one of the next process call and the two behind it
-    int pf_count = 0;
     RtlIngestStage rtl;
     bool poisoned = false;      // a call failed after some stage had advanced its carried state
     // what the Costas loop of the CURRENT call reported when it was finished: taken there, because with a registered next input the
@@ -121,32 +97,6 @@ struct xrit_demod {
     std::vector<std::string> prof_names;
 };
 
-struct xrit_fir { int device; hipStream_t stream; FirStage st; DevBuf in, out; };
-struct xrit_agc { int device; hipStream_t stream; AgcStage st; DevBuf in, out; };
-struct xrit_costas { int device; hipStream_t stream; CostasStage st; DevBuf in, out; };
-struct xrit_clock { int device; hipStream_t stream; ClockStage st; DevBuf in, out; };
-struct xrit_rtl { int device; hipStream_t stream; RtlIngestStage st; DevBuf in, out; };
-
-template <typename H> static int stage_open(H *h, int device)
-{
-    XR_TRY(select_device(device));
-    h->device = device;
-    XR_HIP(hipStreamCreate(&h->stream));
-    return XRIT_OK;
-}
-template <typename H> static void stage_close(H *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); }
-    h->st.release();
-    h->in.release();
-    h->out.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
-
 extern "C" {
 
 const char *xrit_last_error(void) { return get_error(); }
@@ -158,24 +108,6 @@ int xrit_device_count(void)
     if (hipGetDeviceCount(&count) != hipSuccess) return 0;
     return count;
 }
-
-int xrit_lowpass_taps(double gain, double sample_rate, double cutoff, double transition_width, float *taps, int cap)
-{
-    std::vector<float> h = design_lowpass(gain, sample_rate, cutoff, transition_width);
-    if ((int)h.size() > cap || !taps) return -(int)h.size();
-    memcpy(taps, h.data(), h.size() * sizeof(float));
-    return (int)h.size();
-}
-
-int xrit_rrc_taps(double gain, double sample_rate, double symbol_rate, double alpha, int ntaps, float *taps, int cap)
-{
-    std::vector<float> h = design_rrc(gain, sample_rate, symbol_rate, alpha, ntaps);
-    if ((int)h.size() > cap || !taps) return -(int)h.size();
-    memcpy(taps, h.data(), h.size() * sizeof(float));
-    return (int)h.size();
-}
-
-void xrit_mmse_table(float *table) { design_mmse_table(table); }
 
 static void config_common(xrit_demod_config *c, float sample_rate, uint32_t decimation)
 {
@@ -207,89 +139,6 @@ void xrit_demod_config_hrit(xrit_demod_config *c, float sample_rate, uint32_t de
     c->symbol_rate = 927000;   // HRIT_SYMBOL_RATE
     c->rrc_alpha = 0.3f;       // HRIT_RRC_ALPHA
 }
-
-// A stream with a hardware queue of its own.  HIP deals ordinary streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4) by
-// its own count of what the process has created so far, and two streams of a handle that land in one queue serialise: the
-// walkers of two bursts behind one another, or a Costas loop behind a burst's walkers -- measured late in round 5: the second and
-// the fourth handle of a process ran their bursts in 2.5 ms instead of 1.8, and so did a handle created after others had been
-// destroyed.  A stream created with a CU mask gets a queue of its own; the mask here is every CU.  (Not a guarantee either: with
-// eight handles alive in one process -- 16 such queues beside HIP's pools -- the fourth and later ones were slow again, hardware
-// queue slots being what they are; the first three handles of a process run at the same speed, which HIP's own dealing did not
-// give the second one.  XRIT_SHARED_QUEUES=1: plain hipStreamCreate.)
-static hipError_t create_own_queue_stream(hipStream_t *s)
-{
-    if (getenv("XRIT_SHARED_QUEUES")) return hipStreamCreate(s);      // (A/B: HIP's own dealing)
-    uint32_t mask[32];
-    for (auto &m : mask) m = 0xffffffffu;
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (cus > 32 * 32) cus = 32 * 32;            // (the mask array holds 32 words)
-    const uint32_t words = (uint32_t)((cus + 31) / 32);
-    if (cus % 32) mask[words - 1] = (1u << (cus % 32)) - 1u;
-    const hipError_t e = hipExtStreamCreateWithCUMask(s, words, mask);
-    if (e == hipSuccess) return e;
-    (void)hipGetLastError();
-    return hipStreamCreate(s);
-}
-
-static bool create_walker_streams(xrit_demod *d)
-{
-    for (auto &w : d->stream3) if (create_own_queue_stream(&w) != hipSuccess) return false;
-    return true;
-}
-
-// The streams of a handle are kept when the handle is destroyed and given to the next handle created on that device (round 6).
-// How fast a handle runs depends on which hardware queues its streams sit on (above), and what HIP deals a NEW stream depends
-// on everything the process has created before: a handle created after others had been destroyed ran its bursts in 2.5 ms
-// instead of 1.8 (round 5, profiles/r5_handles_in_one_process.txt).  With the pool such a handle runs on the very streams --
-// the very queues -- of the one before it: create / destroy sequences are as fast as the first handle, whatever their length.
-// (Handles that are alive TOGETHER still take a set each: more queues than the hardware has slots for are time-sliced.)
-namespace {
-struct StreamSet {
-    int device = -1;
-    hipStream_t s = nullptr, s2 = nullptr, s3[XRIT_WALK_STREAMS] = {}, sc = nullptr;
-};
-std::mutex g_pool_mu;
-std::vector<StreamSet> g_pool;
-
-bool stream_set_acquire(int device, StreamSet *out)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        for (size_t i = 0; i < g_pool.size(); ++i)
-            if (g_pool[i].device == device) { *out = g_pool[i]; g_pool.erase(g_pool.begin() + (long)i); return true; }
-    }
-    StreamSet n;
-    n.device = device;
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    // (the second stream at the lowest priority: a hardware queue of its own -- streams of one priority share a few
-    // queues round-robin, and a front end that lands in the queue of the caller's stream does not overlap anything --
-    // and the loops of the current burst go first where the two compete)
-    bool ok = hipStreamCreate(&n.s) == hipSuccess && hipStreamCreateWithPriority(&n.s2, hipStreamDefault, prio_least) == hipSuccess;
-    for (auto &w : n.s3) ok = ok && create_own_queue_stream(&w) == hipSuccess;
-    ok = ok && create_own_queue_stream(&n.sc) == hipSuccess;
-    if (!ok) {
-        if (n.s) (void)hipStreamDestroy(n.s);
-        if (n.s2) (void)hipStreamDestroy(n.s2);
-        for (auto w : n.s3) if (w) (void)hipStreamDestroy(w);
-        if (n.sc) (void)hipStreamDestroy(n.sc);
-        return false;
-    }
-    *out = n;
-    return true;
-}
-
-void stream_set_release(const StreamSet &st)
-{
-    if (st.s) (void)hipStreamSynchronize(st.s);
-    if (st.s2) (void)hipStreamSynchronize(st.s2);
-    for (auto w : st.s3) if (w) (void)hipStreamSynchronize(w);
-    if (st.sc) (void)hipStreamSynchronize(st.sc);
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    g_pool.push_back(st);
-}
-}  // namespace
 
 int xrit_demod_create(const xrit_demod_config *cfg, xrit_demod **out)
 {
@@ -334,23 +183,21 @@ int xrit_demod_create(const xrit_demod_config *cfg, xrit_demod **out)
         {
             StreamSet st;
             if (!stream_set_acquire(d->device, &st)) { set_error("hipStreamCreate failed"); rc = XRIT_E_HIP; break; }
-            d->stream = st.s; d->stream2 = st.s2; d->stream_c_pool = st.sc;
-            for (int i = 0; i < XRIT_WALK_STREAMS; ++i) d->stream3[i] = st.s3[i];
+            d->own[CHAIN_CALLER] = st.s; d->own[CHAIN_FRONT] = st.s2; d->own[CHAIN_COSTAS] = st.sc;
+            for (int i = 0; i < XRIT_WALK_STREAMS; ++i) d->own[CHAIN_WALK0 + i] = st.s3[i];
             d->pooled = true;
         }
-        if (hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->ev_ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->ev_fe[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->ev_fe[1], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->ev_relay, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&d->ev_costas, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); rc = XRIT_E_HIP; break; }
+        for (auto &e : d->ev)
+            if (rc == XRIT_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); rc = XRIT_E_HIP; }
+        if (rc != XRIT_OK) break;
         std::vector<float> rrc = design_rrc(1, d->circuit_rate, cfg->symbol_rate, cfg->rrc_alpha, cfg->rrc_taps);
         std::vector<float> lp = design_lowpass(1, cfg->sample_rate, d->circuit_rate / 2, 100e3);
         d->dec_ntaps = (int)lp.size();
         // (cfg.front_exact = 2: both filters summed in the CPU chain's order, the AGC and the Costas loop walked literally --
         // the front end bit for bit the CPU chain's through the Costas loop; fir.hip, agc.hip, costas_exact.hip)
         d->dec.exact = d->rrc.exact = d->agc.exact = d->costas.exact = cfg->front_exact == 2;
-        if (cfg->front_exact == 2 && !getenv("XRIT_NO_COSTAS_STREAM")) d->stream_c = d->stream_c_pool;
+        // (... and its Costas loops -- their exact walkers are latency, not work -- beside the next front end)
+        d->q.has_costas_stream = cfg->front_exact == 2 && !getenv("XRIT_NO_COSTAS_STREAM");
         // (wherever such a call takes the bit-exact front end -- the default and parity mode --, a call of up to 200 k symbols, i.e.
         // every chunk size of the reference, is ONE exact walk of the clock recovery: the CPU chain's words.  With the fast
         // front end on calls of every size, cfg.front_exact = -1 / 1, the limit stays where one walk costs no more than the
@@ -372,7 +219,7 @@ int xrit_demod_create(const xrit_demod_config *cfg, xrit_demod **out)
         d->no_defer = getenv("XRIT_NO_DEFER") != nullptr;
 #endif
 #ifdef XRIT_EXPERIMENTS
-        if (const char *e = getenv("XRIT_OV_CSTREAM_BELOW")) d->costas_own_stream_below = (size_t)atoll(e);
+        if (const char *e = getenv("XRIT_OV_CSTREAM_BELOW")) d->q.costas_own_stream_below = (size_t)atoll(e);
 #endif
         d->clock.relay_window = cfg->clock_exact_window > 0 ? cfg->clock_exact_window : 0;
         if (cfg->clock_min_passes > 0)
@@ -387,17 +234,11 @@ void xrit_demod_destroy(xrit_demod *d)
 {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    if (d->stream2) (void)hipStreamSynchronize(d->stream2);     // a front end that ran ahead may still be at work
-    if (d->stream_c) (void)hipStreamSynchronize(d->stream_c);
-    for (auto w : d->stream3) if (w) (void)hipStreamSynchronize(w);     // ... or walkers
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    // a front end that ran ahead may still be at work, or a Costas loop, or walkers; the caller's own stream last
+    for (ChainStream st : {CHAIN_FRONT, CHAIN_COSTAS, CHAIN_WALK0, CHAIN_WALK1, CHAIN_CALLER})
+        if (d->own[st]) (void)hipStreamSynchronize(d->own[st]);
     d->dec.release(); d->rrc.release(); d->agc.release(); d->costas.release(); d->clock.release();
-    if (d->stream_c_pool) (void)hipStreamSynchronize(d->stream_c_pool);
-    if (d->ev_done) (void)hipEventDestroy(d->ev_done);
-    if (d->ev_ready) (void)hipEventDestroy(d->ev_ready);
-    if (d->ev_relay) (void)hipEventDestroy(d->ev_relay);
-    if (d->ev_costas) (void)hipEventDestroy(d->ev_costas);
-    for (int i = 0; i < 2; ++i) if (d->ev_fe[i]) (void)hipEventDestroy(d->ev_fe[i]);
+    for (auto e : d->ev) if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { d->bufA[i].release(); d->bufB[i].release(); d->bufC[i].release(); d->bufR[i].release(); d->stat[i].release(); }
     d->rtl.release();
     d->in_dev.release(); d->soft_dev.release();
@@ -405,8 +246,8 @@ void xrit_demod_destroy(xrit_demod *d)
     for (auto &b : d->stage_buf) b.release();
     if (d->pooled) {
         StreamSet st;
-        st.device = d->device; st.s = d->stream; st.s2 = d->stream2; st.sc = d->stream_c_pool;
-        for (int i = 0; i < XRIT_WALK_STREAMS; ++i) st.s3[i] = d->stream3[i];
+        st.device = d->device; st.s = d->own[CHAIN_CALLER]; st.s2 = d->own[CHAIN_FRONT]; st.sc = d->own[CHAIN_COSTAS];
+        for (int i = 0; i < XRIT_WALK_STREAMS; ++i) st.s3[i] = d->own[CHAIN_WALK0 + i];
         stream_set_release(st);
     }
     delete d;
@@ -416,17 +257,16 @@ int xrit_demod_reset(xrit_demod *d, void *stream)
 {
     if (!d) { set_error("null argument"); return XRIT_E_INVALID; }
     XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-    XR_HIP(hipStreamSynchronize(d->stream2));       // a front end that ran ahead belongs to the stream being left
-    if (d->stream_c) XR_HIP(hipStreamSynchronize(d->stream_c));
-    for (auto w : d->stream3) XR_HIP(hipStreamSynchronize(w));      // ... and so do walkers
-    if (d->costas.job.n && d->pf_count > 0) {
+    hipStream_t s = stream ? (hipStream_t)stream : d->own[CHAIN_CALLER];
+    // a front end that ran ahead belongs to the stream being left, and so do Costas loops and walkers
+    for (ChainStream st : {CHAIN_FRONT, CHAIN_COSTAS, CHAIN_WALK0, CHAIN_WALK1})
+        if (st != CHAIN_COSTAS || d->q.has_costas_stream) XR_HIP(hipStreamSynchronize(d->own[st]));
+    if (d->costas.job.n && d->q.count > 0) {
         // (a Costas loop begun ahead and never looked at: the stage's bookkeeping is brought to an end before its state is reset)
-        for (int i = 0; i < d->pf_count; ++i)
-            if (d->pf[i].costas_begun && !d->pf[i].costas_finished) { bool redone = false; (void)d->costas.finish(d->pf[i].c_stream ? d->pf[i].c_stream : d->stream2, nullptr, &redone); }
+        for (int i = 0; i < d->q.count; ++i)
+            if (d->q.in[i].costas_begun && !d->q.in[i].costas_finished) { bool redone = false; (void)d->costas.finish(d->own[d->q.in[i].costas_stream], nullptr, &redone); }
     }
-    d->pf_count = 0;
-    d->last_fe_set = -1;
+    chain_reset(d->q);
     XR_TRY(d->dec.reset(s));
     XR_TRY(d->rrc.reset(s));
     XR_TRY(d->agc.reset(s));
@@ -446,7 +286,7 @@ int xrit_build_experiments(void)
 #endif
 }
 
-void *xrit_demod_stream(xrit_demod *d) { return d ? (void *)d->stream : nullptr; }
+void *xrit_demod_stream(xrit_demod *d) { return d ? (void *)d->own[CHAIN_CALLER] : nullptr; }
 float xrit_demod_sps(const xrit_demod *d) { return d ? d->sps : 0.f; }
 int xrit_demod_decimator_ntaps(const xrit_demod *d) { return d ? d->dec_ntaps : 0; }
 
@@ -553,27 +393,31 @@ static int front_end(xrit_demod *d, const void *in, size_t n, int type, int set,
     return XRIT_OK;
 }
 
-static bool ov_call(xrit_demod *d, size_t n);
-
-// the front end of a registered input on stream2 (xrit_demod_prefetch_device); `after`: not before this event
-static int launch_prefetched(xrit_demod *d, xrit_demod::Prefetched &f, hipEvent_t after)
+// a call of n input samples walks overlapping blocks (clock_overlap.h): bursts of a million symbols and more in the default
+// configuration
+static bool ov_call(xrit_demod *d, size_t n)
 {
-    // stream2 may read the input once whatever the caller queued on its stream at registration is done, and may touch
+    return chain_ov_call(d->clock, d->clock.xpad, d->keep_stages || d->keep_symbols, d->cfg.decimation, n);
+}
+
+// the front end of a registered input on the front ends' stream (xrit_demod_prefetch_device); `after`: not before this event
+static int launch_prefetched(xrit_demod *d, ChainInput &f, hipEvent_t after)
+{
+    // the stream may read the input once whatever the caller queued on its stream at registration is done, and may touch
     // the stages once the previous front end (on either stream) is done
-    XR_HIP(hipStreamWaitEvent(d->stream2, d->ev_ready, 0));
-    if (after) XR_HIP(hipStreamWaitEvent(d->stream2, after, 0));
-    if (d->last_fe_set >= 0) XR_HIP(hipStreamWaitEvent(d->stream2, d->ev_fe[d->last_fe_set], 0));
-    const int set = d->next_set;
-    d->next_set ^= 1;
+    hipStream_t s2 = d->own[CHAIN_FRONT];
+    XR_HIP(hipStreamWaitEvent(s2, d->ev[EV_READY], 0));
+    if (after) XR_HIP(hipStreamWaitEvent(s2, after, 0));
+    const ChainFrontEnd fe = chain_front_end_take(d->q);
+    if (fe.behind_set >= 0) XR_HIP(hipStreamWaitEvent(s2, d->ev[EV_FE0 + fe.behind_set], 0));
     Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
     // (the filters' waves in front of the walkers at issue -- where the walkers' latency is hidden: bursts that walk overlapping blocks)
-    d->dec.prio = d->rrc.prio = ov_call(d, f.n) ? 1 : 0;
-    int rc = front_end(d, f.samples, f.n, f.type, set, d->stream2, prof, &f.io);
+    d->dec.prio = d->rrc.prio = f.ov ? 1 : 0;
+    int rc = front_end(d, f.samples, f.n, f.type, fe.set, s2, prof, &f.io);
     d->dec.prio = d->rrc.prio = 0;
     if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-    XR_HIP(hipEventRecord(d->ev_fe[set], d->stream2));
-    d->last_fe_set = set;
-    f.launched = true;
+    XR_HIP(hipEventRecord(d->ev[EV_FE0 + fe.set], s2));
+    chain_front_end_done(d->q, f, fe.set);
     return XRIT_OK;
 }
 
@@ -589,40 +433,38 @@ static int costas_enqueue(xrit_demod *d, const SliceIO &io, hipStream_t s, Profi
     if (length) om = d->clock.om_slot((int)((length + (size_t)L - 1) / (size_t)L), L);
     const double inv_sps = 1.0 / (double)d->sps;
     const float2 *stat = io.stat_ready ? d->stat[io.set].as<float2>() : nullptr;
-    XR_TRY(d->costas.begin(io.rrc, slot, length, s, prof, stat, om, 0, inv_sps, io.exact));
+    XR_TRY(d->costas.begin(static_cast<const float2 *>(io.rrc), slot, length, s, prof, stat, om, 0, inv_sps, io.exact));
     if (length) XR_TRY(d->clock.om_scan(s));     // the timing guess's count curve, behind the final pass that leaves its statistic
-    if (length) XR_TRY(d->agc.request_flag_at(io.agc_flag, s));   // the AGC's guard flag rides along: no wait of its own
+    if (length) XR_TRY(d->agc.request_flag_at(static_cast<const float *>(io.agc_flag), s));   // the AGC's guard flag rides along: no wait of its own
     *slot_out = slot;
     return XRIT_OK;
 }
 
 // (a registered front end of the next burst goes in front of this call's relay kernels -- and behind it, where this call's
-// own Costas loop is done with the stage, the next burst's Costas loop)
+// own Costas loop is done with the stage, the next burst's Costas loop: chain_pipeline.h, the chains path's second moment)
 static void set_relay_hook(xrit_demod *d, hipStream_t s)
 {
     d->clock.before_relay = [d, s](int phase) -> int {
         // phase 0: in front of the relay kernels (an event marks the spot); phase 1: once they are enqueued
-        if (phase == 0) {
-            if (d->pf_count > 0 && !d->pf[0].launched) XR_HIP(hipEventRecord(d->ev_relay, s));
-            return XRIT_OK;
-        }
-        if (d->pf_count > 0 && !d->pf[0].launched) {
-            if (d->clock.trace_env) fprintf(stderr, "[xrit] the registered front end starts with the relay kernels%s\n", d->costas_idle ? ", its Costas loop behind it" : "");
-            XR_TRY(launch_prefetched(d, d->pf[0], d->ev_relay));
-            if (d->costas_idle) {
-                xrit_demod::Prefetched &f = d->pf[0];
-                int rc = costas_enqueue(d, f.io, d->stream2, d->prof.enabled ? &d->prof : nullptr, &f.slot);
-                if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-                XR_HIP(hipEventRecord(d->ev_costas, d->stream2));
-                f.costas_begun = true;
-            }
+        if (!chain_start_under_relay(d->q)) return XRIT_OK;
+        if (phase == 0) { XR_HIP(hipEventRecord(d->ev[EV_RELAY], s)); return XRIT_OK; }
+        const bool costas_too = chain_costas_under_relay(d->costas_idle);
+        if (d->clock.trace_env) fprintf(stderr, "[xrit] the registered front end starts with the relay kernels%s\n", costas_too ? ", its Costas loop behind it" : "");
+        ChainInput &f = d->q.in[0];
+        XR_TRY(launch_prefetched(d, f, d->ev[EV_RELAY]));
+        if (costas_too) {
+            float2 *slot = nullptr;
+            int rc = costas_enqueue(d, f.io, d->own[CHAIN_FRONT], d->prof.enabled ? &d->prof : nullptr, &slot);
+            if (rc != XRIT_OK) { d->poisoned = true; return rc; }
+            XR_HIP(hipEventRecord(d->ev[EV_COSTAS], d->own[CHAIN_FRONT]));
+            chain_costas_begun(d->q, f, CHAIN_FRONT, slot, -1, 0);      // (no overlap job is noted: its call takes the chains path)
         }
         return XRIT_OK;
     };
 }
 
 // clock recovery (:156, SymbolManager.cpp:104) of a slice whose Costas loop has been enqueued on s (costas_done: has been
-// finished ahead of this call, on stream2)
+// finished ahead of this call, on the front ends' stream)
 static void costas_note(xrit_demod *d)
 {
     d->costas_seen.passes = d->costas.passes;
@@ -639,20 +481,6 @@ static int costas_look(xrit_demod *d, size_t length, hipStream_t s, Profiler *pr
     const int rc = d->costas.finish(s, prof, redone);
     if (rc == XRIT_OK) costas_note(d);
     return rc;
-}
-
-// a process call takes the oldest registered input, and no other
-static int pf_check_front(xrit_demod *d, const void *d_samples, size_t n, int type)
-{
-    if (d->pf[0].samples == d_samples && d->pf[0].n == n && d->pf[0].type == type) return XRIT_OK;
-    set_error("process calls must take the prefetched inputs in the order they were prefetched");
-    d->poisoned = true;
-    return XRIT_E_INVALID;
-}
-static void pf_pop(xrit_demod *d)
-{
-    for (int i = 1; i < d->pf_count; ++i) d->pf[i - 1] = d->pf[i];
-    --d->pf_count;
 }
 
 // a finished call's statistics, from what the stages and the call's look at its Costas loop hold
@@ -677,20 +505,22 @@ static void fill_stats(xrit_demod *d, size_t n, size_t length, size_t nsym, int 
 }
 
 static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, size_t *nsym, hipStream_t s, Profiler *prof,
-                 bool costas_done = false, float2 *slot_done = nullptr)
+                 long call_id, bool costas_done = false, float2 *slot_done = nullptr)
 {
+    // call_id: the registration this call took (0: none -- and then no input waits behind it either)
     const size_t length = io.length;
     float2 *slot = slot_done;
     // Costas (:152) and clock recovery are enqueued back to back -- guesses, a batch of hand-off passes each with a
     // device-side stop test, final / output passes -- and the host waits once.  Only when a batch did not close (cold
     // start, unlocked input) does it continue pass by pass.
     if (!costas_done) XR_TRY(costas_enqueue(d, io, s, prof, &slot));
-    if (!costas_done && d->pf_count > 0 && !d->pf[0].launched) {
+    if (chain_costas_first(d->q, costas_done)) {
         // A stream with its next input registered: this call's Costas loop is finished FIRST (one more wait of the host), so
         // that the stage is free for the next burst's loop behind its front end, under this call's relay -- from the next
         // call on that is how every Costas loop of the stream runs and the extra wait is gone.
-        XR_HIP(hipEventRecord(d->ev_costas, s));
-        XR_HIP(hipEventSynchronize(d->ev_costas));
+        XR_HIP(hipEventRecord(d->ev[EV_COSTAS], s));
+        d->q.costas_event_of = call_id;
+        XR_HIP(hipEventSynchronize(d->ev[EV_COSTAS]));
         bool redone = false;
         XR_TRY(costas_look(d, length, s, prof, &redone));
         if (redone) d->clock.om_scanned = false;     // (the final pass ran again: the statistic is new, begin() unwraps it itself)
@@ -725,108 +555,90 @@ static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, si
     return rc;
 }
 
-// ---- round 5: bursts whose clock recovery walks overlapping blocks (clock_overlap.h) -----------------------------------------
-// Nothing in such a burst's clock recovery waits for the burst in front of it, so EVERYTHING up to its walkers runs ahead of
-// its process call: front end and Costas loop on stream2 (in the order of the inputs: the stages carry their state from one
-// to the next), the walkers on stream3 behind the Costas loop.  With two inputs registered behind the current call
-// (xrit_demod_prefetch_device) the device holds, at any time, the walkers of bursts b and b + 1 and the front end / Costas loop
-// of burst b + 2; a process call enqueues what the newest registration allows, waits for its own walkers and lays out its
-// symbols (ClockStage::ov_finalize) -- the relay's latency, which bounded a burst in round 4, is hidden.
-static bool ov_call(xrit_demod *d, size_t n)
+// a process call takes the oldest registered input, and no other
+static int pf_check_front(xrit_demod *d, const void *d_samples, size_t n, int type)
 {
-    const unsigned D = d->cfg.decimation;
-    d->clock.ov_allow = !(d->keep_stages || d->keep_symbols);
-    return d->clock.ov_eligible(D > 1 ? n / D : n);
+    if (chain_front_is(d->q, d_samples, n, type)) return XRIT_OK;
+    set_error("process calls must take the prefetched inputs in the order they were prefetched");
+    d->poisoned = true;
+    return XRIT_E_INVALID;
 }
 
-// whatever can be enqueued for the registered inputs, oldest first, without waiting for the device.  Returns an error code;
+// ---- bursts whose clock recovery walks overlapping blocks (clock_overlap.h): chain_next (chain_pipeline.h) says what may be
+// enqueued for the registered inputs; a process call enqueues what the newest registration allows, waits for its own walkers
+// and lays out its symbols (ClockStage::ov_finalize) -- the relay's latency, which bounds a relayed burst, is hidden.
+struct ChainFacts {
+    xrit_demod *d;
+    bool costas_event_done() { return hipEventQuery(d->ev[EV_COSTAS]) == hipSuccess; }
+    unsigned long long ov_serial() { return d->clock.ov_serial; }
+    bool can_launch_ahead(int job) { return d->clock.ov_can_launch_ahead(job); }
+};
+
+// one pass of chain_next's steps, each performed with HIP and its outcome written back.  Returns an error code;
 // *progress: something was enqueued or finished.
 static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
 {
     Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
     if (progress) *progress = false;
-    bool costas_busy = false;       // a Costas loop begun and not yet finished: the stage takes the next input behind it
-    for (int i = 0; i < d->pf_count && i < limit; ++i) {
-        xrit_demod::Prefetched &f = d->pf[i];
-        if (!ov_call(d, f.n)) break;                    // (inputs that take the other path are started by their own calls)
-        // (two sets of front-end buffers: the input two in front used the set this one takes, and its Costas loop reads that set
-        // until the host has seen it close -- a loop that did not close inside its batch goes on from the host)
-        if (!f.launched && (i < 2 || d->pf[i - 2].costas_finished)) {
+    ChainFacts facts{d};
+    ChainScan scan;
+    for (;;) {
+        const ChainStep st = chain_next(d->q, scan, facts, limit);
+        if (st.kind == CHAIN_NONE) return XRIT_OK;
+        ChainInput &f = d->q.in[st.i];
+        hipStream_t s = d->own[st.stream];
+        int rc = XRIT_OK;
+        switch (st.kind) {
+        case CHAIN_FRONT_END:
             XR_TRY(launch_prefetched(d, f, nullptr));
-            if (progress) *progress = true;
-        }
-        if (!f.launched) break;
-        if (f.costas_begun && !f.costas_finished) {
-            if (hipEventQuery(d->ev_costas) != hipSuccess) { costas_busy = true; continue; }
+            break;
+        case CHAIN_COSTAS_LOOK: {
             if (f.io.length && d->agc.requested_flag() == 2.0f) f.agc_fallback = true;
             bool redone = false;
-            int rc = d->costas.finish(f.c_stream ? f.c_stream : d->stream2, prof, &redone);
-            if (rc != XRIT_OK) { d->poisoned = true; return rc; }
+            rc = d->costas.finish(s, prof, &redone);
+            if (rc != XRIT_OK) break;
             f.c_passes = d->costas.passes; f.c_unconverged = d->costas.unconverged; f.c_max_residual = d->costas.max_residual;
             f.c_walked = d->costas.job.rescued && d->costas.walked;
-            f.costas_finished = true;
-            if (redone && f.ov_job >= 0) {
-                // the loop went on from the host and rewrote its output (and the timing statistic): walkers that were started
-                // behind the first batch have read the old one
-                rc = d->clock.ov_restart(f.ov_job, d->stream2);
-                if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-                f.walk_launched = false;
-            }
-            if (progress) *progress = true;
+            chain_costas_looked(f, redone);
+            break;
         }
-        if (!f.costas_begun && !costas_busy) {
-            // (on a stream of its own behind this input's front end: the front end of the input behind it runs beside this loop)
-            // (on the front ends' stream, behind this input's: measured with every stream on a hardware queue of its own
-            // -- GPU_MAX_HW_QUEUES=8 -- a Costas stream beside the front ends' costs 10 %, 2.05 against 1.85 ms per C2 burst: the
-            // loop's passes and the next input's decimator fill the chip each and only slow one another)
-            // (... unless the loop is a handful of small kernels -- C5: 2 M samples at the circuit rate, 0.3 ms of launches --, which
-            // then overlap the next input's decimator: 1.1 -> 0.9 ms per C5 burst)
-            // (round 5, late: not a stream of its own but the walker stream this burst's OWN walkers will take -- the one the
-            // walkers of the burst two in front are on: the loop then runs behind them instead of beside them, and its walkers
-            // behind it.  That is what HIP's dealing of streams onto hardware queues had arranged by accident on the first handle
-            // of a process, and measured better than a queue of its own: C5 1.08 against 1.11-1.14 ms per burst)
-            // (round 6, cfg.front_exact = 2: the exact AGC chains and the exact Costas walkers are a wave per SIMD or less for
-            // milliseconds -- latency, not work --, so the Costas loop of burst b runs on a stream of its own beside the front end
-            // of burst b + 1 instead of in front of it)
-            f.costas_stream = d->stream_c ? 2 : (f.io.length < d->costas_own_stream_below ? 1 : 0);
-            hipStream_t sc = f.costas_stream == 2 ? d->stream_c : f.costas_stream ? d->stream3[(d->clock.ov_serial + 1) % XRIT_WALK_STREAMS] : d->stream2;
-            f.c_stream = sc;
-            if (f.costas_stream) XR_HIP(hipStreamWaitEvent(sc, d->ev_fe[f.io.set], 0));
-            int rc = costas_enqueue(d, f.io, sc, prof, &f.slot);
-            if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-            XR_HIP(hipEventRecord(d->ev_costas, sc));
-            f.costas_begun = true;
-            f.ov_job = d->clock.ov_job;
-            costas_busy = true;
-            if (progress) *progress = true;
+        case CHAIN_WALK_RESTART:
+            rc = d->clock.ov_restart(f.ov_job, s);
+            if (rc == XRIT_OK) chain_walk_restarted(f);
+            break;
+        case CHAIN_COSTAS_BEGIN: {
+            if (st.wait_fe) XR_HIP(hipStreamWaitEvent(s, d->ev[EV_FE0 + f.io.set], 0));
+            float2 *slot = nullptr;
+            rc = costas_enqueue(d, f.io, s, prof, &slot);
+            if (rc != XRIT_OK) break;
+            XR_HIP(hipEventRecord(d->ev[EV_COSTAS], s));
+            const int job = d->clock.ov_job;
+            chain_costas_begun(d->q, f, st.stream, slot, job, job >= 0 ? d->clock.ov[job].serial : 0);
+            break;
         }
-        if (f.costas_begun && f.ov_job >= 0 && !f.walk_launched && d->clock.ov_can_launch_ahead(f.ov_job)) {
-            // (behind the Costas loop's batch and the timing curve: speculative until the host has seen the loop's stop test)
-            // (two walker streams, alternating: the walkers of bursts b and b + 1 side by side, those of b + 2 behind b's)
-            hipStream_t sw = d->stream3[d->clock.ov[f.ov_job].serial % XRIT_WALK_STREAMS];
-            XR_HIP(hipStreamWaitEvent(sw, d->ev_costas, 0));
-            int rc = d->clock.ov_launch(f.ov_job, sw, true, prof);
-            if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-            f.walk_launched = true;
-            if (progress) *progress = true;
+        case CHAIN_WALK_LAUNCH:
+            XR_HIP(hipStreamWaitEvent(s, d->ev[EV_COSTAS], 0));
+            rc = d->clock.ov_launch(f.ov_job, s, true, prof);
+            if (rc == XRIT_OK) chain_walk_launched(f);
+            break;
+        case CHAIN_NONE:
+            break;
         }
-        if (!f.costas_begun || !f.costas_finished) costas_busy = true;      // (the inputs behind wait for this one's loop)
+        if (rc != XRIT_OK) { d->poisoned = true; return rc; }
+        if (progress) *progress = true;
     }
-    return XRIT_OK;
 }
 
 static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int type, float *d_soft, size_t cap, size_t *n_out,
                            hipStream_t s, Profiler *prof)
 {
     // the call's own input goes through the same queue: registered now if it was not registered ahead
-    if (d->pf_count > 0) {
+    if (d->q.count > 0) {
         XR_TRY(pf_check_front(d, d_samples, n, type));
     } else {
-        XR_HIP(hipEventRecord(d->ev_ready, s));
-        xrit_demod::Prefetched &f = d->pf[0];
-        f = xrit_demod::Prefetched{};
-        f.samples = d_samples; f.n = n; f.type = type; f.launched = false;
-        d->pf_count = 1;
+        XR_HIP(hipEventRecord(d->ev[EV_READY], s));
+        chain_stage(d->q, d_samples, n, type, true);
+        d->q.count = 1;
     }
     auto fail = [&](int rc) { d->poisoned = true; *n_out = 0; return rc; };
     int rc = ov_service(d, nullptr);
@@ -834,26 +646,26 @@ static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int t
     // this call's Costas loop must have been looked at before its clock recovery is laid out
     // (only THIS input here: what the host enqueues for the inputs behind it -- a Costas loop, a front end: 0.2 ms of launches --
     // goes behind this call's walkers, which are on the critical path when nothing ran ahead)
-    for (int spins = 0; !d->pf[0].costas_finished; ++spins) {
-        if (d->pf[0].costas_begun) { if (hipEventSynchronize(d->ev_costas) != hipSuccess) { set_error("hipEventSynchronize failed"); return fail(XRIT_E_HIP); } }
+    ChainInput &f0 = d->q.in[0];
+    for (int spins = 0; !f0.costas_finished; ++spins) {
+        if (f0.costas_begun) { if (hipEventSynchronize(d->ev[EV_COSTAS]) != hipSuccess) { set_error("hipEventSynchronize failed"); return fail(XRIT_E_HIP); } }
         if ((rc = ov_service(d, nullptr, 1)) != XRIT_OK) return fail(rc);
         if (spins > 8) { set_error("the Costas loop of the call could not be started"); return fail(XRIT_E_INVALID); }
     }
-    xrit_demod::Prefetched &f0 = d->pf[0];
     d->agc_fallback_seen = f0.agc_fallback;
     d->costas_seen.passes = f0.c_passes; d->costas_seen.unconverged = f0.c_unconverged;
     d->costas_seen.max_residual = f0.c_max_residual; d->costas_seen.walked = f0.c_walked;
     // joints, output and result behind this call's walkers (started here if they did not run ahead), on the call's stream.
-    // (the host has SEEN the end of everything stream2 did for this input -- the Costas loop's event, a continued loop's
-    // synchronise --, so s needs no event of stream2's; the finalize kernels wait for the walkers' event)
+    // (the host has SEEN the end of everything the other streams did for this input -- the Costas loop's event, a continued
+    // loop's synchronise --, so s needs no event of theirs; the finalize kernels wait for the walkers' event)
     rc = d->clock.begin(f0.io.length, d_soft, nullptr, cap, s, prof);
     if (rc != XRIT_OK) return fail(rc);
-    if (hipEventRecord(d->ev_done, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(XRIT_E_HIP); }
+    if (hipEventRecord(d->ev[EV_DONE], s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(XRIT_E_HIP); }
     if ((rc = ov_service(d, nullptr)) != XRIT_OK) return fail(rc);
     // while the walkers finish: keep the inputs behind this one moving (the Costas loop of the next one may close meanwhile,
     // which frees the stage for the one after it)
     for (;;) {
-        const hipError_t q = hipEventQuery(d->ev_done);
+        const hipError_t q = hipEventQuery(d->ev[EV_DONE]);
         if (q == hipSuccess) break;
         if (q != hipErrorNotReady) { set_error("hipEventQuery failed: %s", hipGetErrorString(q)); return fail(XRIT_E_HIP); }
         bool progress = false;
@@ -863,7 +675,7 @@ static int process_overlap(xrit_demod *d, const void *d_samples, size_t n, int t
     size_t nsym = 0;
     rc = d->clock.finish(&nsym, s, prof);
     const size_t length = f0.io.length;
-    pf_pop(d);
+    chain_pop(d->q);
     if (rc != XRIT_OK) return fail(rc);
     if (prof) d->prof.collect();
     fill_stats(d, n, length, nsym, d->clock.relay_segments);       // (the walkers count as the call's segments)
@@ -882,7 +694,7 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
     if (type < 0 || type > 3) { set_error("unknown sample type %d", type); return XRIT_E_INVALID; }
     *n_out = 0;
     XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+    hipStream_t s = stream ? (hipStream_t)stream : d->own[CHAIN_CALLER];
     Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
     const unsigned D = d->cfg.decimation;
     if (d->poisoned) {
@@ -902,48 +714,49 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
         }
     }
     // (round 5: bursts of a million symbols and more in the default configuration)
-    if (ov_call(d, n) && !(d->pf_count > 0 && d->pf[0].costas_begun && d->pf[0].ov_job < 0))
+    if (chain_call_overlaps(d->q, ov_call(d, n)))
         return process_overlap(d, d_samples, n, type, d_soft, cap, n_out, s, prof);
     size_t total_sym = 0, total_len = 0;
     d->agc_fallback_seen = false;
     SliceIO io;
     int rc = XRIT_OK;
     bool costas_ahead = false;
-    if (d->pf_count > 0) {
+    long call_id = 0;
+    if (d->q.count > 0) {
         // the front end of this call ran ahead (xrit_demod_prefetch_device): the loops wait for it, nothing else
         XR_TRY(pf_check_front(d, d_samples, n, type));
         // (registered only: the call before had no relay phase to put it in front of)
-        if (!d->pf[0].launched) XR_TRY(launch_prefetched(d, d->pf[0], nullptr));
-        const xrit_demod::Prefetched f = d->pf[0];
-        pf_pop(d);
+        if (chain_start_at_call(d->q)) XR_TRY(launch_prefetched(d, d->q.in[0], nullptr));
+        const ChainInput f = d->q.in[0];
+        chain_pop(d->q);
         io = f.io;
+        call_id = f.id;
         if (f.costas_begun) {
             // its Costas loop ran ahead as well (under the relay of the call before): the host looks at its stop test now
-            // (continuing the passes on stream2 in the rare case the batch did not close), the clock recovery follows on s.
-            // The host has WAITED for everything stream2 was given for this burst -- front end, Costas loop, count curve; a
+            // (continuing the passes on the front ends' stream in the rare case the batch did not close), the clock recovery follows on s.
+            // The host has WAITED for everything that stream was given for this burst -- front end, Costas loop, count curve; a
             // continued loop ends with a stream synchronise of its own -- so s needs no event to wait for (every runtime
             // call here sits between the end of one burst's relay and the start of the next one's, with the device idle:
             // measured, steady state: 8 us between two calls, 6 us from entry to ClockStage::begin, 30 us to enqueue
             // tail + guess + relay kernels, of which the device spends 20 in the first two).
             // (from here on the registered input has been consumed: a failure poisons the handle below, no early return)
-            if (hipEventSynchronize(d->ev_costas) != hipSuccess) { set_error("hipEventSynchronize failed"); rc = XRIT_E_HIP; }
+            if (hipEventSynchronize(d->ev[EV_COSTAS]) != hipSuccess) { set_error("hipEventSynchronize failed"); rc = XRIT_E_HIP; }
             bool redone = false;
-            if (rc == XRIT_OK) rc = costas_look(d, io.length, d->stream2, prof, &redone);
+            if (rc == XRIT_OK) rc = costas_look(d, io.length, d->own[f.costas_stream], prof, &redone);
             if (redone) d->clock.om_scanned = false;
-            if (rc == XRIT_OK) rc = loops(d, io, d_soft, cap, &total_sym, s, prof, true, f.slot);
+            if (rc == XRIT_OK) rc = loops(d, io, d_soft, cap, &total_sym, s, prof, call_id, true, static_cast<float2 *>(f.slot));
             costas_ahead = true;
         } else {
-            if (hipStreamWaitEvent(s, d->ev_fe[f.io.set], 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); rc = XRIT_E_HIP; }
+            if (hipStreamWaitEvent(s, d->ev[EV_FE0 + f.io.set], 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); rc = XRIT_E_HIP; }
         }
     } else {
-        const int set = d->next_set;
-        d->next_set ^= 1;
+        const ChainFrontEnd fe = chain_front_end_take(d->q);
         // (a front end that ran ahead on the other stream earlier must be done before this one touches the stages)
-        if (d->last_fe_set >= 0) XR_HIP(hipStreamWaitEvent(s, d->ev_fe[d->last_fe_set], 0));
-        rc = front_end(d, d_samples, n, type, set, s, prof, &io);
-        if (rc == XRIT_OK) { XR_HIP(hipEventRecord(d->ev_fe[set], s)); d->last_fe_set = set; }
+        if (fe.behind_set >= 0) XR_HIP(hipStreamWaitEvent(s, d->ev[EV_FE0 + fe.behind_set], 0));
+        rc = front_end(d, d_samples, n, type, fe.set, s, prof, &io);
+        if (rc == XRIT_OK) { XR_HIP(hipEventRecord(d->ev[EV_FE0 + fe.set], s)); chain_front_end_started(d->q, fe.set); }
     }
-    if (rc == XRIT_OK && !costas_ahead) rc = loops(d, io, d_soft, cap, &total_sym, s, prof);
+    if (rc == XRIT_OK && !costas_ahead) rc = loops(d, io, d_soft, cap, &total_sym, s, prof, call_id);
     if (rc != XRIT_OK) {
         // some stage has flipped its ping-pong state, a later one has not: the handle cannot go on
         d->poisoned = true;
@@ -966,15 +779,39 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
     return XRIT_OK;
 }
 
+// ---- between two plain calls: what touches the carried state of the loops.  The shared prologue: arguments, a poisoned
+// handle, no registered input in flight (`why_not`: the entry's own end of that sentence), the device, the stream.
+// (A registered input's front end / Costas loop may have started from the state as it was, and left the clock stage its
+// timing statistic.)
+static int between_calls(xrit_demod *d, bool args_ok, const char *null_text, size_t *n_out, const char *why_not, void *stream, hipStream_t *s)
+{
+    if (!d || !args_ok) { set_error("%s", null_text); return XRIT_E_INVALID; }
+    if (n_out) *n_out = 0;
+    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
+    if (d->q.count > 0) { set_error("a prefetched input waits for its process call: %s", why_not); return XRIT_E_INVALID; }
+    XR_HIP(hipSetDevice(d->device));
+    *s = stream ? (hipStream_t)stream : d->own[CHAIN_CALLER];
+    return XRIT_OK;
+}
+
+// a clock recovery run again: where its complex symbols go, and what it leaves in the statistics
+static float2 *redo_symbols(xrit_demod *d) { return (d->keep_stages || d->keep_symbols) ? d->stage_buf[4].as<float2>() : nullptr; }
+static int redo_done(xrit_demod *d, int rc, size_t k, size_t *n_out)
+{
+    if (rc != XRIT_OK) { d->poisoned = true; return rc; }
+    d->stage_n[4] = k;
+    d->stats.symbols_out = k;
+    d->stats.clock_passes = d->clock.passes;
+    d->stats.clock_relay_passes = d->clock.relay_passes;
+    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
+    *n_out = k;
+    return XRIT_OK;
+}
+
 int xrit_demod_prepare_flipped(xrit_demod *d, void *stream)
 {
-    if (!d) { set_error("null argument"); return XRIT_E_INVALID; }
-    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    // (a registered input's front end / Costas loop may have started from the unflipped state, and left the clock stage its
-    // timing statistic: the flip belongs between two plain calls)
-    if (d->pf_count > 0) { set_error("a prefetched input waits for its process call: the flipped re-run belongs between plain calls"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+    hipStream_t s;
+    XR_TRY(between_calls(d, true, "null argument", nullptr, "the flipped re-run belongs between plain calls", stream, &s));
     int rc = d->clock.make_alt(s, d->prof.enabled ? &d->prof : nullptr);
     if (rc != XRIT_OK) d->poisoned = true;
     return rc;
@@ -984,11 +821,10 @@ size_t xrit_demod_clock_carry_bytes(void) { return ClockStage::CARRY_BYTES; }
 
 int xrit_demod_export_clock_carry(xrit_demod *d, int which, void *d_rec, void *stream)
 {
-    if (!d || !d_rec || which < 0 || which > 1) { set_error("null or invalid argument"); return XRIT_E_INVALID; }
-    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    if (d->pf_count > 0) { set_error("a prefetched input waits for its process call: the carried state is not between two calls"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(d->device));
-    return d->clock.export_carry(d_rec, which, stream ? (hipStream_t)stream : d->stream);
+    hipStream_t s;
+    XR_TRY(between_calls(d, d_rec && which >= 0 && which <= 1, "null or invalid argument", nullptr,
+                         "the carried state is not between two calls", stream, &s));
+    return d->clock.export_carry(d_rec, which, s);
 }
 
 int xrit_demod_last_clock_exact(const xrit_demod *d)
@@ -999,65 +835,35 @@ int xrit_demod_last_clock_exact(const xrit_demod *d)
 
 int xrit_demod_redo_clock_from(xrit_demod *d, const void *d_rec, float *d_soft, size_t cap, size_t *n_out, void *stream)
 {
-    if (!d || !d_rec || !n_out || !d_soft) { set_error("null argument"); return XRIT_E_INVALID; }
-    *n_out = 0;
-    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    if (d->pf_count > 0) { set_error("a prefetched input waits for its process call: the re-run belongs between plain calls"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+    hipStream_t s;
+    XR_TRY(between_calls(d, d_rec && n_out && d_soft, "null argument", n_out, "the re-run belongs between plain calls", stream, &s));
     unsigned head[4] = {0, 0, 0, 0};
     XR_HIP(hipMemcpyAsync(head, d_rec, sizeof head, hipMemcpyDeviceToHost, s));
     XR_HIP(hipStreamSynchronize(s));
     if (head[0] != 1u || head[1] > 1024u) { set_error("not a carried clock state (xrit_demod_export_clock_carry)"); return XRIT_E_INVALID; }
-    Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
-    float2 *sym = (d->keep_stages || d->keep_symbols) ? d->stage_buf[4].as<float2>() : nullptr;
     size_t k = 0;
-    const int rc = d->clock.redo_from(d_rec, head[1], d_soft, sym, cap, &k, s, prof);
-    if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-    d->stage_n[4] = k;
-    d->stats.symbols_out = k;
-    d->stats.clock_passes = d->clock.passes;
-    d->stats.clock_relay_passes = d->clock.relay_passes;
-    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
-    *n_out = k;
-    return XRIT_OK;
+    const int rc = d->clock.redo_from(d_rec, head[1], d_soft, redo_symbols(d), cap, &k, s, d->prof.enabled ? &d->prof : nullptr);
+    return redo_done(d, rc, k, n_out);
 }
 
 int xrit_demod_flip_costas_phase(xrit_demod *d, void *stream)
 {
-    if (!d) { set_error("null argument"); return XRIT_E_INVALID; }
-    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    if (d->pf_count > 0) { set_error("a prefetched input waits for its process call: its Costas loop may already have started"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(d->device));
-    return d->costas.flip_phase(stream ? (hipStream_t)stream : d->stream);
+    hipStream_t s;
+    XR_TRY(between_calls(d, true, "null argument", nullptr, "its Costas loop may already have started", stream, &s));
+    return d->costas.flip_phase(s);
 }
 
 int xrit_demod_redo_clock_flipped(xrit_demod *d, float *d_soft, size_t cap, size_t *n_out, void *stream)
 {
-    if (!d || !n_out || !d_soft) { set_error("null argument"); return XRIT_E_INVALID; }
-    *n_out = 0;
-    if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    // (a registered input's front end / Costas loop may have started from the unflipped state, and left the clock stage its
-    // timing statistic: the flip belongs between two plain calls)
-    if (d->pf_count > 0) { set_error("a prefetched input waits for its process call: the flipped re-run belongs between plain calls"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-    Profiler *prof = d->prof.enabled ? &d->prof : nullptr;
-    float2 *sym = (d->keep_stages || d->keep_symbols) ? d->stage_buf[4].as<float2>() : nullptr;
+    hipStream_t s;
+    XR_TRY(between_calls(d, n_out && d_soft, "null argument", n_out, "the flipped re-run belongs between plain calls", stream, &s));
     size_t k = 0;
     // The negated Costas output is the other lock's output to rounding only, which alone moves a float32 M&M by its
     // 5e-5 .. 1e-4.  The run is repeated in the handle's own configuration (cfg.clock_exact: by
     // default two hand-off passes and three relay passes, csrc/clock_relay.h).
-    int rc = d->clock.redo_flipped(d_soft, sym, cap, &k, s, prof);
+    int rc = d->clock.redo_flipped(d_soft, redo_symbols(d), cap, &k, s, d->prof.enabled ? &d->prof : nullptr);
     if (rc == XRIT_OK) rc = d->costas.flip_phase(s);
-    if (rc != XRIT_OK) { d->poisoned = true; return rc; }
-    d->stage_n[4] = k;
-    d->stats.symbols_out = k;
-    d->stats.clock_passes = d->clock.passes;
-    d->stats.clock_relay_passes = d->clock.relay_passes;
-    d->stats.clock_relay_closed = d->clock.relay_closed ? 1 : 0;
-    *n_out = k;
-    return XRIT_OK;
+    return redo_done(d, rc, k, n_out);
 }
 
 int xrit_demod_prefetch_depth(xrit_demod *d, size_t n)
@@ -1072,37 +878,21 @@ int xrit_demod_prefetch_device(xrit_demod *d, const void *d_samples, size_t n, i
     if (!d || (n && !d_samples)) { set_error("null argument"); return XRIT_E_INVALID; }
     if (type < 0 || type > 3) { set_error("unknown sample type %d", type); return XRIT_E_INVALID; }
     if (d->poisoned) { set_error("this handle's carried state is inconsistent after an earlier failed call"); return XRIT_E_INVALID; }
-    // Two sets of front-end buffers: the front end of the input two behind a call would overwrite what that call's loops still
-    // read.  Bursts whose clock recovery walks overlapping blocks hold their front ends back until that is safe (ov_service) and
-    // may wait three deep -- the call in progress and two behind it --; everything else two deep, as before round 5.
-    {
-        bool all_ov = ov_call(d, n);
-        for (int i = 0; i < d->pf_count && all_ov; ++i) all_ov = ov_call(d, d->pf[i].n);
-        const int room = all_ov ? XRIT_AHEAD + 1 : 2;
-        if (d->pf_count >= room) { set_error("%d prefetched inputs are already waiting for their process calls", d->pf_count); return XRIT_E_INVALID; }
-    }
+    const bool ov = ov_call(d, n);
+    if (d->q.count >= chain_room(d->q, ov)) { set_error("%d prefetched inputs are already waiting for their process calls", d->q.count); return XRIT_E_INVALID; }
     // stage copies and per-kernel event brackets belong to one call at a time: no running ahead then
     if (d->keep_stages || d->keep_symbols || (d->prof.enabled && !d->prof.light)) return XRIT_OK;
     XR_HIP(hipSetDevice(d->device));
-    hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-    // stream2 may read the input once whatever the caller queued on its stream is done, and may touch the stages once
-    // the previous front end (on either stream) is done
-    XR_HIP(hipEventRecord(d->ev_ready, s));
-    xrit_demod::Prefetched &f = d->pf[d->pf_count];
-    f = xrit_demod::Prefetched{};
-    f.samples = d_samples; f.n = n; f.type = type; f.launched = false;
-    // Unless the relay is off (cfg.clock_exact < 0) the next process call ends in relay kernels that occupy three
-    // waves per CU: the front end waits for those (ClockStage::before_relay) instead of competing with the Costas and
-    // hand-off passes.  (Registered inputs start in order: the process call that takes one starts it if it still waits,
-    // and starts the one behind it in front of its own relay kernels.)
-    // (bursts whose clock recovery walks overlapping blocks: the next process call enqueues everything that can run ahead)
-    const bool defer = (d->clock.relay_by_default() && !d->no_defer) || ov_call(d, n);
-    if (!defer) {
+    hipStream_t s = stream ? (hipStream_t)stream : d->own[CHAIN_CALLER];
+    // the front ends' stream may read the input once whatever the caller queued on its stream is done
+    XR_HIP(hipEventRecord(d->ev[EV_READY], s));
+    ChainInput &f = chain_stage(d->q, d_samples, n, type, ov);
+    if (!chain_defer(d->clock.relay_by_default(), d->no_defer, ov)) {
         // (front ends run in the order of their inputs: one that is still waiting goes first)
-        if (d->pf_count > 0 && !d->pf[0].launched) XR_TRY(launch_prefetched(d, d->pf[0], nullptr));
+        if (chain_start_oldest_first(d->q)) XR_TRY(launch_prefetched(d, d->q.in[0], nullptr));
         XR_TRY(launch_prefetched(d, f, nullptr));
     }
-    ++d->pf_count;
+    ++d->q.count;
     return XRIT_OK;
 }
 
@@ -1115,12 +905,12 @@ int xrit_demod_process(xrit_demod *d, const void *samples, size_t n, int type, f
     const size_t esz = type == XRIT_SAMPLE_FLOATIQ ? 8 : (type == XRIT_SAMPLE_S16IQ ? 4 : 2);
     XR_TRY(d->in_dev.reserve(n * esz + 16));
     XR_TRY(d->soft_dev.reserve((cap + 1) * sizeof(float)));
-    if (n) XR_HIP(hipMemcpyAsync(d->in_dev.p, samples, n * esz, hipMemcpyHostToDevice, d->stream));
-    int rc = xrit_demod_process_device(d, d->in_dev.p, n, type, d->soft_dev.as<float>(), cap, n_out, d->stream);
+    if (n) XR_HIP(hipMemcpyAsync(d->in_dev.p, samples, n * esz, hipMemcpyHostToDevice, d->own[CHAIN_CALLER]));
+    int rc = xrit_demod_process_device(d, d->in_dev.p, n, type, d->soft_dev.as<float>(), cap, n_out, d->own[CHAIN_CALLER]);
     if (rc != XRIT_OK) return rc;
     if (*n_out)
-        XR_HIP(hipMemcpyAsync(soft_out, d->soft_dev.p, *n_out * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-    XR_HIP(hipStreamSynchronize(d->stream));
+        XR_HIP(hipMemcpyAsync(soft_out, d->soft_dev.p, *n_out * sizeof(float), hipMemcpyDeviceToHost, d->own[CHAIN_CALLER]));
+    XR_HIP(hipStreamSynchronize(d->own[CHAIN_CALLER]));
     return XRIT_OK;
 }
 
@@ -1135,7 +925,7 @@ int xrit_demod_read_stage(xrit_demod *d, int stage, float *out, size_t cap, size
     if (!out) return XRIT_OK;
     if (*n > cap) { set_error("stage %d holds %zu elements, capacity %zu", stage, *n, cap); return XRIT_E_CAPACITY; }
     XR_HIP(hipSetDevice(d->device));
-    XR_HIP(hipStreamSynchronize(d->stream));
+    XR_HIP(hipStreamSynchronize(d->own[CHAIN_CALLER]));
     if (*n) XR_HIP(hipMemcpy(out, d->stage_buf[stage].p, *n * sizeof(float2), hipMemcpyDeviceToHost));
     return XRIT_OK;
 }
@@ -1145,7 +935,7 @@ int xrit_demod_keep_stages(xrit_demod *d, int enable)
     if (!d) return XRIT_E_INVALID;
     // (what runs ahead of a registered input's call is chosen by these flags: a call whose Costas loop and walkers have already
     // been started as an overlap job must not be taken by the stage-keeping path afterwards)
-    if (d->pf_count > 0) { set_error("prefetched inputs wait for their process calls: stage copies are switched between plain calls"); return XRIT_E_INVALID; }
+    if (d->q.count > 0) { set_error("prefetched inputs wait for their process calls: stage copies are switched between plain calls"); return XRIT_E_INVALID; }
     d->keep_stages = enable == 1;
     d->keep_symbols = enable == 2;
     return XRIT_OK;
@@ -1197,83 +987,6 @@ int xrit_demod_profile_samples(xrit_demod *d, const char *name, float *ms, int c
     return n;
 }
 
-int xrit_quantize_i8_device(const float *d_soft, int8_t *d_out, size_t n, int device, void *stream)
-{
-    XR_TRY(select_device(device));
-    return launch_quantize_i8(d_soft, d_out, n, (hipStream_t)stream);
-}
-
-int xrit_sync_correlate_device(const int8_t *d_symbols, size_t n, const uint64_t *words, int nwords, uint32_t frame,
-                               xrit_sync_hit *d_hits, int device, void *stream)
-{
-    if (!words || (n >= frame && (!d_symbols || !d_hits))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    return launch_sync_correlate(d_symbols, n, reinterpret_cast<const unsigned long long *>(words), nwords, frame, d_hits,
-                                 (hipStream_t)stream);
-}
-
-int xrit_sync_correlate(const int8_t *symbols, size_t n, const uint64_t *words, int nwords, uint32_t frame,
-                        xrit_sync_hit *hits, int device)
-{
-    if (!words || frame == 0 || (n >= frame && (!symbols || !hits))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    const size_t nf = n / frame;
-    if (nf == 0) return XRIT_OK;
-    DevBuf din, dh;
-    int rc = din.reserve(nf * frame);
-    if (rc == XRIT_OK) rc = dh.reserve(nf * sizeof(xrit_sync_hit));
-    if (rc == XRIT_OK && hipMemcpy(din.p, symbols, nf * frame, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); rc = XRIT_E_HIP; }
-    if (rc == XRIT_OK)
-        rc = launch_sync_correlate(din.as<int8_t>(), nf * frame, reinterpret_cast<const unsigned long long *>(words), nwords, frame,
-                                   dh.as<xrit_sync_hit>(), nullptr);
-    if (rc == XRIT_OK && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpy(hits, dh.p, nf * sizeof(xrit_sync_hit), hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_error("sync: device error");
-        rc = XRIT_E_HIP;
-    }
-    din.release();
-    dh.release();
-    return rc;
-}
-
-int xrit_sync_fix_frames_device(const int8_t *d_symbols, size_t n, const xrit_sync_hit *d_hits, uint32_t frame,
-                                uint32_t min_correlation, int8_t *d_frames, uint8_t *d_valid, int device, void *stream)
-{
-    if (frame == 0 || (n >= frame && (!d_symbols || !d_hits || !d_frames || !d_valid))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    return launch_sync_fix(d_symbols, n, d_hits, frame, min_correlation, d_frames, d_valid, (hipStream_t)stream);
-}
-
-int xrit_sync_fix_frames(const int8_t *symbols, size_t n, const xrit_sync_hit *hits, uint32_t frame,
-                         uint32_t min_correlation, int8_t *frames, uint8_t *valid, int device)
-{
-    if (frame == 0 || (n >= frame && (!symbols || !hits || !frames || !valid))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    const size_t nf = n / frame;
-    if (nf == 0) return XRIT_OK;
-    DevBuf din, dh, dout, dv;
-    int rc = din.reserve(n + 8);
-    if (rc == XRIT_OK) rc = dh.reserve(nf * sizeof(xrit_sync_hit));
-    if (rc == XRIT_OK) rc = dout.reserve(nf * frame);
-    if (rc == XRIT_OK) rc = dv.reserve(nf);
-    if (rc == XRIT_OK && (hipMemcpy(din.p, symbols, n, hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(dh.p, hits, nf * sizeof(xrit_sync_hit), hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("hipMemcpy failed");
-        rc = XRIT_E_HIP;
-    }
-    if (rc == XRIT_OK)
-        rc = launch_sync_fix(din.as<int8_t>(), n, dh.as<xrit_sync_hit>(), frame, min_correlation, dout.as<int8_t>(),
-                             dv.as<unsigned char>(), nullptr);
-    if (rc == XRIT_OK && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpy(frames, dout.p, nf * frame, hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(valid, dv.p, nf, hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_error("sync: device error");
-        rc = XRIT_E_HIP;
-    }
-    din.release(); dh.release(); dout.release(); dv.release();
-    return rc;
-}
-
 int xrit_quantize_i8(xrit_demod *d, const float *soft, int8_t *out, size_t n)
 {
     if (!d || (n && (!soft || !out))) { set_error("null argument"); return XRIT_E_INVALID; }
@@ -1281,287 +994,10 @@ int xrit_quantize_i8(xrit_demod *d, const float *soft, int8_t *out, size_t n)
     XR_TRY(d->q_in.reserve(n * sizeof(float) + 16));
     XR_TRY(d->q_out.reserve(n + 16));
     if (!n) return XRIT_OK;
-    XR_HIP(hipMemcpyAsync(d->q_in.p, soft, n * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    XR_TRY(launch_quantize_i8(d->q_in.as<float>(), d->q_out.as<int8_t>(), n, d->stream));
-    XR_HIP(hipMemcpyAsync(out, d->q_out.p, n, hipMemcpyDeviceToHost, d->stream));
-    XR_HIP(hipStreamSynchronize(d->stream));
+    XR_HIP(hipMemcpyAsync(d->q_in.p, soft, n * sizeof(float), hipMemcpyHostToDevice, d->own[CHAIN_CALLER]));
+    XR_TRY(launch_quantize_i8(d->q_in.as<float>(), d->q_out.as<int8_t>(), n, d->own[CHAIN_CALLER]));
+    XR_HIP(hipMemcpyAsync(out, d->q_out.p, n, hipMemcpyDeviceToHost, d->own[CHAIN_CALLER]));
+    XR_HIP(hipStreamSynchronize(d->own[CHAIN_CALLER]));
     return XRIT_OK;
 }
-
-// ---------------------------------------------------------------- stage objects
-int xrit_fir_create(unsigned decimation, const float *taps, int ntaps, int device, xrit_fir **out)
-{
-    if (!taps || ntaps < 1 || !out) { set_error("bad argument"); return XRIT_E_INVALID; }
-    xrit_fir *f = new (std::nothrow) xrit_fir();
-    if (!f) return XRIT_E_NOMEM;
-    f->stream = nullptr;
-    int rc = stage_open(f, device);
-    if (rc == XRIT_OK) rc = f->st.init(taps, ntaps, (int)decimation);
-    if (rc != XRIT_OK) { stage_close(f); return rc; }
-    *out = f;
-    return XRIT_OK;
-}
-
-int xrit_fir_work(xrit_fir *f, const float *in, float *out, size_t n_out)
-{
-    if (!f || (n_out && (!in || !out))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(f->device));
-    size_t n_in = n_out * (size_t)f->st.D;
-    XR_TRY(f->in.reserve((n_in + 8) * sizeof(float2)));
-    XR_TRY(f->out.reserve((n_out + 8) * sizeof(float2)));
-    if (n_in) XR_HIP(hipMemcpyAsync(f->in.p, in, n_in * sizeof(float2), hipMemcpyHostToDevice, f->stream));
-    XR_TRY(f->st.run(f->in.p, XRIT_SAMPLE_FLOATIQ, f->out.as<float2>(), n_out, f->stream, nullptr));
-    if (n_out) XR_HIP(hipMemcpyAsync(out, f->out.p, n_out * sizeof(float2), hipMemcpyDeviceToHost, f->stream));
-    XR_HIP(hipStreamSynchronize(f->stream));
-    return XRIT_OK;
-}
-
-int xrit_fir_set_exact(xrit_fir *f, int exact)
-{
-    if (!f) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(f->device));
-    XR_HIP(hipStreamSynchronize(f->stream));
-    return f->st.set_exact(exact != 0);
-}
-
-void xrit_fir_destroy(xrit_fir *f) { stage_close(f); }
-
-int xrit_agc_create(float rate, float reference, float gain, float max_gain, int device, xrit_agc **out)
-{
-    if (!out) return XRIT_E_INVALID;
-    xrit_agc *a = new (std::nothrow) xrit_agc();
-    if (!a) return XRIT_E_NOMEM;
-    a->stream = nullptr;
-    int rc = stage_open(a, device);
-    if (rc == XRIT_OK) rc = a->st.init(rate, reference, gain, max_gain);
-    if (rc != XRIT_OK) { stage_close(a); return rc; }
-    *out = a;
-    return XRIT_OK;
-}
-
-int xrit_agc_work(xrit_agc *a, const float *in, float *out, size_t n)
-{
-    if (!a || (n && (!in || !out))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(a->device));
-    XR_TRY(a->in.reserve((n + 8) * sizeof(float2)));
-    XR_TRY(a->out.reserve((n + 8) * sizeof(float2)));
-    if (n) XR_HIP(hipMemcpyAsync(a->in.p, in, n * sizeof(float2), hipMemcpyHostToDevice, a->stream));
-    XR_TRY(a->st.run(a->in.as<float2>(), a->out.as<float2>(), n, a->stream, nullptr));
-    if (n) XR_HIP(hipMemcpyAsync(out, a->out.p, n * sizeof(float2), hipMemcpyDeviceToHost, a->stream));
-    XR_HIP(hipStreamSynchronize(a->stream));
-    return XRIT_OK;
-}
-
-int xrit_agc_set_exact(xrit_agc *a, int exact)
-{
-    if (!a) { set_error("null argument"); return XRIT_E_INVALID; }
-    a->st.exact = exact != 0;
-    return XRIT_OK;
-}
-
-int xrit_agc_exact_stats(xrit_agc *a, uint32_t *counters8)
-{
-    if (!a || !counters8) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(a->device));
-    return a->st.exact_counters(counters8, a->stream);
-}
-
-float xrit_agc_gain(xrit_agc *a)
-{
-    float g = NAN;
-    if (!a) return g;
-    (void)hipSetDevice(a->device);
-    (void)a->st.gain(&g, a->stream);
-    return g;
-}
-
-void xrit_agc_destroy(xrit_agc *a) { stage_close(a); }
-
-int xrit_costas_create(float loop_bw, int order, int device, xrit_costas **out)
-{
-    if (!out) return XRIT_E_INVALID;
-    if (order != 2) { set_error("only the 2nd-order (BPSK) loop is implemented, as the reference uses (LOOP_ORDER 2)"); return XRIT_E_INVALID; }
-    xrit_costas *c = new (std::nothrow) xrit_costas();
-    if (!c) return XRIT_E_NOMEM;
-    c->stream = nullptr;
-    int rc = stage_open(c, device);
-    if (rc == XRIT_OK) rc = c->st.init(loop_bw, 0, 0);
-    if (rc != XRIT_OK) { stage_close(c); return rc; }
-    *out = c;
-    return XRIT_OK;
-}
-
-int xrit_costas_work(xrit_costas *c, const float *in, float *out, size_t n)
-{
-    if (!c || (n && (!in || !out))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(c->device));
-    XR_TRY(c->in.reserve((n + 8) * sizeof(float2)));
-    XR_TRY(c->out.reserve((n + 8) * sizeof(float2)));
-    if (n) XR_HIP(hipMemcpyAsync(c->in.p, in, n * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-    XR_TRY(c->st.run(c->in.as<float2>(), c->out.as<float2>(), n, c->stream, nullptr));
-    if (n) XR_HIP(hipMemcpyAsync(out, c->out.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-    XR_HIP(hipStreamSynchronize(c->stream));
-    return XRIT_OK;
-}
-
-int xrit_loop_sincosf(const float *x, float *sin_out, float *cos_out, size_t n, int device)
-{
-    if (n && (!x || !sin_out || !cos_out)) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    if (n == 0) return XRIT_OK;
-    DevBuf dx, ds, dc;
-    int rc = dx.reserve(n * sizeof(float));
-    if (rc == XRIT_OK) rc = ds.reserve(n * sizeof(float));
-    if (rc == XRIT_OK) rc = dc.reserve(n * sizeof(float));
-    if (rc == XRIT_OK && hipMemcpy(dx.p, x, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); rc = XRIT_E_HIP; }
-    if (rc == XRIT_OK) rc = launch_loop_sincosf(dx.as<float>(), ds.as<float>(), dc.as<float>(), n, nullptr);
-    if (rc == XRIT_OK && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpy(sin_out, ds.p, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(cos_out, dc.p, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_error("loop_sincosf: device error");
-        rc = XRIT_E_HIP;
-    }
-    dx.release(); ds.release(); dc.release();
-    return rc;
-}
-
-int xrit_costas_set_exact(xrit_costas *c, int exact, int history)
-{
-    if (!c) { set_error("null argument"); return XRIT_E_INVALID; }
-    if (history < 0) { set_error("history = %d", history); return XRIT_E_INVALID; }
-    c->st.exact = exact != 0;
-    c->st.ex_hist = history > 0 ? history : -1;
-    return XRIT_OK;
-}
-
-int xrit_costas_exact_stats(xrit_costas *c, uint64_t *blocks, uint64_t *rounds, uint32_t *joints_open, uint32_t *fix_rounds,
-                            uint64_t *lattice_segments, uint64_t *lattice_fallbacks)
-{
-    if (!c) { set_error("null argument"); return XRIT_E_INVALID; }
-    if (blocks) *blocks = c->st.ex_blocks;
-    if (rounds) *rounds = c->st.ex_picard;
-    if (joints_open) *joints_open = c->st.ex_open;
-    if (fix_rounds) *fix_rounds = (uint32_t)c->st.ex_rounds;
-    if (lattice_segments) *lattice_segments = c->st.ex_segs;
-    if (lattice_fallbacks) *lattice_fallbacks = c->st.ex_fallbacks;
-    return XRIT_OK;
-}
-
-int xrit_costas_state(xrit_costas *c, float *phase, float *freq)
-{
-    if (!c || !phase || !freq) return XRIT_E_INVALID;
-    XR_HIP(hipSetDevice(c->device));
-    return c->st.get_state(phase, freq, c->stream);
-}
-
-void xrit_costas_destroy(xrit_costas *c) { stage_close(c); }
-
-int xrit_clock_create(float omega, float gain_omega, float mu, float gain_mu, float omega_rel_limit, int device,
-                      xrit_clock **out)
-{
-    if (!out || !(omega >= 1.0f)) { set_error("bad argument"); return XRIT_E_INVALID; }
-    xrit_clock *c = new (std::nothrow) xrit_clock();
-    if (!c) return XRIT_E_NOMEM;
-    c->stream = nullptr;
-    int rc = stage_open(c, device);
-    if (rc == XRIT_OK) rc = c->st.init(omega, gain_omega, mu, gain_mu, omega_rel_limit, 0, 0);
-    if (rc != XRIT_OK) { stage_close(c); return rc; }
-    c->st.ov_allow = false;         // (the stage object hands out complex symbols: ClockRecovery::Work's output)
-    *out = c;
-    return XRIT_OK;
-}
-
-int xrit_clock_work(xrit_clock *c, const float *in, size_t n, float *out, size_t cap, size_t *n_out)
-{
-    if (!c || !n_out || (n && !in)) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(c->device));
-    float2 *slot = nullptr;
-    XR_TRY(c->st.input_slot(n, &slot, c->stream));
-    if (n) XR_HIP(hipMemcpyAsync(slot, in, n * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-    XR_TRY(c->out.reserve((cap + 8) * sizeof(float2)));
-    XR_TRY(c->st.run(n, nullptr, c->out.as<float2>(), cap, n_out, c->stream, nullptr));
-    if (*n_out && out)
-        XR_HIP(hipMemcpyAsync(out, c->out.p, *n_out * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-    XR_HIP(hipStreamSynchronize(c->stream));
-    return XRIT_OK;
-}
-
-int xrit_clock_set_serial(xrit_clock *c, int serial)
-{
-    if (!c) return XRIT_E_INVALID;
-    c->st.serial = serial != 0;
-    return XRIT_OK;
-}
-
-int xrit_clock_set_exact(xrit_clock *c, int exact, int window)
-{
-    if (!c) return XRIT_E_INVALID;
-    if (exact < -3) { set_error("clock_exact = %d: -3 .. n (see xrit_demod_config.clock_exact)", exact); return XRIT_E_INVALID; }
-    c->st.exact = exact == -3 ? 0 : exact;          // (-3: the default's plan, its first relay passes approximate -- as in xrit_demod_create)
-    c->st.relay_quick = exact == -3;
-    c->st.relay_window = window > 0 ? window : 0;
-    return XRIT_OK;
-}
-
-void xrit_clock_destroy(xrit_clock *c) { stage_close(c); }
-
-int xrit_rtl_create(float sample_rate, int device, xrit_rtl **out)
-{
-    if (!out || !(sample_rate > 0)) { set_error("bad argument"); return XRIT_E_INVALID; }
-    xrit_rtl *r = new (std::nothrow) xrit_rtl();
-    if (!r) return XRIT_E_NOMEM;
-    r->stream = nullptr;
-    int rc = stage_open(r, device);
-    if (rc == XRIT_OK) rc = r->st.init(sample_rate);
-    if (rc != XRIT_OK) { stage_close(r); return rc; }
-    *out = r;
-    return XRIT_OK;
-}
-
-int xrit_rtl_work(xrit_rtl *r, const uint8_t *data, size_t n_complex, float *out_iq)
-{
-    if (!r || (n_complex && (!data || !out_iq))) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_HIP(hipSetDevice(r->device));
-    XR_TRY(r->in.reserve(2 * n_complex + 16));
-    XR_TRY(r->out.reserve((n_complex + 8) * sizeof(float2)));
-    if (n_complex) XR_HIP(hipMemcpyAsync(r->in.p, data, 2 * n_complex, hipMemcpyHostToDevice, r->stream));
-    XR_TRY(r->st.run(r->in.p, r->out.as<float2>(), n_complex, r->stream, nullptr));
-    if (n_complex) XR_HIP(hipMemcpyAsync(out_iq, r->out.p, n_complex * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
-    XR_HIP(hipStreamSynchronize(r->stream));
-    return XRIT_OK;
-}
-
-void xrit_rtl_destroy(xrit_rtl *r) { stage_close(r); }
-
-// ---------------------------------------------------------------- synth
-void xrit_synth_defaults(xrit_synth_params *p)
-{
-    if (!p) return;
-    p->fs_in = 1.25e6;
-    p->symbol_rate = 293883.0;
-    p->alpha = 0.5;
-    p->amplitude = 0.1;
-    p->carrier_hz = 500.0;
-    p->phase0 = 0.7;
-    p->timing_offset = 0.3;
-    p->clock_ppm = 20.0;
-    p->esn0_db = 12.0;
-    p->seed = 0x58524954ull;
-}
-
-int xrit_synth_generate_device(const xrit_synth_params *p, uint64_t start, size_t n, float *d_out, int device,
-                               void *stream)
-{
-    if (!p || (n && !d_out)) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    return launch_synth(*p, start, n, reinterpret_cast<float2 *>(d_out), (hipStream_t)stream);
-}
-
-int xrit_device_read_bandwidth(const void *d_buf, size_t bytes, int reps, int device, void *stream, double *gb_per_s)
-{
-    if (!d_buf || !gb_per_s) { set_error("null argument"); return XRIT_E_INVALID; }
-    XR_TRY(select_device(device));
-    return launch_read_bw(d_buf, bytes, reps, (hipStream_t)stream, gb_per_s);
-}
-
 }  // extern "C"
