@@ -682,7 +682,9 @@ int xrit_packets_reset(xrit_packets *pa);
 /* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
  * behind xrit_demux_process_device, which hands it its row count in d_offsets[64] on the device.  max_rows (<= 2^24)
  * is the host's bound on that count (the demux call's nf): launches and scratch are sized from it; a larger
- * d_offsets[64] raises overflow = 2 in the summary and nothing else is written, the state unchanged.
+ * d_offsets[64] raises overflow = 2 in the summary (packets = bytes = 0, the counters the handle's) and all 65
+ * entries of d_pkt_offsets are written as zeros, so that a files call queued behind sees no packets; nothing else is
+ * written, the state unchanged.
  * d_bytes: max_bytes; d_packets: max_packets descriptors, 8-byte aligned; d_pkt_offsets: 65 entries, the exclusive
  * prefix of the per-channel packet counts; d_summary: 8-byte aligned.  Capacity: descriptor k is written iff
  * k < max_packets, a packet's bytes iff offset + length <= max_bytes; the summary carries the true counts and

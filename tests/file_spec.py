@@ -6,6 +6,8 @@ The reference decoder ends at the VCDU, so this layer is specified here, from th
 primary header record, the image structure record) and the GOES mission specific record 131 (Rice compression).  The
 field offsets are as we read those documents; no recorded downlink was at hand (DESIGN.md lists what is unverified).
 `process` is the serial statement, one packet at a time, and the device must equal it byte for byte."""
+import copy
+
 import numpy as np
 
 import packet_spec as ps
@@ -449,3 +451,55 @@ def damage(rng, stream, share=0.02):
             one = short_first(one, 0, rng)
         out.extend(one)
     return out
+
+
+# ---- generators that reach what the random ones leave to chance -------------------------------------------------------
+MANY = [(v, a) for v in (0, 1, 5, 30, 62) for a in (0, 1, 2, 63, 64, 65, 700, 1023, 1024, 2046, 2047)]
+# user data per packet: on either side of the device's 2048-byte gather step and of two such steps, what real LRIT
+# packets carry (8190), and close to the most a space packet can (65534)
+LONG_USERS = (2047, 2048, 2049, 4095, 4096, 4097, 8190, 65524)
+
+
+def long_piece_stream(seed=0, count=600, keys=tuple(MANY[6:12]), share=0.01):
+    """`count` packets of generated files over the keys, lightly damaged, every batch of six files cut every LONG_USERS[i]
+    bytes and long enough to span several such packets.  -> (stream, the generated files as a set of bytes)."""
+    rng = np.random.default_rng([seed, 5])
+    stream, files, i = [], set(), 0
+    while len(stream) < count + count // 8 + 8:
+        mu = LONG_USERS[i % len(LONG_USERS)]
+        i += 1
+        s, f = random_stream(rng, 6, list(keys), max_bytes=6 * mu, max_user=mu)
+        stream += s
+        files |= set(f.values())
+    return damage(rng, stream, share)[:count], files
+
+
+def many_pieces_stream(seed=0, count=60000, share=0.005, tail=4000, long_keys=tuple(MANY[-6:])):
+    """`count` packets of generated files over MANY, lightly damaged, 60 bytes of user data each, so that one call emits
+    far more pieces than the device's gather grid takes in one pass (4096 workgroups of 8); among the last `tail` packets
+    files cut every 8190 bytes on keys that sort last: long pieces for the second pass."""
+    rng = np.random.default_rng([seed, 6])
+    stream = []
+    while len(stream) < count - tail:
+        stream += random_stream(rng, 12, MANY, max_bytes=12000, max_user=60)[0]
+    stream = stream[:count - tail]
+    while len(stream) < count + count // 8:
+        stream += random_stream(rng, 3, MANY, max_bytes=12000, max_user=60)[0]
+        stream += random_stream(rng, 8, list(long_keys), max_bytes=50000, max_user=8190)[0]
+    return damage(rng, stream, share)[:count]
+
+
+_CACHE = {}
+
+
+def many_pieces_case():
+    """The stage's input for many_pieces_stream() and what the specification makes of it in one call and in the same call
+    once more behind it: (args, [(result, state after it)] for the two calls), computed once for all the tests."""
+    if "many" not in _CACHE:
+        args = stage_input(many_pieces_stream())
+        st, runs = State(), []
+        for _ in range(2):
+            res = process(st, *args)
+            runs.append((res, copy.deepcopy(st)))
+        _CACHE["many"] = (args, runs)
+    return _CACHE["many"]

@@ -338,6 +338,160 @@ def group(rows_by_vc):
     return vcdu, offsets
 
 
+# ---- generators that reach what the random ones leave to chance -------------------------------------------------------
+# (total, zone offset of the long packet's first byte): ten rows; the longest packet with one byte in its last row, so
+# that a cut in front of that row leaves 65541 bytes pending; the longest packet beginning 1, 3, 4, 5 bytes before a
+# zone's end: the header split by the rows' joint, with 5 the length field itself
+LONG_CASES = {"ten_rows": (8198, 300), "one_byte_last": (PACKET_MAX, 759), "tail_1": (PACKET_MAX, ZONE - 1),
+              "tail_3": (PACKET_MAX, ZONE - 3), "tail_4": (PACKET_MAX, ZONE - 4), "tail_5": (PACKET_MAX, ZONE - 5)}
+
+
+def long_packet_stream(case, vcid=5, seed=0):
+    """-> (Stream, index of the long packet in its .packets): one channel without fill packets between the packets or
+    idle zones: three short packets that end where the long one is to begin, the long one, three short ones."""
+    total, start = LONG_CASES[case]
+    rng = np.random.default_rng([seed, total, start, vcid])
+    front = start if start >= 21 else start + ZONE
+    sizes = [front // 3, front // 3, front - 2 * (front // 3)] + [total] + [40, 60, 80]
+    pkts = [make_packet(20 + i % 3, i, n, rng) for i, n in enumerate(sizes)]
+    st = build_stream(vcid, pkts, rng, fill=0.0, idle=0.0)
+    assert [p for p, _, _ in st.packets] == pkts and st.packets[3][1] == front // ZONE
+    return st, 3
+
+
+def rows_of(st):
+    return [bytes(r) for r in st.rows]
+
+
+def with_fhp(row, fhp):
+    """The row under another first header pointer (the spare bits kept)."""
+    r = bytearray(row)
+    r[6], r[7] = (r[6] & 0xF8) | fhp >> 8, fhp & 255
+    return bytes(r)
+
+
+def with_counter(row, counter):
+    r = bytearray(row)
+    r[2], r[3], r[4] = counter >> 16 & 255, counter >> 8 & 255, counter & 255
+    return bytes(r)
+
+
+def counter_of(row):
+    return row[2] << 16 | row[3] << 8 | row[4]
+
+
+def run_calls(calls, state=None):
+    """The calls ({vcid: rows} each) through the specification.  -> (state, [(result of process, the pending lengths
+    after the call)])."""
+    state = State() if state is None else state
+    out = []
+    for part in calls:
+        res = process(state, *group(part))
+        out.append((res, [len(p) for p in state.pending]))
+    return state, out
+
+
+def joint_damage(case, vcid=5):
+    """[(name, first call, second call)] as row lists: a long packet's rows cut at a handful of places, the second call
+    beginning with a row that does not continue what the first one left pending."""
+    st, k = long_packet_stream(case, vcid)
+    rows = rows_of(st)
+    _, a, b = st.packets[k]
+    out = []
+    for c in sorted({a + 1, a + 2, (a + b) // 2, b}):
+        head, rest = rows[:c], rows[c:]
+        if len(rest) > 1:
+            out.append((f"{c}_skipped_counter", head, rest[1:]))
+        out.append((f"{c}_repeated_row", head, [rows[c - 1]] + rest))
+        for fhp in (0, 400, FHP_IDLE, 1000, 2045):
+            out.append((f"{c}_fhp_{fhp}", head, [with_fhp(rest[0], fhp)] + rest[1:]))
+        if c < b:
+            # the packet's last row, with its right pointer and the next counter, in front of the zones it needs
+            moved = with_counter(rows[b], counter_of(rows[c]))
+            out.append((f"{c}_early_end", head, [moved] + [with_counter(r, (counter_of(r) + 1) & 0xFFFFFF) for r in rest]))
+    _, start = LONG_CASES[case]
+    if ZONE - start < 6:
+        # the length field's low byte lies in the second row's zone: the right pointer (2047), another length
+        at = 8 + 5 - (ZONE - start)
+        for flip in (0x01, 0x80):
+            r = bytearray(rows[a + 1])
+            r[at] ^= flip
+            out.append((f"{a + 1}_length_{flip}", rows[:a + 1], [bytes(r)] + rows[a + 2:]))
+    return out
+
+
+def three_call_cases(seed=0, count=30):
+    """[(c1, c2, calls)], calls three {vcid: rows}: channel 5 carries LONG_CASES["one_byte_last"] cut in front of rows
+    c1 <= c2 that both lie inside the long packet, so the first call leaves it pending, the second brings only rows
+    with pointer 2047 (none where c1 == c2) and the third ends it; channel 9 carries "tail_5" cut likewise at places of
+    its own, always with rows in the middle call; channel 63 has rows in every call.  -> (cases, {vcid: Stream})."""
+    rng = np.random.default_rng([seed, 3])
+    sa, ka = long_packet_stream("one_byte_last", 5)
+    sb, kb = long_packet_stream("tail_5", 9)
+    ra, rb = rows_of(sa), rows_of(sb)
+    (_, a0, a1), (_, b0, b1) = sa.packets[ka], sb.packets[kb]
+    pairs = [(a0 + 1, a0 + 1), (a1, a1), (a0 + 1, a1), (a0 + 1, a0 + 2), (a1 - 1, a1), (a0 + 37, a0 + 37)]
+    while len(pairs) < count:
+        c1 = int(rng.integers(a0 + 1, a1 + 1))
+        pairs.append((c1, c1 if rng.random() < 0.15 else int(rng.integers(c1, a1 + 1))))
+    cases = []
+    for c1, c2 in pairs:
+        d1 = int(rng.integers(b0 + 1, b1))
+        d2 = int(rng.integers(d1 + 1, b1 + 1))
+        junk = [[bytes(r) for r in rng.integers(0, 256, (int(rng.integers(1, 4)), VCDU_BYTES), dtype=np.uint8)] for _ in range(3)]
+        cases.append((c1, c2, [{5: ra[:c1], 9: rb[:d1], 63: junk[0]}, {5: ra[c1:c2], 9: rb[d1:d2], 63: junk[1]},
+                               {5: ra[c2:], 9: rb[d2:], 63: junk[2]}]))
+    return cases, {5: sa, 9: sb}
+
+
+def chunks_of(total):
+    """The 4096-byte steps in which the device runs a packet's CRC (they end where the CRC's two bytes begin)."""
+    return -(-(total - 2) // 4096) if total >= 8 else 0
+
+
+# every total around the first two chunk edges: the zeroed header and the initial value's XOR on data bytes 6 and 7 fall
+# on either side of them; the two-byte CRC on either side of a step's end
+LADDER_EDGES = list(range(4097, 4108)) + list(range(8193, 8204))
+# one total per chunk count 4 .. 16: the first chunk holding 1, 6, 7, 8 bytes, an exact edge, the others anywhere
+LADDER_STEPS = [4096 * 3 + 2 + 1, 4096 * 5 + 2, 4096 * 5 + 2 + 6, 4096 * 6 + 2 + 7, 4096 * 7 + 2 + 8] + \
+    [4096 * (m - 1) + 2 + (977 * m) % 4096 for m in range(9, 17)]
+LADDER = LADDER_EDGES + LADDER_STEPS + [PACKET_MAX - 1]
+assert [chunks_of(t) for t in LADDER_STEPS] == list(range(4, 17))
+
+
+def crc_ladder(flip=False, seed=0):
+    """-> ({vcid: Stream}, long): a good-CRC packet of every total in LADDER on channels 5 and 30, short packets between
+    them so that they begin at varied zone offsets; `long` the generated long packets.  With flip, the same packets with
+    one bit of one data byte of every long packet changed (the first data bytes, the last, the bytes on either side of the
+    last chunk's beginning, one in the middle, in turn)."""
+    rng = np.random.default_rng([seed, 4])
+    totals = [LADDER[i] for i in rng.permutation(len(LADDER))]
+    packets, long = [], []
+    for i, total in enumerate(totals):
+        v = (5, 30)[i % 2]
+        for _ in range(int(rng.integers(1, 4))):
+            packets.append((v, make_packet(1 + i % 5, len(packets), int(rng.integers(7, 300)), rng)))
+        p = make_packet(100 + i % 7, i, total, rng)
+        if flip:
+            e = total - 2
+            at = min(max((6, 7, e - 1, e - 4096, e - 4097, (6 + e) // 2)[i % 6], 6), e - 1)
+            p = p[:at] + bytes([p[at] ^ 1 << (i % 8)]) + p[at + 1:]
+        long.append(p)
+        packets.append((v, p))
+    return build_streams(packets, rng, fill=0.0, idle=0.0), long
+
+
+_LADDER_CRC = {}
+
+
+def ladder_crcs():
+    """{packet: the CRC of its data field by the definition, bit by bit} for crc_ladder()'s long packets, computed once
+    for all the tests."""
+    if not _LADDER_CRC:
+        _LADDER_CRC.update({p: crc16(p[6:-2]) for p in crc_ladder()[1]})
+    return _LADDER_CRC
+
+
 def block_of(vcdu_row):
     """The 1020-byte RS block around a given VCDU (ccsds.make_block fills its own with random bytes)."""
     data = np.frombuffer(bytes(vcdu_row), np.uint8)

@@ -193,3 +193,31 @@ def test_random_packets_never_raise_and_stay_within_the_input():
     col, st, recs, s = run(stream, cuts=50, rng=rng)
     assert s["files_begun"] > 50 and s["files_aborted"] > 10 and s["orphans"] > 10 and s["short_first"] > 10
     assert s["bad_packets"] > 50 and {int(r["header_state"]) for r in recs} == {0, 1, 2}
+
+
+# ---- the generators of the GPU tier reach what they are there for ------------------------------------------------------
+def test_long_piece_stream_has_pieces_around_the_gather_steps():
+    stream, files = fs.long_piece_stream()
+    assert len(stream) == 600
+    col, state, recs, s = run(stream)
+    data, pieces, _, _ = fs.process(fs.State(), *fs.stage_input(stream))
+    lengths = {int(x) for x in pieces["length"]}
+    assert {2047, 2048, 2049, 4095, 4096, 4097, 8190, 65524} <= lengths and max(lengths) == 65524
+    assert len(pieces) >= 500 and int((pieces["length"] > 2048).sum()) >= 250 and len(data) > 2_000_000
+    # the files that came through whole are generated ones, and there are many of them, over several pieces
+    whole = [d for d in col.done if d[4]["flags"] & fs.LENGTH_MATCH]
+    assert len(whole) >= 100 and all(d[3] in files for d in whole)
+    assert sum(len(d[3]) > 3 * 2048 for d in whole) >= 50
+    # ... and in calls cut at random the same ones
+    col2 = run(stream, cuts=40, rng=np.random.default_rng(16))[0]
+    assert sorted(d[:4] for d in col2.done) == sorted(d[:4] for d in col.done)
+
+
+def test_many_pieces_stream_emits_more_than_one_gather_pass():
+    args, runs = fs.many_pieces_case()
+    assert len(args[1]) == 60000
+    for (data, pieces, files, summary), state in runs:
+        assert summary["pieces"] == len(pieces) >= 40000 > 4096 * 8
+        # the second pass moves long pieces too
+        assert int((pieces["length"][4096 * 8:] > 2048).sum()) >= 100 and int(pieces["length"][4096 * 8:].max()) == 8190
+    assert runs[1][1].total_pieces == runs[0][0][3]["pieces"] + runs[1][0][3]["pieces"] and runs[0][1].open_files() > 0

@@ -1,5 +1,6 @@
 """GPU tier: the file assembler (xrit_files_*, FileAssembler) against the specification of tests/file_spec.py -- generator
-streams with every kind of damage at tile-edge packet counts over one key and many, packets of random bytes, calls cut
+streams with every kind of damage at tile-edge packet counts over one key and many, pieces longer than a gather step, more
+pieces than one pass of the gather grid, packets of random bytes, calls cut
 at random with the state compared after every call, reset, several handles, every capacity, the device path behind
 decoder, demultiplexer and packet assembler on one stream.  Every comparison is exact."""
 import numpy as np
@@ -11,7 +12,7 @@ import packet_spec as ps
 
 pytestmark = pytest.mark.gpu
 
-MANY = [(v, a) for v in (0, 1, 5, 30, 62) for a in (0, 1, 2, 63, 64, 65, 700, 1023, 1024, 2046, 2047)]
+MANY = fs.MANY
 
 
 @pytest.fixture(scope="module")
@@ -70,6 +71,47 @@ def test_one_call_matches_spec(xa, count, keys):
     # ... and once more behind itself: open files and sequence counts in front of the same packets
     same(fa.process(*args), fs.process(st, *args))
     same_state(fa, st)
+    fa.close()
+
+
+def test_long_pieces_in_one_call_and_in_cut_calls(xa):
+    """Pieces on either side of the gather's 2048-byte step and of two steps, of 8190 bytes and of 65524 (the generator
+    and what it reaches: file_spec.long_piece_stream, checked in test_file_spec.py)."""
+    stream, generated = fs.long_piece_stream()
+    args = fs.stage_input(stream)
+    fa, st = xa.FileAssembler(), fs.State()
+    res = fa.process(*args)
+    same(res, fs.process(st, *args))
+    same_state(fa, st)
+    assert int(res[1]["length"].max()) == 65524 and int((res[1]["length"] > 2048).sum()) >= 250
+    one = fs.Collector()
+    one.add(*res[:3])
+    fa.reset()
+    st, col = fs.State(), fs.Collector()
+    rng = np.random.default_rng(37)
+    for part in fs.cut_calls(rng, stream, 40):
+        args = fs.stage_input(part)
+        res = fa.process(*args)
+        same(res, fs.process(st, *args))
+        same_state(fa, st)
+        col.add(*res[:3])
+    # the files that came through whole are generated ones, cut or not
+    for c in (one, col):
+        whole = [d[3] for d in c.done if d[4]["flags"] & fs.LENGTH_MATCH]
+        assert len(whole) >= 100 and all(f in generated for f in whole)
+    assert sorted(d[:4] for d in col.done) == sorted(d[:4] for d in one.done)
+    fa.close()
+
+
+def test_more_pieces_than_one_pass_of_the_gather_grid(xa):
+    """A call of more than 4096 x 8 pieces, long ones among those beyond (file_spec.many_pieces_case, checked in
+    test_file_spec.py), and the same call once more behind itself."""
+    args, runs = fs.many_pieces_case()
+    assert runs[0][0][3]["pieces"] >= 40000
+    fa = xa.FileAssembler()
+    for want, st in runs:
+        same(fa.process(*args), want)
+        same_state(fa, st)
     fa.close()
 
 

@@ -1,6 +1,7 @@
 """GPU tier: the packet assembler (xrit_packets_*, PacketAssembler) against the specification of tests/packet_spec.py --
 generator streams with lost, repeated and damaged rows at tile-edge sizes and VCID mixes, rows of random bytes, calls
-cut at random, reset, several handles, the capacities, the device path behind decoder and demultiplexer, the chain from
+cut at random, a long packet cut at every row and carried over three calls, damage at the joint, every count of CRC
+chunks, reset, several handles, the capacities, the row bound, the device path behind decoder and demultiplexer, the chain from
 IQ and the host program.  Every comparison is exact."""
 import os
 import subprocess
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 import ccsds
+import file_spec as fs
 import packet_spec as ps
 import synth
 
@@ -221,6 +223,175 @@ def test_capacity(xa):
     pa = xa.PacketAssembler()
     same(pa.process(*ps.group(first), max_packets=n, max_bytes=nb), w1)
     pa.close()
+
+
+# ---- a long packet across calls, the CRC's chunks, the row bound (generators and what they reach: packet_spec.py, checked
+# in test_packet_spec.py) ------------------------------------------------------------------------------------------------
+def run_calls(xa, pa, calls):
+    """A reset handle through the calls ({vcid: rows} each), after every one against the specification.  -> (the
+    packets emitted per channel, their descriptors, the specification's state)."""
+    pa.reset()
+    st = ps.State()
+    got, descs = {}, []
+    for part in calls:
+        vcdu, off = ps.group(part)
+        res = pa.process(vcdu, off)
+        same(res, ps.process(st, vcdu, off))
+        same_state(xa, pa, st)
+        for p, d in zip(pa.split(res[0], res[1]), res[1]):
+            got.setdefault(int(d["vcid"]), []).append(p)
+        descs.append(res[1])
+    return got, np.concatenate(descs), st
+
+
+@pytest.mark.parametrize("case", list(ps.LONG_CASES))
+def test_long_packet_cut_at_every_row(xa, case):
+    stream, k = ps.long_packet_stream(case)
+    rows = ps.rows_of(stream)
+    want = [p for p, _, _ in stream.packets]
+    pa = xa.PacketAssembler()
+    longest = 0
+    for c in range(1, len(rows)):
+        got, desc, st = run_calls(xa, pa, [{5: rows[:c]}, {5: rows[c:]}])
+        assert got == {5: want} and (desc["crc_ok"] == 1).all(), c          # the generated packets, byte for byte
+        assert int(desc["first_counter"][k]) == ps.counter_of(rows[stream.packets[k][1]])
+        longest = max(longest, int(desc["length"].max()))
+    assert longest == ps.LONG_CASES[case][0]
+    pa.close()
+
+
+def test_long_packets_over_three_calls(xa):
+    cases, streams = ps.three_call_cases()
+    want = {v: [p for p, _, _ in s.packets] for v, s in streams.items()}
+    pa = xa.PacketAssembler()
+    for c1, c2, calls in cases:
+        got, desc, st = run_calls(xa, pa, calls)
+        assert got == want and (desc["crc_ok"] == 1).all(), (c1, c2)
+    pa.close()
+
+
+@pytest.mark.parametrize("case", ["ten_rows", "one_byte_last", "tail_5", "tail_1"])
+def test_damage_at_the_joint(xa, case):
+    stream, k = ps.long_packet_stream(case)
+    first_row = stream.packets[k][1]
+    pa = xa.PacketAssembler()
+    for name, head, rest in ps.joint_damage(case):
+        got, desc, st = run_calls(xa, pa, [{5: head}, {5: rest}])
+        assert st.discarded[5] >= 1, name
+        assert (stream.packets[k][0] in got.get(5, [])) == (name == f"{first_row + 1}_repeated_row"), name
+    pa.close()
+
+
+def ladder_input(flip):
+    streams, long = ps.crc_ladder(flip=flip)
+    return ps.group({v: s.rows for v, s in streams.items()}), long
+
+
+def test_crc_ladder(xa):
+    (vcdu, off), long = ladder_input(False)
+    pa = xa.PacketAssembler()
+    st = ps.State()
+    res, want = pa.process(vcdu, off), ps.process(st, vcdu, off)
+    same(res, want)
+    same_state(xa, pa, st)
+    data, desc = res[0], res[1]
+    assert (desc["crc_ok"] == 1).all() and sorted(int(n) for n in desc["length"] if n > 4096) == sorted(ps.LADDER)
+    assert {ps.chunks_of(int(n)) for n in desc["length"]} == set(range(1, 18))
+    packets = pa.split(data, desc)
+    assert sorted(p for p in packets if len(p) > 4096) == sorted(long)      # the generated packets, byte for byte
+    bitwise = ps.ladder_crcs()                                  # the definition, bit by bit
+    for p, d in zip(packets, desc):
+        if len(p) > 4096:
+            assert int(d["crc_computed"]) == bitwise[p], len(p)
+    # one bit of every long packet changed: the computed CRC follows the data, the carried one stays
+    (vcdu2, off2), bad = ladder_input(True)
+    pa.reset()
+    st = ps.State()
+    res2, want2 = pa.process(vcdu2, off2), ps.process(st, vcdu2, off2)
+    same(res2, want2)
+    same_state(xa, pa, st)
+    is_long = res2[1]["length"] > 4096
+    assert is_long.sum() == len(ps.LADDER) and (res2[1]["crc_ok"][is_long] == 0).all() and (res2[1]["crc_ok"][~is_long] == 1).all()
+    assert np.array_equal(res2[1]["crc_computed"], want2[1]["crc_computed"])
+    assert np.array_equal(res2[1]["crc_carried"], desc["crc_carried"])
+    assert (res2[1]["crc_computed"][is_long] != desc["crc_computed"][is_long]).all()
+    pa.close()
+
+
+def test_more_rows_than_the_bound_changes_nothing(xa):
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(27)
+    sa, ka = ps.long_packet_stream("ten_rows", 5)
+    sb, _ = ps.long_packet_stream("tail_5", 9)
+    ra, rb = ps.rows_of(sa), ps.rows_of(sb)
+    # an earlier call: pending bytes on two channels, counters; the file assembler behind has seen a call too
+    pa, fa = xa.PacketAssembler(), xa.FileAssembler()
+    st = ps.State()
+    earlier = ps.group({5: ra[:4], 9: rb[:30], 63: random_rows(rng, 3)})
+    same(pa.process(*earlier), ps.process(st, *earlier))
+    same_state(xa, pa, st)
+    assert st.pending[5] and st.pending[9] and st.total("packets") > 0
+    files_in = fs.stage_input(fs.random_stream(rng, 6, [(5, 20), (9, 21)], max_bytes=3000, max_user=500)[0][:-2])
+    fst = fs.State()
+    want_f = fs.process(fst, *files_in)
+    got_f = fa.process(*files_in)
+    assert got_f[1].tobytes() == want_f[1].tobytes() and got_f[2].tobytes() == want_f[2].tobytes()
+    before, files_before = pa.stats().tobytes(), fa.stats().tobytes()
+    assert int(fa.stats()["open_files"]) > 0 and int(fa.stats()["total_pieces"]) > 0
+
+    vcdu, off = ps.group({5: ra[4:], 9: rb[30:], 63: random_rows(rng, 2)})
+    n = int(off[64])
+    want = ps.process(st, vcdu, off)
+    assert len(want[1]) >= 8
+    dev = torch.device("cuda:0")
+    ee = lambda nbytes: torch.full((nbytes,), 0xEE, dtype=torch.uint8, device=dev)
+    d_vcdu = torch.from_numpy(vcdu.copy()).to(dev)
+    d_off = torch.from_numpy(off.view(np.uint8).copy()).to(dev)
+    max_bytes, max_packets = xa.packets_max_bytes(n), 64
+    d_bytes, d_desc, d_pko, d_sum = ee(max_bytes), ee(max_packets * 32), ee(260), ee(72)
+    d_fbytes, d_pieces, d_frecs, d_fsum = ee(max_bytes), ee(max_packets * 32), ee(2 * max_packets * 80), ee(104)
+
+    def call(bound):
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            pa.process_device(d_vcdu.data_ptr(), d_off.data_ptr(), bound, d_bytes.data_ptr(), max_bytes, d_desc.data_ptr(),
+                              max_packets, d_pko.data_ptr(), d_sum.data_ptr(), stream=s.cuda_stream)
+            fa.process_device(d_bytes.data_ptr(), max_bytes, d_desc.data_ptr(), d_pko.data_ptr(), max_packets,
+                              d_fbytes.data_ptr(), max_bytes, d_pieces.data_ptr(), max_packets, d_frecs.data_ptr(),
+                              2 * max_packets, d_fsum.data_ptr(), stream=s.cuda_stream)
+        s.synchronize()
+        return d_sum.cpu().numpy().view(xa.PACKETS_SUMMARY_DTYPE)[0], d_fsum.cpu().numpy().view(xa.FILES_SUMMARY_DTYPE)[0]
+
+    summ, fsum = call(n - 1)
+    assert int(summ["overflow"]) == 2 and int(summ["packets"]) == 0 and int(summ["bytes"]) == 0
+    assert (d_bytes.cpu().numpy() == 0xEE).all() and (d_desc.cpu().numpy() == 0xEE).all()
+    assert (d_pko.cpu().numpy() == 0).all()                     # the one thing written besides the summary: no packets
+    assert pa.stats().tobytes() == before
+    # the file assembler queued behind it saw an empty call
+    assert [int(fsum[k]) for k in ("pieces", "bytes", "files", "overflow")] == [0, 0, 0, 0]
+    assert (d_pieces.cpu().numpy() == 0xEE).all() and (d_frecs.cpu().numpy() == 0xEE).all() and (d_fbytes.cpu().numpy() == 0xEE).all()
+    assert fa.stats().tobytes() == files_before
+    # the true bound: the call as if the refused one had not been
+    summ, fsum = call(n)
+    got = (d_bytes.cpu().numpy()[:int(summ["bytes"])], d_desc.cpu().numpy().view(xa.PACKET_DTYPE)[:int(summ["packets"])],
+           d_pko.cpu().numpy().view(np.uint32), summ)
+    same(got, want)
+    same_state(xa, pa, st)
+    assert sa.packets[ka][0] in pa.split(got[0], got[1])
+    # ... and the file assembler behind it the packets of that call (unsegmented ones: a file each)
+    want_f = fs.process(fst, d_bytes.cpu().numpy(), got[1], got[2])
+    assert int(fsum["overflow"]) == 0 and want_f[3]["files_completed"] >= 8
+    for key, w in want_f[3].items():
+        assert int(fsum[key]) == w, key
+    assert d_pieces.cpu().numpy().view(xa.FILE_PIECE_DTYPE)[:len(want_f[1])].tobytes() == want_f[1].tobytes()
+    assert d_frecs.cpu().numpy().view(xa.FILE_RECORD_DTYPE)[:len(want_f[2])].tobytes() == want_f[2].tobytes()
+    assert np.array_equal(d_fbytes.cpu().numpy()[:len(want_f[0])], want_f[0])
+    for x in (pa, fa):
+        x.close()
+    del d_vcdu, d_off, d_bytes, d_desc, d_pko, d_sum, d_fbytes, d_pieces, d_frecs, d_fsum
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
 
 
 def interleave(rows):

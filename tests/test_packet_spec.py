@@ -262,6 +262,103 @@ def test_calls_cut_at_random_equal_one_call():
     assert many.pending == one.pending and many.last == one.last
 
 
+# ---- the generators of the GPU tier reach what they are there for ------------------------------------------------------
+@pytest.mark.parametrize("case", list(ps.LONG_CASES))
+def test_long_packet_cut_at_every_row(case):
+    total, start = ps.LONG_CASES[case]
+    st, k = ps.long_packet_stream(case)
+    rows = ps.rows_of(st)
+    long, a, b = st.packets[k]
+    assert len(long) == total and b - a + 1 == -(-(start + total) // ps.ZONE) and len(rows) == b + 1
+    want = [p for p, _, _ in st.packets]
+    pending = []
+    for c in range(1, len(rows)):
+        state, ((r1, p1), (r2, p2)) = ps.run_calls([{5: rows[:c]}, {5: rows[c:]}])
+        assert ps.packets_of(r1[0], r1[1]) + ps.packets_of(r2[0], r2[1]) == want
+        assert (r1[1]["crc_ok"] == 1).all() and (r2[1]["crc_ok"] == 1).all() and state.total("discarded") == 0
+        assert p2[5] == 0
+        pending.append(p1[5])
+    # the first call holds the packet's head and whole zones behind it: every length the packet passes through
+    first = ps.ZONE - start
+    assert pending[a:b] == [first + ps.ZONE * i for i in range(b - a)]
+    assert max(pending) > 4096 + ps.ZONE
+    if case == "one_byte_last":
+        assert pending[b - 1] == ps.PACKET_MAX - 1 == 65541
+    if case.startswith("tail_"):
+        assert pending[a] == int(case[5:]) < 6
+
+
+def test_three_calls_grow_the_pending_state_in_the_middle():
+    cases, streams = ps.three_call_cases()
+    want = {v: [p for p, _, _ in s.packets] for v, s in streams.items()}
+    assert len(cases) >= 30 and sum(c1 == c2 for c1, c2, _ in cases) >= 4 and sum(c2 - c1 >= 5 for c1, c2, _ in cases) >= 5
+    for c1, c2, calls in cases:
+        state, ((r1, p1), (r2, p2), (r3, p3)) = ps.run_calls(calls)
+        assert all(len(c[63]) > 0 for c in calls) and state.rows[63] == 0
+        assert p1[5] > 0 and p1[9] > 0 and p1[5] != p1[9]                       # two channels pending at once
+        assert int(r2[2][6] - r2[2][5]) == 0 and int(r2[2][10] - r2[2][9]) == 0 and len(r2[1]) == 0
+        assert p2[5] == p1[5] + ps.ZONE * (c2 - c1) and len(calls[1][5]) == c2 - c1
+        assert p2[9] > p1[9] and (p2[9] - p1[9]) % ps.ZONE == 0
+        assert all(ps.with_fhp(r, ps.FHP_NONE) == r for v in (5, 9) for r in calls[1][v])
+        assert p3[5] == 0 and p3[9] == 0 and state.total("discarded") == 0
+        got = {v: [] for v in want}
+        for res, _ in ((r1, 0), (r2, 0), (r3, 0)):
+            for p, d in zip(ps.packets_of(res[0], res[1]), res[1]):
+                got[int(d["vcid"])].append(p)
+                assert d["crc_ok"] == 1
+        assert got == want
+
+
+@pytest.mark.parametrize("case", ["ten_rows", "one_byte_last", "tail_5", "tail_1"])
+def test_joint_damage_drops_the_long_packet(case):
+    st, k = ps.long_packet_stream(case)
+    long = st.packets[k][0]
+    cases = ps.joint_damage(case)
+    names = [n for n, _, _ in cases]
+    assert len(set(names)) == len(names) >= 20
+    kinds = {n.split("_", 1)[1] for n in names}
+    assert {"skipped_counter", "repeated_row", "fhp_0", "fhp_400", "fhp_2046", "fhp_1000", "early_end"} <= kinds
+    assert case.startswith("tail_") == ("length_1" in kinds)
+    for name, head, rest in cases:
+        state, ((r1, p1), (r2, p2)) = ps.run_calls([{5: head}, {5: rest}])
+        assert p1[5] > 0, name
+        got = ps.packets_of(r1[0], r1[1]) + ps.packets_of(r2[0], r2[1])
+        assert state.discarded[5] >= 1, name
+        # (the row the packet begins in, repeated: dropped and begun again)
+        assert (long in got) == (name == f"{st.packets[k][1] + 1}_repeated_row"), name
+        assert state.bad_fhp[5] == (1 if name.endswith(("fhp_1000", "fhp_2045")) else 0), name
+
+
+def test_crc_ladder_has_every_chunk_count():
+    streams, long = ps.crc_ladder()
+    assert sorted(len(p) for p in long) == sorted(ps.LADDER)
+    assert set(range(4097, 4108)) | set(range(8193, 8204)) | {65541} <= set(ps.LADDER)
+    assert any((t - 2) % 4096 == 0 for t in ps.LADDER_STEPS)
+    state, ((res, _),) = ps.run_calls([{v: s.rows for v, s in streams.items()}])
+    got = ps.packets_of(res[0], res[1])
+    assert got == [p for v in sorted(streams) for p, _, _ in streams[v].packets] and (res[1]["crc_ok"] == 1).all()
+    assert {ps.chunks_of(int(n)) for n in res[1]["length"]} == set(range(1, 18))
+    where = {}                      # the long packets begin all over the zone
+    for v, s in streams.items():
+        for p, a, _ in s.packets:
+            if len(p) > 4096:
+                where[p] = a
+    assert len(where) == len(ps.LADDER)
+    bitwise = ps.ladder_crcs()
+    assert set(bitwise) == set(long)
+    for p, d in zip(got, res[1]):
+        if len(p) > 4096:
+            assert int(d["crc_computed"]) == bitwise[p]
+    # flipped: the same stream but for one bit in every long packet, which the CRC sees
+    flipped, bad = ps.crc_ladder(flip=True)
+    assert [len(p) for p in bad] == [len(p) for p in long] and all(sum(x != y for x, y in zip(p, q)) == 1 for p, q in zip(long, bad))
+    state, ((res2, _),) = ps.run_calls([{v: s.rows for v, s in flipped.items()}])
+    assert np.array_equal(res2[1]["length"], res[1]["length"])
+    is_long = res[1]["length"] > 4096
+    assert (res2[1]["crc_ok"][is_long] == 0).all() and (res2[1]["crc_ok"][~is_long] == 1).all()
+    assert (res2[1]["crc_carried"] == res[1]["crc_carried"]).all() and state.total("crc_failures") == len(ps.LADDER)
+
+
 # ---- the ABI, CPU side -------------------------------------------------------------------------------------------------
 PACKET_FUNCTIONS = ["xrit_packets_create", "xrit_packets_destroy", "xrit_packets_process", "xrit_packets_process_device",
                     "xrit_packets_reset", "xrit_packets_stats"]
