@@ -937,6 +937,160 @@ int xrit_images_stats(xrit_images *im, xrit_images_counters *out);
 int xrit_images_key(xrit_images *im, unsigned vcid, unsigned apid, xrit_image_key *out);
 
 /* ------------------------------------------------------------------------
+ * Image canvases: the decoded lines of one files call and the images call on it,
+ * placed into full images in device memory (DESIGN.md section 20;
+ * tests/canvas_spec.py is the serial statement).  GOES sends an image as several
+ * segment files; each carries a segment identification record (mission
+ * specific, type 128, length 17; seven big-endian 16-bit fields: image_id,
+ * segment, start_column, start_line, max_segment, max_column, max_row) that says
+ * where its rows belong.  UNVERIFIED, our reading, no recorded downlink and no
+ * other implementation at hand: that layout; that the segments of one image
+ * share vcid and image_id, possibly on different apids; that start_line and
+ * start_column count from 0.
+ *  - the handle owns `slots` canvases of slot_bytes each, all zero while free.
+ *  - the records are taken in record order.  A record with BEGINS whose
+ *    xrit_image_file.rice is 1: the headers in its first piece are walked (as the
+ *    file stage walks them) for the first record 128 of length 17 and the first
+ *    annotation record (type 4; its first 64 bytes, zero padded, are the name).
+ *    Without record 128 the file is an image of one segment: image_id 0xFFFFFFFF
+ *    (never joins), segment = max_segment = 1, start (0, 0), max_column = columns,
+ *    max_row = lines of the image structure record.  Then, in this order:
+ *      BAD_SEGMENT   max_segment 0 or > 64; segment 0 or > max_segment; max_column,
+ *                    max_row or the record's lines 0; start_column + columns >
+ *                    max_column; start_line + lines > max_row
+ *      TOO_LARGE     pitch * max_row > slot_bytes; pitch = (max_column * width + 3)
+ *                    & ~3, width 1 for bits <= 8, else 2
+ *      a slot in use with the same (vcid, image_id, max_column, max_row,
+ *      max_segment, bits), image_id != 0xFFFFFFFF -- the apid is not part of it:
+ *      DUPLICATE     the segment's bit is set in begun_mask
+ *      OVERLAP       its rectangle meets that of a segment begun there
+ *                    otherwise it joins
+ *      no such slot: the free slot of lowest index is born;
+ *      NO_SLOT       none is free
+ *    On success the key (vcid, apid) carries the placement (xrit_canvas_key_state); a
+ *    BEGINS record that is not rice, or that was refused, leaves it without one.
+ *  - a rice record without BEGINS is placed iff the key's state has `placed` with
+ *    the record's key_serial and the slot is in use with the same generation;
+ *    otherwise NO_PLACEMENT.
+ *  - every xrit_image_line of a placed record, whatever its status, is copied as
+ *    the image stage wrote it: `length` bytes to slot base + (start_line + row) *
+ *    pitch + start_column * width.  A line with row >= the segment's declared
+ *    lines (or one that the inputs do not hold whole) is counted clipped.  No two
+ *    lines ever write one pixel, so the canvas is deterministic without atomics.
+ *  - ENDS sets the segment's bit in done_mask, ABORTED in aborted_mask (its rows
+ *    stay; the segment is never accepted again); complete iff done_mask covers
+ *    1 .. max_segment.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_canvas xrit_canvas;
+#define XRIT_CANVAS_NOT_RICE     0   /* the image stage said so: every field of the xrit_canvas_file is 0 */
+#define XRIT_CANVAS_PLACED       1
+#define XRIT_CANVAS_BAD_SEGMENT  2
+#define XRIT_CANVAS_TOO_LARGE    3
+#define XRIT_CANVAS_DUPLICATE    4
+#define XRIT_CANVAS_OVERLAP      5
+#define XRIT_CANVAS_NO_SLOT      6
+#define XRIT_CANVAS_NO_PLACEMENT 7
+#define XRIT_CANVAS_NO_ID        0xFFFFFFFFu
+#define XRIT_CANVAS_MAX_SLOTS    64
+#define XRIT_CANVAS_MAX_SEGMENTS 64
+typedef struct xrit_canvas_file {
+    int32_t  slot;                   /* -1: none (refused); 0 with reason NOT_RICE */
+    uint32_t reason;                 /* XRIT_CANVAS_* */
+    uint32_t segment;                /* of a placed record, 1 .. max_segment */
+    uint32_t start_line, start_column;
+    uint32_t lines_placed, lines_clipped;    /* of this call */
+    uint32_t faults;                 /* placed lines of this call with status != 0 */
+} xrit_canvas_file;                  /* 32 bytes */
+typedef struct xrit_canvas_slot {
+    uint64_t begun_mask, done_mask, aborted_mask;    /* bit segment - 1 */
+    uint32_t image_id;
+    uint32_t max_column, max_row, max_segment;
+    uint32_t pitch;                  /* bytes per canvas row */
+    uint32_t lines_placed, faults;   /* over the slot's segments */
+    uint32_t generation;             /* releases of this slot */
+    uint32_t born_call, touched_call;    /* the handle's call counter: 1 for its first call */
+    uint8_t  in_use, complete, vcid, bits;
+    uint8_t  reserved[4];
+    uint8_t  name[64];               /* the annotation text, zero padded */
+} xrit_canvas_slot;                  /* 136 bytes */
+typedef struct xrit_canvas_segment {
+    uint32_t start_line, start_column, lines, columns;
+    uint32_t placed, faults;         /* lines placed so far; those with status != 0 */
+    uint32_t key_serial;             /* of its file on (slot's vcid, apid) */
+    uint16_t apid;
+    uint8_t  begun;
+    uint8_t  reserved;
+} xrit_canvas_segment;               /* 32 bytes */
+/* what one key carries (xrit_canvas_key reads it) */
+typedef struct xrit_canvas_key_state {
+    uint32_t key_serial, slot, generation, segment, start_line, start_column;
+    uint32_t lines;                  /* the segment's declared lines */
+    uint8_t  placed;
+    uint8_t  reserved[3];
+} xrit_canvas_key_state;                   /* 32 bytes */
+typedef struct xrit_canvas_counters {
+    uint64_t calls;                  /* calls that were not refused */
+    uint64_t canvases_begun, canvases_completed, segments_begun, segments_done, segments_aborted;
+    uint64_t lines_placed, lines_clipped, faults;
+    uint64_t bad_segment, too_large, duplicate, overlap, no_slot, no_placement;
+} xrit_canvas_counters;              /* 120 bytes */
+typedef struct xrit_canvas_summary {
+    uint64_t placed;                 /* of this call: records placed, */
+    uint64_t call_lines_placed, call_lines_clipped, call_faults;     /* their lines, */
+    uint64_t completed;              /* canvases that became complete */
+    uint64_t calls;                  /* the handle's counters after it */
+    uint64_t canvases_begun, canvases_completed, segments_begun, segments_done, segments_aborted;
+    uint64_t lines_placed, lines_clipped, faults;
+    uint64_t bad_segment, too_large, duplicate, overlap, no_slot, no_placement;
+    uint32_t overflow;               /* 0; 2: a summary handed over has overflow != 0 or counts beyond the host's bounds */
+    uint32_t reserved;
+} xrit_canvas_summary;               /* 168 bytes */
+
+/* slots 1 .. 64, slot_bytes a multiple of 16 (> 0): slots * slot_bytes of pixel memory, allocated once, all zero.
+ * No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_canvas_create(xrit_canvas **cv, int device, unsigned slots, size_t slot_bytes);
+int xrit_canvas_destroy(xrit_canvas *cv);
+/* everything zero, the pixels included; waits for the handle's last call */
+int xrit_canvas_reset(xrit_canvas *cv);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_images_process_device.  d_bytes (n_bytes), d_pieces (max_pieces_in), d_files (max_files_in) and
+ * d_files_summary are the files call's; d_image_bytes (n_image_bytes), d_lines (max_lines_in), d_image_files
+ * (max_files_in) and d_images_summary the images call's.  If either summary has overflow != 0 or counts beyond these
+ * bounds, only d_summary is written, with overflow = 2, and the state is unchanged.  d_canvas_files has max_files_in
+ * entries, d_slots (the slot table after the call) as many as the handle has slots.  Every pointer but the two byte
+ * buffers 8-byte aligned; d_image_bytes 4-byte aligned.  Calls on one handle share its state and scratch: keep them in
+ * order. */
+int xrit_canvas_process_device(xrit_canvas *cv, const uint8_t *d_bytes, size_t n_bytes, const xrit_file_piece *d_pieces,
+                               size_t max_pieces_in, const xrit_file_record *d_files, size_t max_files_in,
+                               const xrit_files_summary *d_files_summary, const uint8_t *d_image_bytes, size_t n_image_bytes,
+                               const xrit_image_line *d_lines, size_t max_lines_in, const xrit_image_file *d_image_files,
+                               const xrit_images_summary *d_images_summary, xrit_canvas_file *d_canvas_files,
+                               xrit_canvas_slot *d_slots, xrit_canvas_summary *d_summary, void *stream);
+/* host buffers (one upload, one download): what xrit_files_process and xrit_images_process returned; the n_* are the
+ * lengths of the arrays handed over (the device's bounds).  canvas_files has n_files_in entries, slots as many as the
+ * handle has.  XRIT_E_ARG with summary->overflow = 2 when the call was refused (nothing else written). */
+int xrit_canvas_process(xrit_canvas *cv, const uint8_t *bytes, size_t n_bytes, const xrit_file_piece *pieces, size_t n_pieces_in,
+                        const xrit_file_record *files, size_t n_files_in, const xrit_files_summary *files_summary,
+                        const uint8_t *image_bytes, size_t n_image_bytes, const xrit_image_line *lines, size_t n_lines_in,
+                        const xrit_image_file *image_files, const xrit_images_summary *images_summary,
+                        xrit_canvas_file *canvas_files, xrit_canvas_slot *slots, xrit_canvas_summary *summary);
+/* the first n_bytes (<= slot_bytes) of the slot's pixels -- a canvas is its first pitch * max_row -- to device memory,
+ * queued on `stream` behind nothing: the caller orders it behind the handle's last call */
+int xrit_canvas_read_device(xrit_canvas *cv, unsigned slot, uint8_t *d_out, size_t n_bytes, void *stream);
+/* the slot's record and its pitch * max_row bytes after the handle's last call (waits for it); XRIT_E_CAPACITY, with
+ * *info written, when max_bytes is less */
+int xrit_canvas_read(xrit_canvas *cv, unsigned slot, uint8_t *out, size_t max_bytes, xrit_canvas_slot *info);
+/* the slot's 64 segments after the handle's last call (waits for it) */
+int xrit_canvas_segments(xrit_canvas *cv, unsigned slot, xrit_canvas_segment *out);
+/* what key (vcid < 64, apid < 2048) carries after the handle's last call (waits for it) */
+int xrit_canvas_key(xrit_canvas *cv, unsigned vcid, unsigned apid, xrit_canvas_key_state *out);
+/* the counters after the handle's last call (waits for it) */
+int xrit_canvas_stats(xrit_canvas *cv, xrit_canvas_counters *out);
+/* the slot free again: pixels, record and segments zero, generation + 1 (so a file still open on it stops being
+ * placed).  Queued on the stream of the handle's last call; no host synchronisation. */
+int xrit_canvas_release(xrit_canvas *cv, unsigned slot);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

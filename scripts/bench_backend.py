@@ -27,9 +27,16 @@ images   xrit_images_process_device on one files call that holds --images rice-c
          device-resident bytes: one xrit_rice_decode_device per rice record (the records read back beforehand, which the
          loop needs and the stage does not; that read-back and its synchronisation are outside the timed region).  Then
          packets + files on one stream with and without the stage behind them.
-all      the seven in front of images, in this order (images is asked for by name).
+canvas   xrit_canvas_process_device on one files call of --canvases images of three segments each over four keys at real
+         widths (2784 and 5424 columns), every call from a reset handle (the reset is outside the timed region): the stage
+         alone, and packets + files + images with and without it on one stream.  Beside it what the stage replaces:
+         downloading the image stage's lines and placing them on the host with NumPy (the download is inside that timed
+         region: the host cannot place what it has not got; the stage's own read-back of the finished canvases is
+         outside its timed region and reported on its own line).  The bytes the place kernel reads plus writes over
+         the whole stage's time -- a lower bound on that kernel's rate -- next to the device read rate of the same run.
+all      the seven in front of images, in this order (images and canvas are asked for by name).
 
-    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,lock,images,all} [--frames N] [--images I] [--reps R] [--warmup W]
+    python scripts/bench_backend.py {decode,demux,packets,files,rice,framer,lock,images,canvas,all} [--frames N] [--images I] [--reps R] [--warmup W]
                                     [--lines L] [--samples S] [--no-cpu]"""
 import argparse
 import json
@@ -48,7 +55,8 @@ import packet_spec as ps
 import rice_spec as rs
 
 ap = argparse.ArgumentParser()
-ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "lock", "images", "all"])
+ap.add_argument("what", choices=["decode", "demux", "packets", "files", "rice", "framer", "lock", "images", "canvas", "all"])
+ap.add_argument("--canvases", type=int, default=6)
 ap.add_argument("--images", type=int, default=96)
 ap.add_argument("--frames", type=int, default=1 << 16)
 ap.add_argument("--reps", type=int, default=None, help="timed calls per case (decode: 5, the others: 20)")
@@ -532,6 +540,131 @@ def bench_images():
         h.close()
 
 
+def bench_canvas():
+    import canvas_spec as cs
+    import file_spec as fs
+    import image_spec as isp
+    rng = np.random.default_rng(4)
+    keys = [(0, 10), (0, 11), (5, 700), (31, 2046)]
+    items, sources = [], {}
+    for i in range(args.canvases):
+        bits, J, cols, rows = (8, 16, 2784, 36) if i % 2 else (10, 32, 5424, 36)
+        img = cs.samples(rng, bits, J, cols, rows, kinds=("walk3", "scaled"))
+        key = keys[i % len(keys)]
+        sources[(key[0], 100 + i)] = img
+        items += cs.split_image(rng, img, bits, J, 100 + i, [key], [12, 24], name=b"bench image %d" % i)
+    stream = isp.stream_of(rng, items)
+    vcdu, offsets = ps.group({v: s.rows for v, s in ps.build_streams([(v, p) for v, p, _ in stream], rng, fill=0.0, idle=0.0).items()})
+    rows = len(vcdu)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    d_vcdu, d_off = up(vcdu), up(offsets)
+    mb, mp = xa.packets_max_bytes(rows), len(stream) + 64 * 3
+    p_bytes, p_desc, p_off, p_sum = u8(mb), u8(mp * 32), u8(65 * 4), u8(xa.PACKETS_SUMMARY_DTYPE.itemsize)
+    f_bytes, f_pieces, f_recs, f_sum = u8(mb), u8(mp * 32), u8(2 * mp * 80), u8(xa.FILES_SUMMARY_DTYPE.itemsize)
+    slots, slot_bytes = max(8, args.canvases), 1 << 19
+    pa, fa, im, cv = xa.PacketAssembler(), xa.FileAssembler(), xa.ImageDecoder(), xa.ImageCanvas(slots, slot_bytes)
+
+    def packets():
+        pa.process_device(d_vcdu.data_ptr(), d_off.data_ptr(), rows, p_bytes.data_ptr(), mb, p_desc.data_ptr(), mp, p_off.data_ptr(),
+                          p_sum.data_ptr(), stream=st)
+
+    def files():
+        fa.process_device(p_bytes.data_ptr(), mb, p_desc.data_ptr(), p_off.data_ptr(), mp, f_bytes.data_ptr(), mb, f_pieces.data_ptr(), mp,
+                          f_recs.data_ptr(), 2 * mp, f_sum.data_ptr(), stream=st)
+
+    packets()
+    files()
+    torch.cuda.synchronize()
+    fsum = f_sum.cpu().numpy().view(xa.FILES_SUMMARY_DTYPE)[0]
+    assert int(fsum["overflow"]) == 0
+    nrec = int(fsum["files"])
+    recs = f_recs.cpu().numpy().view(xa.FILE_RECORD_DTYPE)[:nrec]
+    max_out = xa.images_max_bytes(recs)
+    o_bytes, o_lines, o_files, o_sum = u8(max_out + 8), u8(mp * 32), u8(2 * mp * 48), u8(xa.IMAGES_SUMMARY_DTYPE.itemsize)
+    c_files, c_slots, c_sum = u8(2 * mp * 32), u8(slots * xa.CANVAS_SLOT_DTYPE.itemsize), u8(xa.CANVAS_SUMMARY_DTYPE.itemsize)
+
+    def images():
+        im.process_device(f_bytes.data_ptr(), mb, f_pieces.data_ptr(), mp, f_recs.data_ptr(), 2 * mp, f_sum.data_ptr(), o_bytes.data_ptr(),
+                          max_out, o_lines.data_ptr(), mp, o_files.data_ptr(), o_sum.data_ptr(), stream=st)
+
+    def canvas():
+        cv.process_device(f_bytes.data_ptr(), mb, f_pieces.data_ptr(), mp, f_recs.data_ptr(), 2 * mp, f_sum.data_ptr(), o_bytes.data_ptr(),
+                          max_out, o_lines.data_ptr(), mp, o_files.data_ptr(), o_sum.data_ptr(), c_files.data_ptr(), c_slots.data_ptr(),
+                          c_sum.data_ptr(), stream=st)
+
+    images()
+    torch.cuda.synchronize()
+    isum = o_sum.cpu().numpy().view(xa.IMAGES_SUMMARY_DTYPE)[0]
+    nl, nb = int(isum["lines"]), int(isum["bytes"])
+    reps, warm = args.reps or 20, 3 if args.warmup is None else args.warmup
+
+    def from_reset(fn):                         # every call on a handle without canvases: the reset is outside the events
+        times = []
+        for i in range(warm + reps):
+            cv.reset()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warm:
+                times.append(a.elapsed_time(b))
+        return float(np.median(times)), min(times)
+
+    # what the stage replaces: the lines come to the host, which places them by the segment records it parsed itself
+    heads = {}
+    pieces = f_pieces.cpu().numpy().view(xa.FILE_PIECE_DTYPE)[:int(fsum["pieces"])]
+    raw = f_bytes.cpu().numpy()
+    for f, r in enumerate(recs):
+        if int(r["flags"]) & xa.FILE_BEGINS:
+            pc = pieces[int(r["first_piece"])]
+            heads[f] = cs.walk_header(raw[int(pc["offset"]):int(pc["offset"]) + int(pc["length"])].tobytes(), r["columns"], r["lines"])[0]
+
+    def on_the_host():
+        t = time.perf_counter()
+        data, lines = o_bytes[:nb].cpu().numpy(), o_lines[:nl * 32].cpu().numpy().view(xa.IMAGE_LINE_DTYPE)
+        out = {}
+        for ln in lines:
+            h, r = heads[int(ln["file"])], recs[int(ln["file"])]
+            w = 1 if int(r["bits_per_pixel"]) <= 8 else 2
+            img = out.setdefault((int(r["vcid"]), h["image_id"]), np.zeros((h["max_row"], h["max_column"] * w), np.uint8))
+            a = int(ln["offset"])
+            img[h["start_line"] + int(ln["row"]), h["start_column"] * w:h["start_column"] * w + int(ln["length"])] = data[a:a + int(ln["length"])]
+        return (time.perf_counter() - t) * 1e3, out
+
+    host_ms = [on_the_host()[0] for _ in range(max(3, reps // 4))]
+    host_images = on_the_host()[1]
+    res = {"canvas": from_reset(canvas), "packets+files+images": from_reset(lambda: (packets(), files(), images())),
+           "packets+files+images+canvas": from_reset(lambda: (packets(), files(), images(), canvas()))}
+    for name, (ms, mn) in res.items():
+        emit(case=name, rows=rows, ms_median=round(ms, 4), ms_min=round(mn, 4))
+    emit(case="host: download the lines, place with NumPy (download inside)", lines=nl, ms_median=round(float(np.median(host_ms)), 3),
+         ms_min=round(min(host_ms), 3))
+    # the stage's canvases are the generated images, and the host's
+    cv.reset()
+    canvas()
+    torch.cuda.synchronize()
+    s = c_sum.cpu().numpy().view(xa.CANVAS_SUMMARY_DTYPE)[0]
+    table = c_slots.cpu().numpy().view(xa.CANVAS_SLOT_DTYPE)
+    t = time.perf_counter()
+    got = {(int(info["vcid"]), int(info["image_id"])): img for info, img in (cv.image(i) for i in range(slots) if table[i]["complete"])}
+    read_ms = (time.perf_counter() - t) * 1e3
+    equal = got.keys() == sources.keys() and all(np.array_equal(got[k], v) for k, v in sources.items())
+    host_equal = all(np.array_equal(host_images[k] if host_images[k].shape[1] == v.shape[1] else host_images[k].view("<u2"), v) for k, v in sources.items())
+    probe = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
+    hbm = xa._capi.device_read_bandwidth(probe.data_ptr(), probe.numel(), reps=10, stream=st)
+    lines = o_lines.cpu().numpy().view(xa.IMAGE_LINE_DTYPE)[:nl]
+    moved = 2 * int(lines["length"].astype(np.int64).sum()) + 32 * nl
+    emit(case="canvas check", canvases=args.canvases, records=nrec, lines=nl, lines_placed=int(s["call_lines_placed"]),
+         completed=int(s["completed"]), overflow=int(s["overflow"]), canvases_equal_sources=bool(equal), host_equal_sources=bool(host_equal),
+         read_back_of_the_finished_canvases_ms=round(read_ms, 3), stage_over_host=round(res["canvas"][0] / float(np.median(host_ms)), 5),
+         chain_difference_ms=round(res["packets+files+images+canvas"][0] - res["packets+files+images"][0], 4),
+         place_bytes_read_plus_written=moved, place_GB_per_s_at_least=round(moved / res["canvas"][0] / 1e6, 2),
+         device_read_GB_per_s=round(hbm, 1))
+    for h in (pa, fa, im, cv):
+        h.close()
+
+
 shared = []                                     # the packets and the files cases run on one stream of frames
 
 
@@ -542,5 +675,6 @@ def packet_chain():
 
 
 for what in ["decode", "demux", "packets", "files", "rice", "framer", "lock"] if args.what == "all" else [args.what]:
-    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "lock": bench_lock, "images": bench_images, "packets": lambda: bench_packets(packet_chain()),
+    {"decode": bench_decode, "demux": bench_demux, "rice": bench_rice, "framer": bench_framer, "lock": bench_lock, "images": bench_images, "canvas": bench_canvas,
+     "packets": lambda: bench_packets(packet_chain()),
      "files": lambda: bench_files(packet_chain())}[what]()

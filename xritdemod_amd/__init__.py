@@ -22,4 +22,6 @@ from ._capi import (  # noqa: F401
     FrameLock, LOCK_STATS_DTYPE, LOCK_FULL, LOCK_SHORT, LOCK_MISS, LOCK_RECHECK, FLYWHEEL_RECHECK,
     FILE_BEGINS, FILE_ENDS, FILE_ABORTED, FILE_LENGTH_MATCH, RiceDecoder, rice_form, is_rice_coded, decode_file_lines,
     ImageDecoder, IMAGE_LINE_DTYPE, IMAGE_FILE_DTYPE, IMAGES_SUMMARY_DTYPE, IMAGES_STATS_DTYPE, IMAGE_KEY_DTYPE, images_max_bytes,
+    ImageCanvas, CANVAS_FILE_DTYPE, CANVAS_SLOT_DTYPE, CANVAS_SEGMENT_DTYPE, CANVAS_KEY_DTYPE, CANVAS_SUMMARY_DTYPE, CANVAS_STATS_DTYPE,
+    CANVAS_REASONS,
 )

@@ -144,6 +144,17 @@ _SIGNATURES = {
     "xrit_images_process": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "xrit_images_stats": (C.c_int, [_vp, _vp]),
     "xrit_images_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
+    "xrit_canvas_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_uint, _sz]),
+    "xrit_canvas_destroy": (C.c_int, [_vp]),
+    "xrit_canvas_reset": (C.c_int, [_vp]),
+    "xrit_canvas_process_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xrit_canvas_process": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "xrit_canvas_read_device": (C.c_int, [_vp, C.c_uint, _vp, _sz, _vp]),
+    "xrit_canvas_read": (C.c_int, [_vp, C.c_uint, _vp, _sz, _vp]),
+    "xrit_canvas_segments": (C.c_int, [_vp, C.c_uint, _vp]),
+    "xrit_canvas_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
+    "xrit_canvas_stats": (C.c_int, [_vp, _vp]),
+    "xrit_canvas_release": (C.c_int, [_vp, C.c_uint]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -1450,3 +1461,139 @@ class ImageDecoder(_Handle):
     def reset(self):
         """Every key closed, counters zero."""
         _check(lib().xrit_images_reset(self._h))
+
+
+# ---- image canvases (DESIGN.md section 20) ------------------------------------------------------------------------------
+CANVAS_REASONS = ("NOT_RICE", "PLACED", "BAD_SEGMENT", "TOO_LARGE", "DUPLICATE", "OVERLAP", "NO_SLOT", "NO_PLACEMENT")
+# xrit_canvas_file: one per files record, all zero where the record is not a rice-coded image's
+CANVAS_FILE_DTYPE = np.dtype([
+    ("slot", np.int32), ("reason", np.uint32), ("segment", np.uint32), ("start_line", np.uint32), ("start_column", np.uint32),
+    ("lines_placed", np.uint32), ("lines_clipped", np.uint32), ("faults", np.uint32)])
+assert CANVAS_FILE_DTYPE.itemsize == 32
+# xrit_canvas_slot: one per canvas of the pool
+CANVAS_SLOT_DTYPE = np.dtype([
+    ("begun_mask", np.uint64), ("done_mask", np.uint64), ("aborted_mask", np.uint64),
+    ("image_id", np.uint32), ("max_column", np.uint32), ("max_row", np.uint32), ("max_segment", np.uint32), ("pitch", np.uint32),
+    ("lines_placed", np.uint32), ("faults", np.uint32), ("generation", np.uint32), ("born_call", np.uint32),
+    ("touched_call", np.uint32),
+    ("in_use", np.uint8), ("complete", np.uint8), ("vcid", np.uint8), ("bits", np.uint8), ("reserved", np.uint8, (4,)),
+    ("name", np.uint8, (64,))])
+assert CANVAS_SLOT_DTYPE.itemsize == 136
+# xrit_canvas_segment: 64 per slot, entry segment - 1
+CANVAS_SEGMENT_DTYPE = np.dtype([
+    ("start_line", np.uint32), ("start_column", np.uint32), ("lines", np.uint32), ("columns", np.uint32), ("placed", np.uint32),
+    ("faults", np.uint32), ("key_serial", np.uint32), ("apid", np.uint16), ("begun", np.uint8), ("reserved", np.uint8)])
+assert CANVAS_SEGMENT_DTYPE.itemsize == 32
+# xrit_canvas_key_state: what one (vcid, apid) carries
+CANVAS_KEY_DTYPE = np.dtype([
+    ("key_serial", np.uint32), ("slot", np.uint32), ("generation", np.uint32), ("segment", np.uint32), ("start_line", np.uint32),
+    ("start_column", np.uint32), ("lines", np.uint32), ("placed", np.uint8), ("reserved", np.uint8, (3,))])
+assert CANVAS_KEY_DTYPE.itemsize == 32
+_CANVAS_COUNTERS = [(k, np.uint64) for k in (
+    "calls", "canvases_begun", "canvases_completed", "segments_begun", "segments_done", "segments_aborted", "lines_placed",
+    "lines_clipped", "faults", "bad_segment", "too_large", "duplicate", "overlap", "no_slot", "no_placement")]
+# xrit_canvas_counters
+CANVAS_STATS_DTYPE = np.dtype(_CANVAS_COUNTERS)
+assert CANVAS_STATS_DTYPE.itemsize == 120
+# xrit_canvas_summary: a call's counts and the handle's counters after it
+CANVAS_SUMMARY_DTYPE = np.dtype([(k, np.uint64) for k in ("placed", "call_lines_placed", "call_lines_clipped", "call_faults", "completed")] +
+                                _CANVAS_COUNTERS + [("overflow", np.uint32), ("reserved", np.uint32)])
+assert CANVAS_SUMMARY_DTYPE.itemsize == 168
+
+
+class ImageCanvas(_Handle):
+    """A pool of `slots` image canvases of slot_bytes each in device memory.  A call takes what FileAssembler.process and
+    ImageDecoder.process on it returned and places every decoded line into the canvas of the image its segment file
+    belongs to (the segment identification record, type 128, says where); which canvases are complete is in the slot
+    table it returns.  The host reads a finished canvas and releases its slot."""
+    _destroy = "xrit_canvas_destroy"
+
+    def __init__(self, slots=8, slot_bytes=1 << 20, device=0):
+        super().__init__()
+        self.slots, self.slot_bytes = int(slots), int(slot_bytes)
+        _check(lib().xrit_canvas_create(C.byref(self._h), device, self.slots, self.slot_bytes))
+
+    def process(self, files_out, images_out):
+        """files_out: (bytes, pieces, files, summary) as FileAssembler.process returned them; images_out: (bytes, lines,
+        image_files, summary) as ImageDecoder.process returned them on those.  -> (canvas_files CANVAS_FILE_DTYPE, one per
+        record of `files`; the slot table after the call, CANVAS_SLOT_DTYPE; summary, a CANVAS_SUMMARY_DTYPE record).
+        A summary with overflow != 0, or with counts beyond the arrays' lengths, is refused: XritError -1, `partial`
+        with the summary (overflow 2) alone, the state unchanged."""
+        data = np.ascontiguousarray(files_out[0], np.uint8).reshape(-1)
+        pieces = np.ascontiguousarray(files_out[1], FILE_PIECE_DTYPE).reshape(-1)
+        files = np.ascontiguousarray(files_out[2], FILE_RECORD_DTYPE).reshape(-1)
+        fsum = np.ascontiguousarray(np.asarray(files_out[3], FILES_SUMMARY_DTYPE).reshape(1))
+        img = np.ascontiguousarray(images_out[0], np.uint8).reshape(-1)
+        lines = np.ascontiguousarray(images_out[1], IMAGE_LINE_DTYPE).reshape(-1)
+        ifiles = np.ascontiguousarray(images_out[2], IMAGE_FILE_DTYPE).reshape(-1)
+        isum = np.ascontiguousarray(np.asarray(images_out[3], IMAGES_SUMMARY_DTYPE).reshape(1))
+        if len(ifiles) != len(files):
+            raise ValueError("one image file per files record")
+        cfiles = np.zeros(max(len(files), 1), CANVAS_FILE_DTYPE)
+        slots = np.zeros(self.slots, CANVAS_SLOT_DTYPE)
+        summary = np.zeros(1, CANVAS_SUMMARY_DTYPE)
+        rc = lib().xrit_canvas_process(self._h, _p(data), len(data), _p(pieces), len(pieces), _p(files), len(files), _p(fsum), _p(img),
+                                       len(img), _p(lines), len(lines), _p(ifiles), _p(isum), _p(cfiles), _p(slots), _p(summary))
+        if rc != 0:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            if int(summary[0]["overflow"]) == 2:
+                err.partial = (summary[0],)
+            raise err
+        return cfiles[:len(files)].copy(), slots, summary[0]
+
+    def process_device(self, d_bytes_ptr, n_bytes, d_pieces_ptr, max_pieces_in, d_files_ptr, max_files_in, d_files_summary_ptr,
+                       d_image_bytes_ptr, n_image_bytes, d_lines_ptr, max_lines_in, d_image_files_ptr, d_images_summary_ptr,
+                       d_canvas_files_ptr, d_slots_ptr, d_summary_ptr, stream=None):
+        """Device pointers as FileAssembler.process_device and ImageDecoder.process_device wrote them; canvas files
+        max_files_in x 32, slots self.slots x 136, summary 168 bytes.  Asynchronous on stream; may be queued behind
+        ImageDecoder.process_device: the counts are read from the two summaries on the device."""
+        _check(lib().xrit_canvas_process_device(
+            self._h, C.c_void_p(d_bytes_ptr), n_bytes, C.c_void_p(d_pieces_ptr), max_pieces_in, C.c_void_p(d_files_ptr), max_files_in,
+            C.c_void_p(d_files_summary_ptr), C.c_void_p(d_image_bytes_ptr), n_image_bytes, C.c_void_p(d_lines_ptr), max_lines_in,
+            C.c_void_p(d_image_files_ptr), C.c_void_p(d_images_summary_ptr), C.c_void_p(d_canvas_files_ptr), C.c_void_p(d_slots_ptr),
+            C.c_void_p(d_summary_ptr), C.c_void_p(stream) if stream else None))
+
+    def read(self, slot):
+        """(the slot's record, its pitch x max_row bytes as a uint8 array (max_row, pitch)) after the last call."""
+        info = np.zeros(1, CANVAS_SLOT_DTYPE)
+        buf = np.zeros(self.slot_bytes, np.uint8)
+        _check(lib().xrit_canvas_read(self._h, slot, _p(buf), len(buf), _p(info)))
+        rows, pitch = int(info[0]["max_row"]), int(info[0]["pitch"])
+        return info[0], buf[:rows * pitch].reshape(rows, pitch).copy()
+
+    def image(self, slot):
+        """(the slot's record, its canvas as samples (max_row, max_column), uint8 or uint16)."""
+        info, raw = self.read(slot)
+        if int(info["bits"]) <= 8:
+            return info, raw[:, :int(info["max_column"])].copy()
+        return info, np.ascontiguousarray(raw[:, :2 * int(info["max_column"])]).view("<u2").copy()
+
+    def read_device(self, slot, d_out_ptr, n_bytes, stream=None):
+        """The first n_bytes of the slot's pixels to device memory, asynchronous on stream."""
+        _check(lib().xrit_canvas_read_device(self._h, slot, C.c_void_p(d_out_ptr), n_bytes, C.c_void_p(stream) if stream else None))
+
+    def segments(self, slot):
+        """The slot's 64 segments (CANVAS_SEGMENT_DTYPE; entry segment - 1) after the last call."""
+        out = np.zeros(64, CANVAS_SEGMENT_DTYPE)
+        _check(lib().xrit_canvas_segments(self._h, slot, _p(out)))
+        return out
+
+    def key(self, vcid, apid):
+        """What (vcid, apid) carries after the last call (a CANVAS_KEY_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, CANVAS_KEY_DTYPE)
+        _check(lib().xrit_canvas_key(self._h, vcid, apid, _p(out)))
+        return out[0]
+
+    def stats(self):
+        """The counters after the last call (a CANVAS_STATS_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, CANVAS_STATS_DTYPE)
+        _check(lib().xrit_canvas_stats(self._h, _p(out)))
+        return out[0]
+
+    def release(self, slot):
+        """The slot free again, all zero, its generation one more; queued behind the last call."""
+        _check(lib().xrit_canvas_release(self._h, slot))
+
+    def reset(self):
+        """Every slot free, every key without placement, counters and pixels zero."""
+        _check(lib().xrit_canvas_reset(self._h))

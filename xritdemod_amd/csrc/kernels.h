@@ -551,6 +551,34 @@ int launch_images(const unsigned char *bytes, size_t n_bytes, const xrit_file_pi
                   const xrit_file_record *files, size_t max_files_in, const xrit_files_summary *fsum, xrit_image_key *keys,
                   xrit_images_counters *counters, ImagesScratch &sc, unsigned char *out, size_t max_bytes, xrit_image_line *lines,
                   size_t max_lines, xrit_image_file *image_files, xrit_images_summary *summary, hipStream_t s);
+// canvas stage (canvas.hip): the handle's state is 64 xrit_canvas_slot records, their 64 x 64 xrit_canvas_segment,
+// FILES_KEYS xrit_canvas_key_state records, one xrit_canvas_counters and the pixels; the per-call scratch for
+// R = max(max_files_in, 1) records
+struct CanvasHead;                                  // canvas_rule.h
+struct CanvasPlace;
+struct CanvasBounds {                               // the host's bounds on what the two summaries may say
+    unsigned long long n_bytes, max_pieces, max_files, n_image_bytes, max_lines;
+};
+struct CanvasState {
+    xrit_canvas_slot *slots;
+    xrit_canvas_segment *segs;
+    xrit_canvas_key_state *keys;
+    xrit_canvas_counters *counters;
+    unsigned char *pixels;
+    unsigned n_slots;
+    size_t slot_bytes;
+};
+struct CanvasScratch {
+    CanvasHead *heads;              // [R] what the header walk found
+    CanvasPlace *place;             // [R] the rule's decision per record
+    unsigned long long *call;       // the rule kernel's tallies of the call
+};
+size_t canvas_scratch_carve(void *p, size_t max_files_in, CanvasScratch &sc);
+int launch_canvas(const unsigned char *bytes, const xrit_file_piece *pieces, const xrit_file_record *files, const xrit_files_summary *fsum,
+                  const unsigned char *image_bytes, const xrit_image_line *lines, const xrit_image_file *image_files,
+                  const xrit_images_summary *isum, const CanvasBounds &b, const CanvasState &st, CanvasScratch &sc,
+                  xrit_canvas_file *canvas_files, xrit_canvas_slot *out_slots, xrit_canvas_summary *summary, hipStream_t s);
+int launch_canvas_release(const CanvasState &st, unsigned slot, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

@@ -46,6 +46,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <cctype>
 #include <cerrno>
 #include <cstdint>
 #include <cstdio>
@@ -86,6 +87,9 @@ struct Options {
     std::string packets;           // --packets DIR: the CRC-checked space packets, DIR/vc{vcid}_apid{apid}.bin
     std::string files;             // --files DIR: the LRIT/HRIT files, DIR/vc{vcid}_apid{apid}_{serial}.lrit
     bool files_decompress = false; // --files-decompress: the scan lines of rice-coded image files, ..._{serial}.img
+    bool canvas = false;           // --canvas: the segment files' lines joined into full images on the device, DIR/<name>.pgm
+    unsigned canvas_slots = 8;     // --canvas-slots N: canvases held at a time
+    size_t canvas_mib = 32;        // --canvas-mib M: MiB per canvas (32: a 5424 x 5424 8-bit image, 29 419 776 bytes, fits)
     bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
     int flywheel = 0;              // --flywheel [N]: the frame lock (xrit_lock_*) in place of framer and decoder, flywheelRecheck = N
 };
@@ -121,6 +125,12 @@ void usage()
                  "         [--files-decompress]   (with --files: image files whose headers say Rice compression -- one coded line per packet behind a\n"
                  "                                 header-only first packet -- are also decoded on the GPU to ..._{serial}.img: lines x columns raw\n"
                  "                                 samples, uint8 or little-endian uint16; a line that faults is written as decoded and counted)\n"
+                 "         [--canvas [--canvas-slots N] [--canvas-mib M]]   (with --files-decompress: GOES sends an image as several segment files;\n"
+                 "                                 their lines are placed into full images on the GPU by the segment identification record\n"
+                 "                                 (type 128) and every image that is complete is written to DIR/<annotation text>.pgm (binary PGM,\n"
+                 "                                 16-bit big-endian above 8 bits; without annotation vc{vcid}_img{image_id}_{call}.pgm); what is\n"
+                 "                                 incomplete at exit becomes ....partial.pgm.  N canvases (1..64, default 8) of M MiB (default 32:\n"
+                 "                                 a 5424 x 5424 8-bit image fits) are held at a time)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -157,6 +167,9 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--packets") { if (!(v = need("--packets"))) return false; o.packets = v; }
         else if (a == "--files") { if (!(v = need("--files"))) return false; o.files = v; }
         else if (a == "--files-decompress") o.files_decompress = true;
+        else if (a == "--canvas") o.canvas = true;
+        else if (a == "--canvas-slots") { if (!(v = need("--canvas-slots"))) return false; o.canvas_slots = (unsigned)std::atoi(v); }
+        else if (a == "--canvas-mib") { if (!(v = need("--canvas-mib"))) return false; o.canvas_mib = (size_t)std::atoll(v); }
         else if (a == "--stream-sync") o.stream_sync = true;
         else if (a == "--flywheel") {
             o.flywheel = 4;                 // parameters.h:41
@@ -206,6 +219,11 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--files-decompress needs --files DIR\n");
         return false;
     }
+    if (o.canvas && (!o.files_decompress || o.canvas_slots < 1 || o.canvas_slots > XRIT_CANVAS_MAX_SLOTS || o.canvas_mib < 1 ||
+                     o.canvas_mib > 4096)) {
+        std::fprintf(stderr, "--canvas needs --files DIR --files-decompress; --canvas-slots 1..%d, --canvas-mib 1..4096\n", XRIT_CANVAS_MAX_SLOTS);
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
 
@@ -247,6 +265,14 @@ struct FrameDecode {
     std::vector<xrit_image_file> im_files;
     xrit_images_summary im_summary{};
     size_t rice_lines = 0, rice_faults = 0;
+    xrit_canvas *cv = nullptr;      // --canvas (set canvas_slots and canvas_bytes before open())
+    unsigned canvas_slots = 0;
+    size_t canvas_bytes = 0;
+    std::vector<xrit_canvas_file> cv_files;
+    std::vector<xrit_canvas_slot> cv_slots;
+    std::vector<uint8_t> cv_pixels, cv_row;
+    xrit_canvas_summary cv_summary{};
+    size_t canvases_written = 0;
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
     std::vector<xrit_frame_stats> records;
@@ -317,6 +343,14 @@ struct FrameDecode {
             if (decompress && xrit_images_create(&im, device) != XRIT_OK) {
                 std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
                 return false;
+            }
+            if (decompress && canvas_slots) {
+                if (xrit_canvas_create(&cv, device, canvas_slots, canvas_bytes) != XRIT_OK) {
+                    std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                    return false;
+                }
+                cv_slots.assign(canvas_slots, xrit_canvas_slot{});
+                cv_pixels.resize(canvas_bytes);
             }
         }
         return true;
@@ -476,6 +510,7 @@ struct FrameDecode {
                                f_pieces.size(), f_recs.data(), f_recs.size(), &f_summary) != XRIT_OK)
             return fail("files");
         if (decompress && !decode_images()) return false;
+        if (cv && !place_lines()) return false;
         for (size_t i = 0; i < f_summary.files; ++i) {
             const xrit_file_record &r = f_recs[i];
             const std::string stem = file_dir + "/vc" + std::to_string(r.vcid) + "_apid" + std::to_string(r.apid) + "_" +
@@ -531,6 +566,53 @@ struct FrameDecode {
         if (xrit_images_process(im, f_bytes.data(), f_summary.bytes, f_pieces.data(), f_summary.pieces, f_recs.data(), f_summary.files,
                                 &f_summary, img.data(), bound, im_lines.data(), f_summary.pieces, im_files.data(), &im_summary) != XRIT_OK)
             return fail("images");
+        return true;
+    }
+    // --canvas: this round's lines into their images' canvases; the ones that became complete are read, written and released
+    bool place_lines()
+    {
+        cv_files.resize(f_summary.files + 1);
+        if (xrit_canvas_process(cv, f_bytes.data(), f_summary.bytes, f_pieces.data(), f_summary.pieces, f_recs.data(), f_summary.files,
+                                &f_summary, img.data(), im_summary.bytes, im_lines.data(), im_summary.lines, im_files.data(), &im_summary,
+                                cv_files.data(), cv_slots.data(), &cv_summary) != XRIT_OK)
+            return fail("canvas");
+        for (unsigned s = 0; cv_summary.completed && s < canvas_slots; ++s) {
+            if (!cv_slots[s].in_use || !cv_slots[s].complete) continue;
+            if (!write_canvas(s, false)) return false;
+            if (xrit_canvas_release(cv, s) != XRIT_OK) return fail("canvas release");
+            cv_slots[s] = xrit_canvas_slot{};
+        }
+        return true;
+    }
+    // one canvas as binary PGM: DIR/<the annotation text reduced to [A-Za-z0-9._-]>.pgm, or vc<vcid>_img<image_id>_<born_call>
+    bool write_canvas(unsigned s, bool partial)
+    {
+        xrit_canvas_slot info{};
+        if (xrit_canvas_read(cv, s, cv_pixels.data(), cv_pixels.size(), &info) != XRIT_OK) return fail("canvas read");
+        std::string name;
+        for (size_t i = 0; i < sizeof info.name && info.name[i]; ++i) {
+            const char c = (char)info.name[i];
+            name += (std::isalnum((unsigned char)c) || c == '.' || c == '_' || c == '-') ? c : '_';
+        }
+        if (name.empty())
+            name = "vc" + std::to_string(info.vcid) + "_img" + std::to_string(info.image_id) + "_" + std::to_string(info.born_call);
+        const std::string path = file_dir + "/" + name + (partial ? ".partial.pgm" : ".pgm");
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::perror(path.c_str()); return false; }
+        const size_t width = info.bits <= 8 ? 1 : 2, row_bytes = (size_t)info.max_column * width;
+        bool ok = std::fprintf(f, "P5\n%u %u\n%u\n", info.max_column, info.max_row, (1u << info.bits) - 1u) > 0;
+        cv_row.resize(row_bytes);
+        for (size_t r = 0; ok && r < info.max_row; ++r) {
+            const uint8_t *src = cv_pixels.data() + r * info.pitch;
+            if (width == 2) {           // the canvas holds little-endian samples, PGM wants the high byte first
+                for (size_t i = 0; i < row_bytes; i += 2) { cv_row[i] = src[i + 1]; cv_row[i + 1] = src[i]; }
+                src = cv_row.data();
+            }
+            ok = std::fwrite(src, 1, row_bytes, f) == row_bytes;
+        }
+        std::fclose(f);
+        if (!ok) { std::perror(path.c_str()); return false; }
+        ++canvases_written;
         return true;
     }
     void close_packet_files()
@@ -596,6 +678,19 @@ struct FrameDecode {
                          (unsigned long long)f_summary.bad_packets, (unsigned long long)f_summary.seq_gaps,
                          (unsigned long long)f_summary.orphans);
             if (decompress) std::fprintf(stderr, "rice: %zu lines decoded, %zu faulted\n", rice_lines, rice_faults);
+            if (cv) {
+                size_t partial = 0;
+                for (unsigned s = 0; s < canvas_slots; ++s)
+                    if (cv_slots[s].in_use && write_canvas(s, true)) ++partial;
+                std::fprintf(stderr, "canvas: %llu images begun, %zu written (%zu of them partial), %llu lines placed, %llu clipped, "
+                                     "%llu segment files refused\n",
+                             (unsigned long long)cv_summary.canvases_begun, canvases_written, partial,
+                             (unsigned long long)cv_summary.lines_placed, (unsigned long long)cv_summary.lines_clipped,
+                             (unsigned long long)(cv_summary.bad_segment + cv_summary.too_large + cv_summary.duplicate + cv_summary.overlap +
+                                                  cv_summary.no_slot + cv_summary.no_placement));
+                xrit_canvas_destroy(cv);
+                cv = nullptr;
+            }
             xrit_files_destroy(fa);
             fa = nullptr;
             if (im) xrit_images_destroy(im);
@@ -919,6 +1014,8 @@ int main(int argc, char **argv)
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
     FrameDecode decode;
+    decode.canvas_slots = o.canvas ? o.canvas_slots : 0;
+    decode.canvas_bytes = o.canvas_mib << 20;
     if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
         !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync, o.flywheel)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
