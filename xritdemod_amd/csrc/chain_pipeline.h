@@ -34,11 +34,8 @@
 
 #include <stddef.h>
 
+#include "clock_jobs.h"     // XRIT_AHEAD: inputs that may wait behind the call in progress
 #include "clock_plan.h"
-
-#ifndef XRIT_AHEAD
-#define XRIT_AHEAD 2            // inputs that may wait behind the call in progress (bursts that walk overlapping blocks)
-#endif
 
 namespace xrit {
 

@@ -1041,8 +1041,6 @@ int ClockStage::init(float omega, float gain_omega, float mu, float gain_mu, flo
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && v >= 65536)
             lds_per_cu = v;
     }
-    cur = 0;
-    carry = 0;
     ov_enabled = getenv("XRIT_NO_OVERLAP") == nullptr;
     if (const char *e = getenv("XRIT_OV_HIST")) { const int v = atoi(e); if (v >= 1024) ov_hist = v; }
 #ifdef XRIT_EXPERIMENTS
@@ -1099,16 +1097,8 @@ __global__ void clock_state_reset_kernel(ClockState *st, float mu, float omega)
 int ClockStage::reset(hipStream_t s)
 {
     hipLaunchKernelGGL(clock_state_reset_kernel, dim3(1), dim3(1), 0, s, st.as<ClockState>(), mu0, par.omega_mid);
-    cur = 0;
-    carry = 0;
-    x_pending = -1;         // (samples a producer has put in place for a call that will not come)
-    for (auto &j : ov) j.state = 0;     // (the caller has waited for whatever walked ahead: xrit_demod_reset synchronises its streams)
-    ov_job = -1;
-    hist_xb = -1; hist_len = 0; hist_job = -1;
+    jobs.reset();           // (the caller has waited for whatever walked ahead: xrit_demod_reset synchronises its streams)
     if (ov_claim.p) (void)hipMemsetAsync(ov_claim.p, 0, RELAY_CLAIM_WORDS * sizeof(unsigned), s);
-    om_ext = false;         // (... and its timing statistic and count curve)
-    om_scanned = false;
-    in_flight = false;
     // what the stage has learnt from the stream it is leaving: as on a new handle (a reset handle gives a new handle's words)
     passes = 0;
     last_passes = -1;
@@ -1116,10 +1106,6 @@ int ClockStage::reset(hipStream_t s)
     relay_batch = 96;
     jmean_valid = false;
     last_symbols = 0;
-    prev_carry = 0;
-    prev_n = 0;
-    redo_ok = false;        // (nothing of an earlier call is left to run again, nor a flipped loop's state to start it from)
-    alt_valid = false;
     return XRIT_OK;
 }
 
@@ -1158,19 +1144,12 @@ void ClockStage::release()
 // block b covering buffer samples [offset + b*BL, ...).  Returns where to write it (double2 per block).
 double2 *ClockStage::om_slot(int nb, int BL)
 {
-    if (ov_job >= 0 && ov[ov_job].state == 1) {
-        // (an overlap job keeps its own statistic and curve: the walkers of the job behind it read them for their first ranges)
-        OvJob &j = ov[ov_job];
-        if (nb < 1 || j.om.reserve((size_t)nb * (sizeof(double2) + sizeof(double))) != XRIT_OK) return nullptr;
-        j.om_ext = true; j.om_scanned = false; j.nb = nb; j.BL = BL;
-        return j.om.as<double2>();
-    }
-    if (nb < 1 || om.reserve((size_t)nb * (sizeof(double2) + sizeof(double))) != XRIT_OK) return nullptr;
-    om_ext = true;
-    om_scanned = false;
-    om_nb = nb;
-    om_BL = BL;
-    return om.as<double2>();
+    // (an overlap job keeps its own statistic and curve: the walkers of the job behind it read them for their first ranges)
+    const int owner = jobs.om_owner();
+    DevBuf &buf = owner >= 0 ? ov[owner].om : om;
+    if (nb < 1 || buf.reserve((size_t)nb * (sizeof(double2) + sizeof(double))) != XRIT_OK) return nullptr;
+    jobs.om_noted(nb, BL);
+    return buf.as<double2>();
 }
 
 // the count curve of a statistic of nb blocks of BL samples in `buf` (the curve goes behind the statistic), with `wk` to work in
@@ -1196,10 +1175,9 @@ int ClockStage::om_scan(hipStream_t s)
 {
     // (an overlap job's curve is needed by its walkers' start states only: unwrapped on THEIR stream, ov_launch -- the
     // producer's stream, which sets a burst's pace, is spared two launches)
-    if (ov_job >= 0 && ov[ov_job].state == 1) return XRIT_OK;
-    if (!om_ext || om_nb < 1) return XRIT_OK;
-    XR_TRY(clock_unwrap(om, om_work, om_nb, om_BL, (double)sps, s));
-    om_scanned = true;
+    if (!jobs.om_scan_here()) return XRIT_OK;
+    XR_TRY(clock_unwrap(om, om_work, jobs.om_nb, jobs.om_BL, (double)sps, s));
+    jobs.om_scan_done();
     return XRIT_OK;
 }
 
@@ -1209,30 +1187,15 @@ int ClockStage::input_slot(size_t n, float2 **slot, hipStream_t s)
 {
     // A buffer nobody reads: not the one of the call in flight, not one whose walkers are at work (overlap jobs), and not the
     // one that holds the stream's last samples -- the history the next overlap call's first walkers warm up over.
-    bool busy[NXB] = {};
-    if (in_flight) busy[xb] = true;
-    for (int q = 0; q < NXB; ++q) if (ov[q].state != 0) busy[q] = true;
-    int b = -1;
     // (the call that follows the stream's last samples may not overwrite them -- unless nothing else is free)
-    for (int q = 0; q < NXB && b < 0; ++q) { const int c = (xb + 1 + q) % NXB; if (!busy[c] && c != hist_xb) b = c; }
-    for (int q = 0; q < NXB && b < 0; ++q) { const int c = (xb + q) % NXB; if (!busy[c]) b = c; }
-    if (b < 0) { set_error("clock recovery: no free sample buffer (%d calls are already in flight)", NXB); return XRIT_E_INVALID; }
-    // (a job whose first walkers warm up over what this buffer holds must have read it: its pad copy and start states)
+    const ClockSlotPick p = jobs.pick_buffer();
+    if (p.b < 0) { set_error("%s", p.err); return XRIT_E_INVALID; }
     for (int q = 0; q < NXB; ++q)
-        if (ov[q].state >= 2 && ov[q].hist_src == b) XR_HIP(hipStreamWaitEvent(s, ov[q].ev_guess, 0));
-    if (b == hist_xb) { hist_xb = -1; hist_len = 0; hist_job = -1; }
-    XR_TRY(xbuf[b].reserve((xpad + n + 64 + 16) * sizeof(float2)));
-    x_pending = b;
-    *slot = xbuf[b].as<float2>() + xpad;
-    ov_job = -1;
-    if (ov_eligible(n)) {
-        OvJob &j = ov[b];
-        j.state = 1;
-        j.n = n;
-        j.om_ext = false; j.om_scanned = false; j.nb = 0;
-        j.serial = ++ov_serial;
-        ov_job = b;
-    }
+        if (p.wait_guess[q]) XR_HIP(hipStreamWaitEvent(s, ov[q].ev_guess, 0));
+    if (p.forget) jobs.hist.forget();
+    XR_TRY(xbuf[p.b].reserve((xpad + n + 64 + 16) * sizeof(float2)));
+    *slot = xbuf[p.b].as<float2>() + xpad;
+    jobs.hand_out(p.b, n, ov_eligible(n));
     return XRIT_OK;
 }
 
@@ -1372,7 +1335,7 @@ int ClockStage::enqueue_relay(int count, bool restart, hipStream_t s, Profiler *
     unsigned *changed = reinterpret_cast<unsigned *>(segs + 3 * (size_t)j.G);
     RelayArgs a{};
     a.x = xbase(); a.table = table.as<float>(); a.N = j.N; a.ni = j.ni;
-    a.first = st.as<ClockState>() + cur; a.S = S.as<ClockState>();
+    a.first = st.as<ClockState>() + jobs.cur; a.S = S.as<ClockState>();
     a.K = j.K; a.cps = j.cps; a.NS = NS; a.G = j.G;
     a.start = segs; a.ends[0] = segs + j.G; a.ends[1] = segs + 2 * (size_t)j.G;
     // steps of the float32 lattice omega and mu + omega live on, in units of 2^-24 sample (the walkers' integer model)
@@ -1424,8 +1387,8 @@ int ClockStage::enqueue_relay(int count, bool restart, hipStream_t s, Profiler *
         // the chip behind the relay, waited ~90 us for them; four waves still waited 75 us behind the 2.4 ms matched filter
         // of a burst at the circuit rate, profiles/r4_c1_kernel_stats.csv)
         hipLaunchKernelGGL(clock_relay_finalize_kernel, dim3(1), dim3(64), 0, s, a.ends[0], a.ends[1], changed,
-                           j.relay_enq, j.G, j.cps * NS, st.as<ClockState>() + cur, st.as<ClockState>() + (cur ^ 1),
-                           clock_res(counters), a.x, tail.as<float2>() + 1024 * (cur ^ 1), j.N, clock_ctl(counters), j.relay_force ? 1 : 0,
+                           j.relay_enq, j.G, j.cps * NS, st.as<ClockState>() + jobs.cur, st.as<ClockState>() + (jobs.cur ^ 1),
+                           clock_res(counters), a.x, tail.as<float2>() + 1024 * (jobs.cur ^ 1), j.N, clock_ctl(counters), j.relay_force ? 1 : 0,
                            a.moments);
     }
     XR_HIP(hipGetLastError());
@@ -1505,9 +1468,9 @@ int ClockStage::enqueue_output(hipStream_t s, Profiler *prof, bool again)
 {
     const Job &j = job;
     const float2 *x = xbase();
-    const ClockState *st_in = st.as<ClockState>() + cur;
-    ClockState *st_out = st.as<ClockState>() + (cur ^ 1);
-    float2 *tail_out = tail.as<float2>() + 1024 * (cur ^ 1);
+    const ClockState *st_in = st.as<ClockState>() + jobs.cur;
+    ClockState *st_out = st.as<ClockState>() + (jobs.cur ^ 1);
+    float2 *tail_out = tail.as<float2>() + 1024 * (jobs.cur ^ 1);
     const unsigned nw = div_up((size_t)j.K, 64);
     {
         ProfScope ps(prof, "clock_output", s);
@@ -1550,119 +1513,92 @@ int ClockStage::enqueue_output(hipStream_t s, Profiler *prof, bool again)
 
 // ---- overlapping exactly walked blocks: host side (clock_overlap.h) -------------------------------------------------  (the job's ranges: clock_ov_plan, clock_plan.h)
 
-bool ClockStage::ov_can_launch_ahead(int job) const
-{
-    if (job < 0 || job >= NXB || ov[job].state != 1 || !ov[job].om_ext) return false;
-    // the job in front must be an overlap job whose samples and timing curve are in place (its walkers may still be at work)
-    for (int q = 0; q < NXB; ++q)
-        if (q != job && ov[q].state >= 1 && ov[q].serial + 1 == ov[job].serial)
-            return ov[q].om_scanned && (size_t)ov[q].padN + ov[q].n >= (size_t)ov_pad_need && ov[q].state >= 2;
-    return false;
-}
-
-static inline unsigned *ov_stat(ClockStage::OvJob &j) { return j.aux.as<unsigned>(); }
-static inline unsigned long long *ov_moments(ClockStage::OvJob &j) { return reinterpret_cast<unsigned long long *>(j.aux.as<unsigned>() + 8); }
-static inline unsigned long long *ov_offs(ClockStage::OvJob &j) { return reinterpret_cast<unsigned long long *>(j.aux.as<char>() + 64); }
-static inline int *ov_j0(ClockStage::OvJob &j) { return reinterpret_cast<int *>(j.aux.as<char>() + 64 + (size_t)j.G * sizeof(unsigned long long)); }
+static inline unsigned *ov_stat(ClockStage::OvJob &d) { return d.aux.as<unsigned>(); }
+static inline unsigned long long *ov_moments(ClockStage::OvJob &d) { return reinterpret_cast<unsigned long long *>(d.aux.as<unsigned>() + 8); }
+static inline unsigned long long *ov_offs(ClockStage::OvJob &d) { return reinterpret_cast<unsigned long long *>(d.aux.as<char>() + 64); }
+static inline int *ov_j0(ClockStage::OvJob &d, int G) { return reinterpret_cast<int *>(d.aux.as<char>() + 64 + (size_t)G * sizeof(unsigned long long)); }
 
 int ClockStage::ov_launch(int job, hipStream_t sw, bool ahead, Profiler *prof)
 {
-    OvJob &j = ov[job];
-    // the history: the job in front when launched ahead (it has not finished: hist_* still describe the call before it)
-    int h_xb = hist_xb, h_job = hist_job;
-    size_t h_len = hist_len;
-    size_t h_n = 0;
-    if (ahead) {
-        int front = -1;
-        for (int q = 0; q < NXB; ++q) if (q != job && ov[q].state >= 1 && ov[q].serial + 1 == j.serial) front = q;
-        if (front < 0) { set_error("clock recovery: no job in front of a job launched ahead"); return XRIT_E_INVALID; }
-        h_xb = front; h_job = front; h_len = (size_t)ov[front].padN + ov[front].n;
-        XR_HIP(hipStreamWaitEvent(sw, ov[front].ev_guess, 0));      // (the curve of the job in front is unwrapped on ITS walkers' stream)
-    }
+    const ClockJob &j = jobs.job[job];      // the job's plain record (clock_jobs.h) ...
+    OvJob &d = ov[job];                     // ... and its device buffers and events
     // history: the samples the call in front left at the end of its buffer, and the timing curve that covers them
-    const bool have_hist = h_xb >= 0 && h_len >= (size_t)ov_pad_need && h_job >= 0 && ov[h_job].om_scanned;      // (scanned: the job in front has been launched)
+    const ClockLaunchHist h = jobs.launch_hist(job, ahead, ov_pad_need);
+    if (h.err) { set_error("%s", h.err); return XRIT_E_INVALID; }
+    if (h.wait_guess >= 0) XR_HIP(hipStreamWaitEvent(sw, ov[h.wait_guess].ev_guess, 0));
+    size_t h_n = 0;
     {
-        const ClockOvPlan plan = clock_ov_plan(*this, j.n, carry, have_hist, ahead);
+        const ClockOvPlan plan = clock_ov_plan(*this, j.n, jobs.carry, h.have, ahead);
         if (plan.err[0]) { set_error("%s", plan.err); return XRIT_E_INVALID; }
-        static_cast<ClockOvPlan &>(j) = plan;
-        j.ahead = ahead;
-        XR_TRY(j.segs.reserve((size_t)j.G * sizeof(OverlapSeg)));
-        XR_TRY(j.S.reserve((size_t)j.G * sizeof(ClockState)));
-        XR_TRY(j.stage.reserve((size_t)j.G * (size_t)j.stride * sizeof(float) + 256));
+        jobs.planned(job, plan, ahead);
+        XR_TRY(d.segs.reserve((size_t)j.G * sizeof(OverlapSeg)));
+        XR_TRY(d.S.reserve((size_t)j.G * sizeof(ClockState)));
+        XR_TRY(d.stage.reserve((size_t)j.G * (size_t)j.stride * sizeof(float) + 256));
         // aux: [0, 8) counters, [8, 12) moments (two 64-bit words), then j0[G] and offs[G] (64-bit, 8-byte aligned)
-        XR_TRY(j.aux.reserve(64 + (size_t)j.G * sizeof(int) + 8 + (size_t)j.G * sizeof(unsigned long long)));
+        XR_TRY(d.aux.reserve(64 + (size_t)j.G * sizeof(int) + 8 + (size_t)j.G * sizeof(unsigned long long)));
     }
     float2 *data = xbuf[job].as<float2>() + xpad;
     float2 *base = data - j.padN;
     if (!j.w0_carried) {
         // the last padN samples of the stream in front of the new ones
-        if (!(h_job >= 0 && h_xb == h_job) || h_len < (size_t)j.padN) { set_error("clock recovery: history without its job"); return XRIT_E_INVALID; }
-        h_n = ov[h_job].n;
-        const float2 *hend = xbuf[h_xb].as<float2>() + xpad + h_n;
+        if (const char *e = ClockJobs::hist_refusal(h, j)) { set_error("%s", e); return XRIT_E_INVALID; }
+        h_n = jobs.job[h.job].n;
+        const float2 *hend = xbuf[h.xb].as<float2>() + xpad + h_n;
         XR_HIP(hipMemcpyAsync(base, hend - j.padN, (size_t)j.padN * sizeof(float2), hipMemcpyDeviceToDevice, sw));
-        j.hist_src = h_xb;
     } else if (j.padN > 0) {
-        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, sw, tail.as<float2>() + 1024 * cur, base, j.padN);
+        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, sw, tail.as<float2>() + 1024 * jobs.cur, base, j.padN);
     }
     // the timing curve: the producer's (Costas final pass + om_scan), else computed here
+    int nb = j.nb;
     const int BL = j.om_ext ? j.BL : CLK_OM_BLOCK;
     if (!j.om_ext) {
-        j.nb = (int)((j.n + CLK_OM_BLOCK - 1) / CLK_OM_BLOCK);
-        j.BL = CLK_OM_BLOCK;
-        XR_TRY(j.om.reserve((size_t)j.nb * (sizeof(double2) + sizeof(double))));
-        hipLaunchKernelGGL(clock_om_kernel, dim3(div_up((size_t)j.nb, 4)), dim3(256), 0, sw, data, j.om.as<double2>(), (long long)j.n, j.nb,
+        nb = (int)((j.n + CLK_OM_BLOCK - 1) / CLK_OM_BLOCK);
+        XR_TRY(d.om.reserve((size_t)nb * (sizeof(double2) + sizeof(double))));
+        hipLaunchKernelGGL(clock_om_kernel, dim3(div_up((size_t)nb, 4)), dim3(256), 0, sw, data, d.om.as<double2>(), (long long)j.n, nb,
                            1.0 / (double)sps);
-        j.om_ext = true;
     }
-    if (!j.om_scanned && j.nb >= 1) {
-        // (an overlap job's curve is unwrapped here, on its walkers' stream: om_scan)
-        XR_TRY(clock_unwrap(j.om, j.om_work, j.nb, j.BL, (double)sps, sw));
-        j.om_scanned = true;
-    }
-    const double *cnt = reinterpret_cast<const double *>(j.om.as<char>() + (size_t)j.nb * sizeof(double2));
+    // (an overlap job's curve is unwrapped here, on its walkers' stream: om_scan)
+    if (!j.om_scanned && nb >= 1) XR_TRY(clock_unwrap(d.om, d.om_work, nb, BL, (double)sps, sw));
+    const double *cnt = reinterpret_cast<const double *>(d.om.as<char>() + (size_t)nb * sizeof(double2));
     const double *cnt_prev = nullptr;
     int nb_prev = 0;
-    if (!j.w0_carried && h_job >= 0) {
-        OvJob &p = ov[h_job];
-        cnt_prev = reinterpret_cast<const double *>(p.om.as<char>() + (size_t)p.nb * sizeof(double2));
+    if (!j.w0_carried && h.job >= 0) {
+        const ClockJob &p = jobs.job[h.job];
+        cnt_prev = reinterpret_cast<const double *>(ov[h.job].om.as<char>() + (size_t)p.nb * sizeof(double2));
         nb_prev = p.nb;
         if (p.BL != BL) { set_error("clock recovery: timing curves of consecutive calls differ in their block length"); return XRIT_E_INVALID; }
     }
     OverlapArgs a{};
     a.x = base; a.table = table.as<float>(); a.N = j.N; a.ni = j.ni;
-    a.start = j.S.as<ClockState>(); a.G = j.G; a.store0 = j.store0; a.first_bound = j.first_bound; a.Ls = j.Ls; a.early = j.early;
-    a.stride = j.stride; a.stage = j.stage.as<float>(); a.segs = j.segs.as<OverlapSeg>(); a.par = par;
+    a.start = d.S.as<ClockState>(); a.G = j.G; a.store0 = j.store0; a.first_bound = j.first_bound; a.Ls = j.Ls; a.early = j.early;
+    a.stride = j.stride; a.stage = d.stage.as<float>(); a.segs = d.segs.as<OverlapSeg>(); a.par = par;
     const ClockLattice lat = clock_lattice(par.omega_mid);
     a.q_om = lat.q_om; a.q_mu = lat.q_mu;
-    a.stat = ov_stat(j); a.moments = ov_moments(j); a.simd_claim = relay_no_claim ? nullptr : ov_claim.as<unsigned>();
+    a.stat = ov_stat(d); a.moments = ov_moments(d); a.simd_claim = relay_no_claim ? nullptr : ov_claim.as<unsigned>();
     const int span = relay_span(par, 64);
-    j.hist_src = j.w0_carried ? -1 : j.hist_src;
     {
         ProfScope ps(prof, "clock_guess", sw);
-        hipLaunchKernelGGL(clock_overlap_guess_kernel, dim3(div_up((size_t)j.G, 256)), dim3(256), 0, sw, cnt, j.nb, cnt_prev, nb_prev,
+        hipLaunchKernelGGL(clock_overlap_guess_kernel, dim3(div_up((size_t)j.G, 256)), dim3(256), 0, sw, cnt, nb, cnt_prev, nb_prev,
                            (long long)h_n, BL, (double)sps, par.omega_mid, base, table.as<float>(), j.ni, j.padN, j.hist, j.G, j.store0,
-                           j.first_bound, j.Ls, st.as<ClockState>() + cur, j.w0_carried ? 1 : 0, j.w0_ii, 0, j.S.as<ClockState>(),
+                           j.first_bound, j.Ls, st.as<ClockState>() + jobs.cur, j.w0_carried ? 1 : 0, j.w0_ii, 0, d.S.as<ClockState>(),
                            a.stat, a.moments);
     }
-    XR_HIP(hipEventRecord(j.ev_guess, sw));       // (from here on the history this job was started from may be overwritten)
+    XR_HIP(hipEventRecord(d.ev_guess, sw));       // (from here on the history this job was started from may be overwritten)
     {
         ProfScope ps(prof, "clock_overlap", sw);
         if (ov_small_ring && span + 8 <= 1024 - RELAY_XCH - 72) hipLaunchKernelGGL(clock_overlap_kernel<1024>, dim3(j.G), dim3(128), 0, sw, a, span);
         else hipLaunchKernelGGL(clock_overlap_kernel<RELAY_RX>, dim3(j.G), dim3(128), 0, sw, a, span);
     }
     XR_HIP(hipGetLastError());
-    XR_HIP(hipEventRecord(j.ev_walk, sw));
-    j.state = 2;
+    XR_HIP(hipEventRecord(d.ev_walk, sw));
+    jobs.launched(job, h, nb, BL);
     return XRIT_OK;
 }
 
-int ClockStage::ov_restart(int job, hipStream_t s)
+int ClockStage::ov_restart(int job)
 {
-    (void)s;
-    if (job < 0 || job >= NXB) return XRIT_OK;
-    OvJob &j = ov[job];
-    if (j.state == 2) XR_HIP(hipEventSynchronize(j.ev_walk));
-    if (j.state >= 1) { j.state = 1; j.om_scanned = false; }
+    if (jobs.restart_waits(job)) XR_HIP(hipEventSynchronize(ov[job].ev_walk));
+    jobs.restarted(job);
     return XRIT_OK;
 }
 
@@ -1670,15 +1606,11 @@ int ClockStage::ov_restart(int job, hipStream_t s)
 // that did not fit: a timing guess off by a symbol): the relay of clock_relay.h, to closure, on the same samples
 int ClockStage::ov_fallback(size_t *n_out, hipStream_t s, Profiler *prof, bool to_closure)
 {
-    const int job = ov_cur;
-    OvJob &j = ov[job];
-    ov_cur = -1;
-    j.state = 0;
-    xb = job;
+    const int job = jobs.overlap_fell_back();
     // the call's samples lie where they were produced; the tail goes in front.  (No signal -- the walkers of a loop that is not
     // locked do not meet at the joints --: the relay's own default, which does not pursue a closure on such an input either)
-    const int rc = run_chains(xbuf[job].as<float2>() + xpad - carry, to_closure ? 1 : 0, j.n, ov_soft, nullptr, ov_cap, n_out, s, prof);
-    if (rc == XRIT_OK) { hist_xb = job; hist_len = (size_t)j.padN + j.n; hist_job = job; }
+    const int rc = run_chains(xbuf[job].as<float2>() + xpad - jobs.carry, to_closure ? 1 : 0, jobs.job[job].n, ov_soft, nullptr, ov_cap, n_out, s, prof);
+    if (rc == XRIT_OK) jobs.ended_fallback(job);
     ov_fell_back = true;
     return rc;
 }
@@ -1686,23 +1618,24 @@ int ClockStage::ov_fallback(size_t *n_out, hipStream_t s, Profiler *prof, bool t
 // the joints, the output and the call's result, on the call's stream behind the walkers
 int ClockStage::ov_finalize(int job, float *soft_out, size_t cap, hipStream_t s, Profiler *prof)
 {
-    OvJob &j = ov[job];
-    XR_HIP(hipStreamWaitEvent(s, j.ev_walk, 0));
-    if (j.ahead) j.w0_ii = j.padN - (int)carry;        // (known now: the call in front has finished)
+    const ClockJob &j = jobs.job[job];
+    OvJob &d = ov[job];
+    XR_HIP(hipStreamWaitEvent(s, d.ev_walk, 0));
+    jobs.w0_known(job);
     {
         ProfScope ps(prof, "clock_joints", s);
         hipLaunchKernelGGL(clock_reset_kernel, dim3(1), dim3(256), 0, s, counters.as<unsigned>(), CLK_CTL_WORDS, (int *)nullptr);
-        hipLaunchKernelGGL(clock_overlap_scan_kernel, dim3(1), dim3(256), 0, s, j.segs.as<OverlapSeg>(), j.G, j.stride,
-                           st.as<ClockState>() + cur, j.w0_ii, j.w0_carried ? 1 : 0, par.omega_mid, ov_j0(j), ov_offs(j),
-                           st.as<ClockState>() + (cur ^ 1), clock_res(counters), xbuf[job].as<float2>() + xpad - j.padN,
-                           tail.as<float2>() + 1024 * (cur ^ 1), j.N, clock_ctl(counters), ov_moments(j), (unsigned long long)cap);
+        hipLaunchKernelGGL(clock_overlap_scan_kernel, dim3(1), dim3(256), 0, s, d.segs.as<OverlapSeg>(), j.G, j.stride,
+                           st.as<ClockState>() + jobs.cur, j.w0_ii, j.w0_carried ? 1 : 0, par.omega_mid, ov_j0(d, j.G), ov_offs(d),
+                           st.as<ClockState>() + (jobs.cur ^ 1), clock_res(counters), xbuf[job].as<float2>() + xpad - j.padN,
+                           tail.as<float2>() + 1024 * (jobs.cur ^ 1), j.N, clock_ctl(counters), ov_moments(d), (unsigned long long)cap);
         if (soft_out)
-            hipLaunchKernelGGL(clock_overlap_copy_kernel, dim3(div_up((size_t)j.stride, 1024), j.G), dim3(256), 0, s, j.stage.as<float>(),
-                               j.segs.as<OverlapSeg>(), ov_j0(j), ov_offs(j), j.stride, soft_out, (unsigned long long)cap, clock_res(counters));
+            hipLaunchKernelGGL(clock_overlap_copy_kernel, dim3(div_up((size_t)j.stride, 1024), j.G), dim3(256), 0, s, d.stage.as<float>(),
+                               d.segs.as<OverlapSeg>(), ov_j0(d, j.G), ov_offs(d), j.stride, soft_out, (unsigned long long)cap, clock_res(counters));
     }
     XR_HIP(hipGetLastError());
     XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    j.state = 3;
+    jobs.finalizing(job);
     return XRIT_OK;
 }
 
@@ -1715,25 +1648,16 @@ void ClockStage::call_reset(size_t n)
     unconverged = 0;
     large_open = 0;
     max_residual = 0;
-    prev_carry = carry;
-    prev_n = n;
-    redo_ok = false;
     ov_fell_back = false;
-    ov_cur = -1;
+    jobs.call_reset(n);
 }
 
 int ClockStage::begin(size_t n, float *soft_out, float2 *sym_out, size_t cap, hipStream_t s, Profiler *prof)
 {
     call_reset(n);
     // this call's overlap job, if its samples were produced into one (input_slot): the oldest job that waits for its call
-    unsigned long long first = ~0ull;
-    for (int q = 0; q < NXB; ++q)
-        if ((ov[q].state == 1 || ov[q].state == 2) && ov[q].serial < first) { first = ov[q].serial; ov_cur = q; }
-    if (ov_cur >= 0 && (ov[ov_cur].n != n || sym_out != nullptr)) {
-        set_error("clock recovery: the call does not match the overlap job its samples were produced for");
-        return XRIT_E_INVALID;
-    }
-    if (ov_cur >= 0) return begin_overlap(n, soft_out, cap, s, prof);
+    if (const char *e = jobs.call_job(n, sym_out != nullptr)) { set_error("%s", e); return XRIT_E_INVALID; }
+    if (jobs.ov_cur >= 0) return begin_overlap(n, soft_out, cap, s, prof);
     return begin_chains(nullptr, exact, n, soft_out, sym_out, cap, s, prof);
 }
 
@@ -1741,14 +1665,11 @@ int ClockStage::begin_overlap(size_t n, float *soft_out, size_t cap, hipStream_t
 {
     job = Job{};
     job.n = n; job.soft = soft_out; job.cap = cap; job.exact = exact;
-    xb = ov_cur;
-    x_pending = -1;
-    ov_job = -1;
-    in_flight = true;
-    om_ext = false; om_scanned = false;
+    jobs.begun_overlap();
     ov_soft = soft_out; ov_cap = cap;
-    if (ov[ov_cur].state == 1) XR_TRY(ov_launch(ov_cur, s, false, prof));
-    return ov_finalize(ov_cur, soft_out, cap, s, prof);
+    const int q = jobs.ov_cur;
+    if (jobs.job[q].state == CLK_JOB_SLOT) XR_TRY(ov_launch(q, s, false, prof));
+    return ov_finalize(q, soft_out, cap, s, prof);
 }
 
 // the chains of a call whose [carry | new] samples lie at `base` (null: in the call's own buffer), with `exact_` for
@@ -1760,26 +1681,20 @@ int ClockStage::begin_chains(float2 *base, int exact_, size_t n, float *soft_out
     const int relay_w = relay_w_plan();
     job = Job{};
     Job &j = job;
-    static_cast<ClockChainPlan &>(j) = clock_chain_plan(k, n, carry, last_passes, relay_w);
+    static_cast<ClockChainPlan &>(j) = clock_chain_plan(k, n, jobs.carry, last_passes, relay_w);
     j.n = n; j.soft = soft_out; j.sym = sym_out; j.cap = cap; j.base = base; j.exact = exact_; j.relay_w = relay_w;
     if (j.N >= (1LL << 31)) { set_error("%s", j.err); return XRIT_E_INVALID; }
-    if (!base) {
-        if (x_pending >= 0) xb = x_pending;
-        x_pending = -1;
-        XR_TRY(xbuf[xb].reserve((size_t)(xpad + n + 64 + 16) * sizeof(float2)));
-    }
-    in_flight = true;
-    if (carry)
-        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, s, tail.as<float2>() + 1024 * cur, xbase(), (int)carry);
-    const bool ext = om_ext;          // statistic supplied by the producer of the samples (Costas final pass)
-    const bool scanned = ext && om_scanned;       // ... and its count curve too (om_scan)
-    om_ext = false;
-    om_scanned = false;
+    jobs.chains_buffer(!base);
+    if (!base) XR_TRY(xbuf[jobs.xb].reserve((size_t)(xpad + n + 64 + 16) * sizeof(float2)));
+    // om: the statistic supplied by the producer of the samples (Costas final pass), and its count curve too (om_scan)
+    const ClockOm om_in = jobs.begun_chains();
+    if (jobs.carry)
+        hipLaunchKernelGGL(clock_tail_kernel, dim3(1), dim3(1024), 0, s, tail.as<float2>() + 1024 * jobs.cur, xbase(), (int)jobs.carry);
     if (j.err[0]) { set_error("%s", j.err); return XRIT_E_INVALID; }
     if (j.short_input) return begin_short(s);
     if (serial) return begin_serial(s, prof);
     NS = j.NS;
-    return launch_chains(ext, scanned, s, prof);
+    return launch_chains(om_in.ext, om_in.scanned, s, prof);
 }
 
 // not enough samples for a single symbol: everything is carried to the next call
@@ -1787,9 +1702,9 @@ int ClockStage::begin_short(hipStream_t s)
 {
     const Job &j = job;
     if (j.N > 0)
-        XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * (cur ^ 1), xbase(), (size_t)j.N * sizeof(float2),
+        XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * (jobs.cur ^ 1), xbase(), (size_t)j.N * sizeof(float2),
                               hipMemcpyDeviceToDevice, s));
-    XR_HIP(hipMemcpyAsync(st.as<ClockState>() + (cur ^ 1), st.as<ClockState>() + cur, sizeof(ClockState),
+    XR_HIP(hipMemcpyAsync(st.as<ClockState>() + (jobs.cur ^ 1), st.as<ClockState>() + jobs.cur, sizeof(ClockState),
                           hipMemcpyDeviceToDevice, s));
     return XRIT_OK;
 }
@@ -1801,8 +1716,8 @@ int ClockStage::begin_serial(hipStream_t s, Profiler *prof)
     {
         ProfScope ps(prof, "clock_serial", s);
         hipLaunchKernelGGL(clock_serial_kernel, dim3(1), dim3(64), 0, s, xbase(), table.as<float>(),
-                           st.as<ClockState>() + cur, st.as<ClockState>() + (cur ^ 1), clock_res(counters), j.soft,
-                           j.sym, (unsigned long long)j.cap, j.N, j.ni, par, tail.as<float2>() + 1024 * (cur ^ 1));
+                           st.as<ClockState>() + jobs.cur, st.as<ClockState>() + (jobs.cur ^ 1), clock_res(counters), j.soft,
+                           j.sym, (unsigned long long)j.cap, j.N, j.ni, par, tail.as<float2>() + 1024 * (jobs.cur ^ 1));
     }
     XR_HIP(hipGetLastError());
     XR_HIP(hipMemcpyAsync(h_res, counters.p, CLK_CTL_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -1815,11 +1730,11 @@ int ClockStage::launch_chains(bool ext, bool scanned, hipStream_t s, Profiler *p
     Job &j = job;
     const int K = j.K;
     float2 *x = xbase();
-    const int BL = ext ? om_BL : CLK_OM_BLOCK;
+    const int BL = ext ? jobs.om_BL : CLK_OM_BLOCK;
     // (the producer's statistic: block b covers buffer samples [carry + b BL, ...), its phasor counted from the first new sample:
     // the count curve is computed in those coordinates -- same symbol instants, see om_scan -- and placed `carry` samples in)
-    const double om_off = ext ? (double)carry : 0.0;
-    const int nb = ext ? om_nb : (int)((j.N + CLK_OM_BLOCK - 1) / CLK_OM_BLOCK);
+    const double om_off = ext ? (double)jobs.carry : 0.0;
+    const int nb = ext ? jobs.om_nb : (int)((j.N + CLK_OM_BLOCK - 1) / CLK_OM_BLOCK);
     XR_TRY(S.reserve((size_t)K * sizeof(ClockState)));
     XR_TRY(E.reserve((size_t)K * sizeof(ClockState)));
     XR_TRY(J.reserve((size_t)K * sizeof(float4)));
@@ -1845,7 +1760,7 @@ int ClockStage::launch_chains(bool ext, bool scanned, hipStream_t s, Profiler *p
     j.written = flags.as<int>() + 3 * K + 4;
     double2 *X = om.as<double2>();
     double *cnt = reinterpret_cast<double *>(om.as<char>() + (size_t)nb * sizeof(double2));
-    const ClockState *st_in = st.as<ClockState>() + cur;
+    const ClockState *st_in = st.as<ClockState>() + jobs.cur;
     if (K <= 1) hipLaunchKernelGGL(clock_reset_kernel, dim3(1), dim3(256), 0, s, counters.as<unsigned>(), (max_passes + 5) * 8, j.terminal);
     if (K > 1) {
         {
@@ -1889,12 +1804,11 @@ bool ClockStage::closed() const
 int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
 {
     *n_out = 0;
-    in_flight = false;      // (the caller has synchronised: whatever finish() still enqueues it waits for itself)
-    if (ov_cur >= 0) return finish_overlap(n_out, s, prof);
+    jobs.call_ended();      // (the caller has synchronised: whatever finish() still enqueues it waits for itself)
+    if (jobs.ov_cur >= 0) return finish_overlap(n_out, s, prof);
     if (job.short_input) {
-        carry = (size_t)job.N;
+        jobs.ended_short(job.N);
         last_symbols = 0;
-        cur ^= 1;
         return XRIT_OK;
     }
     return finish_chains(n_out, s, prof);
@@ -1902,7 +1816,7 @@ int ClockStage::finish(size_t *n_out, hipStream_t s, Profiler *prof)
 
 int ClockStage::finish_overlap(size_t *n_out, hipStream_t s, Profiler *prof)
 {
-    OvJob &oj = ov[ov_cur];
+    const ClockJob &oj = jobs.job[jobs.ov_cur];
     const int *hc = reinterpret_cast<const int *>(h_res);
     ClockResult r;
     memcpy(&r, reinterpret_cast<const unsigned *>(h_res) + CLK_RES_WORD, sizeof r);
@@ -1916,25 +1830,21 @@ int ClockStage::finish_overlap(size_t *n_out, hipStream_t s, Profiler *prof)
     relay_seg_chains = 0;
     passes = 0;
     unconverged = 0; max_residual = 0; large_open = 0;     // (the hand-off's figures: this plan has no hand-off)
-    if (trace_env) XR_TRY(trace_overlap(oj, r));
+    if (trace_env) XR_TRY(trace_overlap(jobs.ov_cur, r));
     const ClockOvVerdict v = clock_overlap_look(*this, hc);
-    if (v == CLK_OV_WATCHDOG) { set_error("clock recovery: a walker gave up waiting for its sample ring (watchdog)"); oj.state = 0; ov_cur = -1; return XRIT_E_HIP; }
+    if (v == CLK_OV_WATCHDOG) { set_error("clock recovery: a walker gave up waiting for its sample ring (watchdog)"); (void)jobs.overlap_released(); return XRIT_E_HIP; }
     if (v != CLK_OV_TAKE) return ov_fallback(n_out, s, prof, v == CLK_OV_FALLBACK_TO_CLOSURE);
-    oj.state = 0;
-    const int jb = ov_cur;
-    ov_cur = -1;
+    const int jb = jobs.overlap_released();
     if (!r.ok) {
         if ((size_t)r.n_symbols > ov_cap) { set_error("clock recovery produced %zu symbols, capacity %zu", (size_t)r.n_symbols, ov_cap); return XRIT_E_CAPACITY; }
         set_error("clock recovery: the walkers did not reach the end of the input");
         return XRIT_E_INVALID;
     }
-    cur ^= 1;
-    carry = (size_t)(oj.N - r.ii_final);
-    if (carry > 1024) { set_error("clock recovery: carry of %zu samples exceeds the hand-over buffer", carry); return XRIT_E_INVALID; }
+    jobs.flip();
+    if (const char *e = jobs.carried(oj.N - r.ii_final)) { set_error("%s", e); return XRIT_E_INVALID; }
     last_symbols = (size_t)r.n_symbols;
     *n_out = last_symbols;
-    hist_xb = jb; hist_len = (size_t)oj.padN + oj.n; hist_job = jb;
-    redo_ok = true;
+    jobs.ended_overlap(jb);
     return XRIT_OK;
 }
 
@@ -2025,7 +1935,7 @@ int ClockStage::finish_chains(size_t *n_out, hipStream_t s, Profiler *prof)
     if (trace_env && job.K > 1) XR_TRY(trace_passes());
     ClockResult r;
     memcpy(&r, reinterpret_cast<const unsigned *>(h_res) + CLK_RES_WORD, sizeof r);
-    cur ^= 1;
+    jobs.flip();
     if (!r.ok && serial) {
         set_error("clock recovery produced more than the %zu symbols the output holds", job.cap);
         return XRIT_E_CAPACITY;
@@ -2038,30 +1948,26 @@ int ClockStage::finish_chains(size_t *n_out, hipStream_t s, Profiler *prof)
         set_error("clock recovery: chain budget exhausted before the end of the input");
         return XRIT_E_INVALID;
     }
-    carry = (size_t)(job.N - r.ii_final);
-    if (carry > 1024) {
-        set_error("clock recovery: carry of %zu samples exceeds the hand-over buffer", carry);
-        return XRIT_E_INVALID;
-    }
+    if (const char *e = jobs.carried(job.N - r.ii_final)) { set_error("%s", e); return XRIT_E_INVALID; }
     last_symbols = (size_t)r.n_symbols;
     *n_out = last_symbols;
     if (last_symbols > job.cap) {
         set_error("clock recovery produced %zu symbols, capacity %zu", last_symbols, job.cap);
         return XRIT_E_CAPACITY;
     }
-    redo_ok = true;
     // (what this call left in its buffer is history for an overlap call behind it only together with a timing curve: none here;
     // a call on samples that lie elsewhere leaves what there was)
-    if (!job.base) { hist_xb = xb; hist_len = prev_carry + prev_n; hist_job = -1; }
+    jobs.ended_chains(!job.base);
     return XRIT_OK;
 }
 
 // ---- XRIT_TRACE=1: what a call did, on stderr ---------------------------------------------------------------------
-int ClockStage::trace_overlap(const OvJob &oj, const ClockResult &r) const
+int ClockStage::trace_overlap(int job, const ClockResult &r) const
 {
+    const ClockJob &oj = jobs.job[job];
     const int *hc = reinterpret_cast<const int *>(h_res);
     unsigned hs[8];
-    XR_HIP(hipMemcpy(hs, oj.aux.p, sizeof hs, hipMemcpyDeviceToHost));
+    XR_HIP(hipMemcpy(hs, ov[job].aux.p, sizeof hs, hipMemcpyDeviceToHost));
     fprintf(stderr, "[xrit] overlap: %d walkers over ranges of %d samples behind %d samples of history (%s), %u steps, %.2f guess rounds per step; "
                     "joints: %d do not fit, largest distance %.3e sample; 2 Es/N0 = %.1f; %llu symbols%s\n",
             oj.G, oj.Ls, oj.hist, oj.w0_carried ? "walker 0 from the carried state" : "walker 0 warms up in the burst before", hs[0],
@@ -2182,26 +2088,22 @@ static constexpr size_t CLK_ALT_SLOT = sizeof(ClockState) + 1024 * sizeof(float2
 int ClockStage::redo_flipped(float *soft_out, float2 *sym_out, size_t cap, size_t *n_out, hipStream_t s, Profiler *prof)
 {
     *n_out = 0;
-    if (!redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
-    // finish() moved on to the other state / tail slot: back to the one the call started from (untouched since)
-    cur ^= 1;
+    if (!jobs.redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
+    // finish() moved on to the other state / tail slot: back to the one the call started from (untouched since).  (The samples
+    // kept as the NEXT call's history are negated now: walkers of an overlap job must not warm up over them)
+    const bool from_alt = jobs.step_back_flipped();
     float2 *data = xdata();     // where the call's input lies
-    const size_t n = prev_n;
-    if (alt_valid) {
+    const size_t n = jobs.prev_n, carry = jobs.carry;
+    if (from_alt) {
         // the flipped loop's own state (make_alt) in place of this one's
-        XR_HIP(hipMemcpyAsync(st.as<ClockState>() + cur, alt.p, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
-        XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * cur, alt.as<char>() + sizeof(ClockState), 1024 * sizeof(float2),
+        XR_HIP(hipMemcpyAsync(st.as<ClockState>() + jobs.cur, alt.p, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
+        XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * jobs.cur, alt.as<char>() + sizeof(ClockState), 1024 * sizeof(float2),
                               hipMemcpyDeviceToDevice, s));
-        carry = alt_carry;
-        alt_valid = false;
     } else {
-        carry = prev_carry;
-        hipLaunchKernelGGL(clock_flip_state_kernel, dim3(1), dim3(1), 0, s, st.as<ClockState>() + cur);
-        if (carry) hipLaunchKernelGGL(clock_negate_kernel, dim3(div_up(carry, 256)), dim3(256), 0, s, tail.as<float2>() + 1024 * cur, carry);
+        hipLaunchKernelGGL(clock_flip_state_kernel, dim3(1), dim3(1), 0, s, st.as<ClockState>() + jobs.cur);
+        if (carry) hipLaunchKernelGGL(clock_negate_kernel, dim3(div_up(carry, 256)), dim3(256), 0, s, tail.as<float2>() + 1024 * jobs.cur, carry);
     }
     if (n) hipLaunchKernelGGL(clock_negate_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, data, n);
-    // (the samples kept as the NEXT call's history are negated now: walkers of an overlap job must not warm up over them)
-    hist_xb = -1; hist_len = 0; hist_job = -1;
     XR_HIP(hipGetLastError());
     // (the input lies where it was; carry <= 1024 <= xpad: never in front of the buffer)
     return run_chains(data - carry, exact, n, soft_out, sym_out, cap, n_out, s, prof);
@@ -2231,10 +2133,10 @@ static_assert(16 + sizeof(ClockState) <= ClockStage::CARRY_HEAD, "the carried re
 
 int ClockStage::export_carry(void *d_rec, int which, hipStream_t s)
 {
-    if (in_flight) { set_error("clock recovery: a call is in flight"); return XRIT_E_INVALID; }
-    if (which != 0 && !redo_ok) { set_error("clock recovery: no finished call whose start state is still held"); return XRIT_E_INVALID; }
-    const int slot = which == 0 ? cur : cur ^ 1;
-    const size_t c = which == 0 ? carry : prev_carry;
+    if (jobs.in_flight) { set_error("clock recovery: a call is in flight"); return XRIT_E_INVALID; }
+    if (which != 0 && !jobs.redo_ok) { set_error("clock recovery: no finished call whose start state is still held"); return XRIT_E_INVALID; }
+    const int slot = which == 0 ? jobs.cur : jobs.cur ^ 1;
+    const size_t c = which == 0 ? jobs.carry : jobs.prev_carry;
     hipLaunchKernelGGL(clock_carry_pack_kernel, dim3(1), dim3(1024), 0, s, static_cast<unsigned char *>(d_rec), st.as<ClockState>() + slot,
                        tail.as<float2>() + 1024 * slot, (int)c);
     XR_HIP(hipGetLastError());
@@ -2243,51 +2145,45 @@ int ClockStage::export_carry(void *d_rec, int which, hipStream_t s)
 
 bool ClockStage::last_walk_exact() const
 {
-    if (!redo_ok || ov_cur >= 0 || job.short_input) return false;
+    if (!jobs.redo_ok || jobs.ov_cur >= 0 || job.short_input) return false;
     return serial || (job.relay && (relay_closed || job.G == 1));
 }
 
 int ClockStage::redo_from(const void *d_rec, size_t carry_rec, float *soft_out, float2 *sym_out, size_t cap, size_t *n_out, hipStream_t s, Profiler *prof)
 {
     *n_out = 0;
-    if (!redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
+    if (!jobs.redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
     if (carry_rec > 1024) { set_error("clock recovery: a carried record with %zu unread samples", carry_rec); return XRIT_E_INVALID; }
     // finish() moved on to the other state / tail slot: back to the one the call started from, which takes the record
-    cur ^= 1;
+    // (what lies in front of the input then is another handle's tail: no history for walkers)
+    jobs.step_back_from(carry_rec);
     float2 *data = xdata();     // where the call's input lies
-    const size_t n = prev_n;
-    hipLaunchKernelGGL(clock_carry_unpack_kernel, dim3(1), dim3(1024), 0, s, static_cast<const unsigned char *>(d_rec), st.as<ClockState>() + cur,
-                       tail.as<float2>() + 1024 * cur, (int)carry_rec);
+    hipLaunchKernelGGL(clock_carry_unpack_kernel, dim3(1), dim3(1024), 0, s, static_cast<const unsigned char *>(d_rec), st.as<ClockState>() + jobs.cur,
+                       tail.as<float2>() + 1024 * jobs.cur, (int)carry_rec);
     XR_HIP(hipGetLastError());
-    carry = carry_rec;
-    alt_valid = false;
-    hist_xb = -1; hist_len = 0; hist_job = -1;      // (what lies in front of the input now is another handle's tail: no history for walkers)
     // (the input lies where it was; carry <= 1024 <= xpad: never in front of the buffer)
-    return run_chains(data - carry, exact, n, soft_out, sym_out, cap, n_out, s, prof);
+    return run_chains(data - carry_rec, exact, jobs.prev_n, soft_out, sym_out, cap, n_out, s, prof);
 }
 
 int ClockStage::make_alt(hipStream_t s, Profiler *prof)
 {
-    alt_valid = false;
-    if (!redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
+    jobs.alt_valid = false;
+    if (!jobs.redo_ok) { set_error("clock recovery: no finished call to run again"); return XRIT_E_INVALID; }
     XR_TRY(alt.reserve(2 * CLK_ALT_SLOT));
     // this sign's outcome aside ...
     char *keep = alt.as<char>() + CLK_ALT_SLOT;
-    const size_t carry_keep = carry;
-    XR_HIP(hipMemcpyAsync(keep, st.as<ClockState>() + cur, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
-    XR_HIP(hipMemcpyAsync(keep + sizeof(ClockState), tail.as<float2>() + 1024 * cur, 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    const size_t carry_keep = jobs.carry;
+    XR_HIP(hipMemcpyAsync(keep, st.as<ClockState>() + jobs.cur, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
+    XR_HIP(hipMemcpyAsync(keep + sizeof(ClockState), tail.as<float2>() + 1024 * jobs.cur, 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
     // ... the call again on its negated input (symbols dropped) ...
     size_t k = 0;
     XR_TRY(redo_flipped(nullptr, nullptr, (size_t)1 << 40, &k, s, prof));
-    XR_HIP(hipMemcpyAsync(alt.p, st.as<ClockState>() + cur, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
-    XR_HIP(hipMemcpyAsync(alt.as<char>() + sizeof(ClockState), tail.as<float2>() + 1024 * cur, 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    alt_carry = carry;
+    XR_HIP(hipMemcpyAsync(alt.p, st.as<ClockState>() + jobs.cur, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
+    XR_HIP(hipMemcpyAsync(alt.as<char>() + sizeof(ClockState), tail.as<float2>() + 1024 * jobs.cur, 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
     // ... and this sign's state back
-    XR_HIP(hipMemcpyAsync(st.as<ClockState>() + cur, keep, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
-    XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * cur, keep + sizeof(ClockState), 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    carry = carry_keep;
-    alt_valid = true;
-    redo_ok = false;
+    XR_HIP(hipMemcpyAsync(st.as<ClockState>() + jobs.cur, keep, sizeof(ClockState), hipMemcpyDeviceToDevice, s));
+    XR_HIP(hipMemcpyAsync(tail.as<float2>() + 1024 * jobs.cur, keep + sizeof(ClockState), 1024 * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    jobs.alt_made(carry_keep);
     return XRIT_OK;
 }
 

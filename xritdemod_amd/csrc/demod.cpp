@@ -523,7 +523,7 @@ static int loops(xrit_demod *d, const SliceIO &io, float *d_soft, size_t cap, si
         XR_HIP(hipEventSynchronize(d->ev[EV_COSTAS]));
         bool redone = false;
         XR_TRY(costas_look(d, length, s, prof, &redone));
-        if (redone) d->clock.om_scanned = false;     // (the final pass ran again: the statistic is new, begin() unwraps it itself)
+        if (redone) d->clock.jobs.om_rewritten();     // (the final pass ran again: the statistic is new, begin() unwraps it itself)
         costas_done = true;
     }
     float2 *sym = nullptr;
@@ -570,8 +570,8 @@ static int pf_check_front(xrit_demod *d, const void *d_samples, size_t n, int ty
 struct ChainFacts {
     xrit_demod *d;
     bool costas_event_done() { return hipEventQuery(d->ev[EV_COSTAS]) == hipSuccess; }
-    unsigned long long ov_serial() { return d->clock.ov_serial; }
-    bool can_launch_ahead(int job) { return d->clock.ov_can_launch_ahead(job); }
+    unsigned long long ov_serial() { return d->clock.jobs.serials; }
+    bool can_launch_ahead(int job) { return d->clock.jobs.can_launch_ahead(job, d->clock.ov_pad_need); }
 };
 
 // one pass of chain_next's steps, each performed with HIP and its outcome written back.  Returns an error code;
@@ -603,7 +603,7 @@ static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
             break;
         }
         case CHAIN_WALK_RESTART:
-            rc = d->clock.ov_restart(f.ov_job, s);
+            rc = d->clock.ov_restart(f.ov_job);
             if (rc == XRIT_OK) chain_walk_restarted(f);
             break;
         case CHAIN_COSTAS_BEGIN: {
@@ -612,8 +612,8 @@ static int ov_service(xrit_demod *d, bool *progress, int limit = 1 << 30)
             rc = costas_enqueue(d, f.io, s, prof, &slot);
             if (rc != XRIT_OK) break;
             XR_HIP(hipEventRecord(d->ev[EV_COSTAS], s));
-            const int job = d->clock.ov_job;
-            chain_costas_begun(d->q, f, st.stream, slot, job, job >= 0 ? d->clock.ov[job].serial : 0);
+            const int job = d->clock.jobs.setting_up;
+            chain_costas_begun(d->q, f, st.stream, slot, job, d->clock.jobs.serial_of(job));
             break;
         }
         case CHAIN_WALK_LAUNCH:
@@ -706,7 +706,7 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
     {
         const size_t length = D > 1 ? n / D : n;
         const double min_omega = (double)d->sps * (1.0 - (double)d->cfg.clock_omega_limit);
-        const size_t worst = (size_t)(((double)length + (double)d->clock.carry) / min_omega) + 2;
+        const size_t worst = (size_t)(((double)length + (double)d->clock.jobs.carry) / min_omega) + 2;
         if (worst > cap && length > 0) {
             set_error("output capacity %zu is below the %zu symbols this call may produce (n / (decimation * sps * (1 - omega limit)) + 2)", cap, worst);
             *n_out = worst;        // the capacity that suffices; nothing has been consumed, the handle is unchanged: a front
@@ -743,7 +743,7 @@ int xrit_demod_process_device(xrit_demod *d, const void *d_samples, size_t n, in
             if (hipEventSynchronize(d->ev[EV_COSTAS]) != hipSuccess) { set_error("hipEventSynchronize failed"); rc = XRIT_E_HIP; }
             bool redone = false;
             if (rc == XRIT_OK) rc = costas_look(d, io.length, d->own[f.costas_stream], prof, &redone);
-            if (redone) d->clock.om_scanned = false;
+            if (redone) d->clock.jobs.om_rewritten();
             if (rc == XRIT_OK) rc = loops(d, io, d_soft, cap, &total_sym, s, prof, call_id, true, static_cast<float2 *>(f.slot));
             costas_ahead = true;
         } else {

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "framer_host.h"
 #include "lock_host.h"
+#include "clock_jobs.h"
 #include "clock_plan.h"
 #include "loop_core.h"
 #include "taps.h"
@@ -221,10 +222,6 @@ struct ClockStage : ClockKnobs {
     bool no_meanj = false;      // XRIT_NO_MEANJ=1: finite-difference Jacobians in every call
     std::function<int(int)> before_relay;   // called by begin() in front of the relay kernels of a call that plans them (the chain
                                          // starts the front end of the next burst there: xrit_demod_prefetch_device)
-#ifndef XRIT_AHEAD
-#define XRIT_AHEAD 2            // inputs that may wait behind the call in progress (bursts that walk overlapping blocks)
-#endif
-    static constexpr int NXB = XRIT_AHEAD + 1;
     // What the loop carries from one call to the next as ONE device record (one capture across GPUs, csrc/group.hip: the rank
     // in front hands it on, so that the stream has one loop state across all slices as the reference has across all chunks,
     // demodulator.cpp:446-450): [valid, carry, -, -], the ClockState, then the unread tail (1024 samples, zero padded).
@@ -244,30 +241,10 @@ struct ClockStage : ClockKnobs {
     bool jmean_valid = false;         // jmean holds the mean chain Jacobian of an earlier, locked call with ...
     int jmean_ns = 0;                 // ... this chain length
 
-    // ---- the stream between calls
-    int cur = 0;
-    size_t carry = 0;       // samples held over from the previous call
-    int xb = 0;             // the buffer the call in flight (the last call) reads
-    int x_pending = -1;     // the buffer input_slot() handed out for the next call
-    // (the statistic's phasor counts samples from the first NEW sample of the call: begin() turns it by the carried ones)
-    bool om_ext = false;
-    int om_nb = 0, om_BL = 256;
-    // (round 4: ... and the producer's stream also unwraps it into the symbol-count curve, om_scan(): two launches less between
-    // the end of one burst's relay and the start of the next one's)
-    bool om_scanned = false;
-    // what the last finished call left in its buffer: the history the next call's first walkers warm up over
-    int hist_xb = -1;           // buffer
-    size_t hist_len = 0;        // samples in it that end where the stream stands ([pad | new] of that call, contiguous)
-    int hist_job = -1;          // ... and, when that call was an overlap job, the job whose timing curve covers them
-    // What the recovery would carry had it run on the sign-flipped stream so far (make_alt(): the last call -- the
-    // halo of a time slice, from a cold start -- is run again on its negated input and the outcome kept aside); a
-    // later redo_flipped() starts from it instead of from the other sign's state with its history negated, whose
-    // timing sits 1e-3 sample off the flipped loop's and takes 1e4..1e5 symbols to come home on the lattice.
-    size_t alt_carry = 0;
-    bool alt_valid = false;
+    // ---- the stream between calls, the sample buffers and the overlap jobs: clock_jobs.h
+    ClockJobs jobs;
 
     // ---- the call in flight
-    bool in_flight = false; // between begin() and finish()
     struct Job : ClockChainPlan {
         size_t n = 0, cap = 0; float *soft = nullptr; float2 *sym = nullptr;
         float2 *base = nullptr;     // where [carry | new] lie when that is not the call's own buffer (a call run again, a fall-back)
@@ -283,24 +260,13 @@ struct ClockStage : ClockKnobs {
     // ---- overlapping exactly walked blocks (clock_overlap.h, round 5): the default configuration's plan for calls of ov_min
     // symbols or more.  A job is one such call; up to three exist at a time (xrit_demod_prefetch_device: the walkers of bursts
     // b and b + 1 at work, burst b + 2's samples being written), each with its own sample buffer (xbuf[job]) and timing curve.
-    struct OvJob : ClockOvPlan {
-        int state = 0;                  // 0: free; 1: slot handed out (samples being produced); 2: walkers enqueued; 3: being finalized
-        size_t n = 0;                   // new samples
-        bool ahead = false;             // enqueued before the call in front of it had finished (its carry is not known to the plan)
-        int nb = 0, BL = 256;           // the timing statistic: nb blocks of BL samples, counted from the first new sample
-        bool om_ext = false, om_scanned = false;
+    // (the plain part of job q: jobs.job[q])
+    struct OvJob {
         DevBuf om, om_work, segs, S, stage, aux;
         hipEvent_t ev_walk = nullptr;   // the walkers have finished
         hipEvent_t ev_guess = nullptr;  // the history has been copied in and the start states computed
-        int hist_src = -1;              // the buffer whose last samples this job's first walkers warm up over (-1: none)
-        unsigned long long serial = 0;  // order of the calls (the job in front: serial - 1)
     } ov[NXB];
-    int ov_job = -1;            // the job of the call being set up / in flight (-1: the call is not such a call)
-    unsigned long long ov_serial = 0;
-    int ov_cur = -1;            // the overlap job of the call between begin() and finish()
     float *ov_soft = nullptr; size_t ov_cap = 0;
-    size_t prev_carry = 0, prev_n = 0;      // of the last call
-    bool redo_ok = false;                   // ... which ended normally (its input is still in xbuf)
 
     // ---- results of the last call
     int passes = 0;
@@ -332,8 +298,8 @@ struct ClockStage : ClockKnobs {
     DevBuf stage;               // soft symbols of a writing hand-off pass, in wave order (ClockPassOut::stage)
     DevBuf alt;                             // ClockState + 1024 samples of unread tail, twice (the second: scratch)
     DevBuf ov_claim;            // which SIMDs hold a walker (clock_relay.h), shared by the jobs in flight
-    float2 *xdata() const { return xbuf[xb].as<float2>() + xpad; }
-    float2 *xbase() const { return job.base ? job.base : xdata() - carry; }
+    float2 *xdata() const { return xbuf[jobs.xb].as<float2>() + xpad; }
+    float2 *xbase() const { return job.base ? job.base : xdata() - jobs.carry; }
 
     int init(float omega, float gain_omega, float mu, float gain_mu, float omega_rel_limit, int chain_syms,
              int max_passes);
@@ -367,10 +333,9 @@ struct ClockStage : ClockKnobs {
     // has been scanned): pad copy, start states, walkers, on `sw` -- ahead of the call itself (ahead: the call in front has not
     // finished) or from begin()
     int ov_launch(int job, hipStream_t sw, bool ahead, Profiler *prof);
-    bool ov_can_launch_ahead(int job) const;
     // a job whose walkers were started ahead on samples that have since been rewritten (the Costas loop went on from the host):
-    // waits for them (on `s`'s behalf: the host synchronises the event) and takes the job back to "samples produced"
-    int ov_restart(int job, hipStream_t s);
+    // waits for them (the host synchronises the event) and takes the job back to "samples produced"
+    int ov_restart(int job);
 
     // ---- the parts of begin() / finish() (clock.hip)
     // the chains on samples at `base` (null: the call's own buffer), with `exact_` for cfg.clock_exact
@@ -393,7 +358,7 @@ struct ClockStage : ClockKnobs {
     int relay_cut();
     int ov_finalize(int job, float *soft_out, size_t cap, hipStream_t s, Profiler *prof);
     int ov_fallback(size_t *n_out, hipStream_t s, Profiler *prof, bool to_closure);
-    int trace_overlap(const OvJob &oj, const struct ClockResult &r) const;
+    int trace_overlap(int job, const struct ClockResult &r) const;
     int trace_relay() const;
     int trace_passes() const;
 };
