@@ -1091,6 +1091,94 @@ int xrit_canvas_stats(xrit_canvas *cv, xrit_canvas_counters *out);
 int xrit_canvas_release(xrit_canvas *cv, unsigned slot);
 
 /* ------------------------------------------------------------------------
+ * Carrier acquisition: a stage IN FRONT of the chain that finds a large carrier
+ * offset and takes it out on the device (DESIGN.md section 21;
+ * tests/acquire_spec.py is the specification).  The reference has no such
+ * stage: its only tuning is the `frequency` key of the config file
+ * (demodulator.cpp:285-290, :461), retuned by hand while watching the
+ * constellation, and its Costas loop locks within about 0.7 kHz at 1.25 Msps.
+ * Samples are converted as onSamplesAvailable does (demodulator.cpp:54-74):
+ * XRIT_SAMPLE_FLOATIQ as is, S16IQ times 2^-15, S8IQ times 2^-7;
+ * XRIT_SAMPLE_U8IQ is refused with XRIT_E_INVALID (its DC tracker belongs to the
+ * chain's ingest).  The output is cf32 and goes to the chain as
+ * XRIT_SAMPLE_FLOATIQ.
+ *  - state, in device memory: acc (uint64, the oscillator's phase in units of
+ *    2^-64 turn) and inc (int64, the phase step per input sample); both 0 after
+ *    create and reset.
+ *  - mix: sample i of a call, with a = acc + i * inc (mod 2^64):
+ *      h = (int32)(a >> 32); theta = (float)h * (float)(pi * 2^-31);
+ *      (s, c) = sincosf(theta)   -- the C library's, bit for bit;
+ *      yr = xr * c + xi * s; yi = xi * c - xr * s   -- float32, no FMA;
+ *    afterwards acc += n * inc.  The phase is an integer, so the output does not
+ *    depend on how a stream is cut into calls, and a change of inc is a
+ *    frequency step without a phase jump.
+ *  - estimate: u[m] = the sum of pre_sum consecutive samples, z = u * u (BPSK
+ *    squared: a spectral line at twice the carrier); M segments of N = 4096 points
+ *    of z, half overlapped, Hann window, FFT; P[k] = the sum of the segments'
+ *    |X_s[k]|^2, k0 its first maximum; the phase of sum_s X_s[k0] conj(X_{s-1}[k0])
+ *    times (-1)^k0 places the line inside the bin.  M = min(segments,
+ *    floor(floor(n / pre_sum) / 2048) - 1).  float32 through |X|^2, float64 behind
+ *    it; no atomics: the same bits from run to run.
+ *    UNAMBIGUOUS ONLY FOR |f| < sample_rate / (4 * pre_sum).
+ *    A strong DC component squares to a line at 0 Hz and would be taken for the
+ *    carrier; behaviour under adjacent-channel interference is not known
+ *    ("Unverified").
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_acquire xrit_acquire;
+#define XRIT_ACQUIRE_OK        0
+#define XRIT_ACQUIRE_TOO_SHORT 1     /* fewer than 31 segments: n < 65536 * pre_sum */
+#define XRIT_ACQUIRE_WEAK      2     /* ratio < min_ratio: no line stands out */
+typedef struct xrit_acquire_params {
+    double   sample_rate;            /* Hz, > 0 */
+    uint32_t pre_sum;                /* R: 1 .. 64; 0 selects 1 */
+    uint32_t segments;               /* the most segments an estimate takes: 31 .. 4095; 0 selects 511 */
+    double   min_ratio;              /* P[k0] / mean(P) below which the result is WEAK; 0 selects the default (8.9) */
+} xrit_acquire_params;               /* 24 bytes */
+typedef struct xrit_acquire_estimate_record {
+    uint32_t status;                 /* XRIT_ACQUIRE_* */
+    uint32_t k0;                     /* the line's bin in the squared signal's spectrum (0 when TOO_SHORT) */
+    uint32_t segments;               /* M */
+    uint32_t reserved0;
+    double   ratio;                  /* P[k0] / mean(P) */
+    double   nu;                     /* cycles per input sample, in [-1/(4R), 1/(4R)) */
+    double   hz;                     /* nu * sample_rate */
+    int64_t  inc;                    /* rint(ldexp(nu, 64)) */
+    uint32_t applied;                /* 1: this call made it the state's inc */
+    uint32_t reserved[3];
+} xrit_acquire_estimate_record;      /* 64 bytes */
+typedef struct xrit_acquire_state {
+    uint64_t acc;
+    int64_t  inc;
+    uint64_t samples_mixed, estimates, applied;      /* since create or reset */
+} xrit_acquire_state;                /* 40 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_acquire_create(xrit_acquire **aq, const xrit_acquire_params *params, int device);
+int xrit_acquire_destroy(xrit_acquire *aq);
+/* acc, inc and the counters zero; waits for the handle's last call */
+int xrit_acquire_reset(xrit_acquire *aq);
+/* inc = llrint(ldexp(hz / sample_rate, 64)), |hz| < sample_rate / 2; acc is untouched.  Queued on the stream of the
+ * handle's last call; no host synchronisation. */
+int xrit_acquire_set_frequency(xrit_acquire *aq, double hz);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation.  The estimate is of the n raw
+ * samples at d_samples (aligned to one complex sample), never of mixed output.  d_record (8-byte aligned) is always
+ * written.  apply != 0 and status OK: the state's inc becomes the record's.  Calls on one handle share its state and
+ * scratch: keep them in order. */
+int xrit_acquire_estimate_device(xrit_acquire *aq, const void *d_samples, size_t n_complex, int sample_type, int apply,
+                                 xrit_acquire_estimate_record *d_record, void *stream);
+/* d_out: n_complex cf32 (8-byte aligned); for XRIT_SAMPLE_FLOATIQ it may be d_samples itself.  16-byte loads and stores
+ * when both pointers are 16-byte aligned.  n_complex = 0 is a call like any other.  May be queued directly behind
+ * xrit_acquire_estimate_device and in front of xrit_demod_process_device on one stream. */
+int xrit_acquire_mix_device(xrit_acquire *aq, const void *d_samples, size_t n_complex, int sample_type, float *d_out,
+                            void *stream);
+/* host buffers: one upload, one download each */
+int xrit_acquire_estimate(xrit_acquire *aq, const void *samples, size_t n_complex, int sample_type, int apply,
+                          xrit_acquire_estimate_record *record);
+int xrit_acquire_mix(xrit_acquire *aq, const void *samples, size_t n_complex, int sample_type, float *out);
+/* the state after the handle's last call (waits for it) */
+int xrit_acquire_get_state(xrit_acquire *aq, xrit_acquire_state *out);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

@@ -24,4 +24,5 @@ from ._capi import (  # noqa: F401
     ImageDecoder, IMAGE_LINE_DTYPE, IMAGE_FILE_DTYPE, IMAGES_SUMMARY_DTYPE, IMAGES_STATS_DTYPE, IMAGE_KEY_DTYPE, images_max_bytes,
     ImageCanvas, CANVAS_FILE_DTYPE, CANVAS_SLOT_DTYPE, CANVAS_SEGMENT_DTYPE, CANVAS_KEY_DTYPE, CANVAS_SUMMARY_DTYPE, CANVAS_STATS_DTYPE,
     CANVAS_REASONS,
+    CarrierAcquirer, ACQUIRE_PARAMS_DTYPE, ACQUIRE_RECORD_DTYPE, ACQUIRE_STATE_DTYPE, ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK,
 )

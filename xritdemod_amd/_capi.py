@@ -155,6 +155,15 @@ _SIGNATURES = {
     "xrit_canvas_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
     "xrit_canvas_stats": (C.c_int, [_vp, _vp]),
     "xrit_canvas_release": (C.c_int, [_vp, C.c_uint]),
+    "xrit_acquire_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int]),
+    "xrit_acquire_destroy": (C.c_int, [_vp]),
+    "xrit_acquire_reset": (C.c_int, [_vp]),
+    "xrit_acquire_set_frequency": (C.c_int, [_vp, C.c_double]),
+    "xrit_acquire_estimate_device": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp]),
+    "xrit_acquire_mix_device": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp]),
+    "xrit_acquire_estimate": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_int, _vp]),
+    "xrit_acquire_mix": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp]),
+    "xrit_acquire_get_state": (C.c_int, [_vp, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -1597,3 +1606,81 @@ class ImageCanvas(_Handle):
     def reset(self):
         """Every slot free, every key without placement, counters and pixels zero."""
         _check(lib().xrit_canvas_reset(self._h))
+
+
+# ---- carrier acquisition (DESIGN.md section 21) -------------------------------------------------------------------------
+ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK = 0, 1, 2
+# xrit_acquire_params
+ACQUIRE_PARAMS_DTYPE = np.dtype([("sample_rate", np.float64), ("pre_sum", np.uint32), ("segments", np.uint32), ("min_ratio", np.float64)])
+assert ACQUIRE_PARAMS_DTYPE.itemsize == 24
+# xrit_acquire_estimate_record: what an estimate writes
+ACQUIRE_RECORD_DTYPE = np.dtype([
+    ("status", np.uint32), ("k0", np.uint32), ("segments", np.uint32), ("reserved0", np.uint32), ("ratio", np.float64), ("nu", np.float64),
+    ("hz", np.float64), ("inc", np.int64), ("applied", np.uint32), ("reserved", np.uint32, (3,))])
+assert ACQUIRE_RECORD_DTYPE.itemsize == 64
+# xrit_acquire_state: what the handle carries
+ACQUIRE_STATE_DTYPE = np.dtype([("acc", np.uint64), ("inc", np.int64), ("samples_mixed", np.uint64), ("estimates", np.uint64),
+                                ("applied", np.uint64)])
+assert ACQUIRE_STATE_DTYPE.itemsize == 40
+_SAMPLE_DTYPES = {SAMPLE_FLOATIQ: (np.complex64, 1), SAMPLE_S16IQ: (np.int16, 2), SAMPLE_S8IQ: (np.int8, 2)}
+
+
+class CarrierAcquirer(_Handle):
+    """A stage in front of the chain: `estimate` finds the carrier offset of a block of raw samples from the spectral
+    line of the squared signal (unambiguous for |f| < sample_rate / (4 * pre_sum)), `mix` takes the state's frequency
+    out with an oscillator whose 64-bit phase lives in device memory, so a stream may be cut into calls anywhere.  The
+    output is cf32 for the chain's SAMPLE_FLOATIQ.  0 for pre_sum, segments or min_ratio selects the default."""
+    _destroy = "xrit_acquire_destroy"
+
+    def __init__(self, sample_rate, pre_sum=0, segments=0, min_ratio=0.0, device=0):
+        super().__init__()
+        par = np.zeros(1, ACQUIRE_PARAMS_DTYPE)
+        par[0] = (sample_rate, pre_sum, segments, min_ratio)
+        _check(lib().xrit_acquire_create(C.byref(self._h), _p(par), device))
+
+    @staticmethod
+    def _samples(samples, sample_type):
+        if sample_type not in _SAMPLE_DTYPES:
+            raise XritError(-1, "acquire: FLOATIQ, S16IQ and S8IQ are taken")
+        dtype, per = _SAMPLE_DTYPES[sample_type]
+        a = np.ascontiguousarray(samples, dtype).reshape(-1)
+        return a, len(a) // per
+
+    def estimate(self, samples, sample_type=SAMPLE_FLOATIQ, apply=False):
+        """-> an ACQUIRE_RECORD_DTYPE scalar record.  apply: a result with status OK becomes the state's frequency."""
+        a, n = self._samples(samples, sample_type)
+        rec = np.zeros(1, ACQUIRE_RECORD_DTYPE)
+        _check(lib().xrit_acquire_estimate(self._h, _p(a), n, sample_type, int(bool(apply)), _p(rec)))
+        return rec[0]
+
+    def mix(self, samples, sample_type=SAMPLE_FLOATIQ):
+        """-> the samples derotated by the state's oscillator, complex64; the phase carries on into the next call."""
+        a, n = self._samples(samples, sample_type)
+        out = np.zeros(n, np.complex64)
+        _check(lib().xrit_acquire_mix(self._h, _p(a), n, sample_type, _p(out)))
+        return out
+
+    def estimate_device(self, d_samples_ptr, n_complex, sample_type, apply, d_record_ptr, stream=None):
+        """Device pointers; the 64-byte record is always written.  Asynchronous on stream."""
+        _check(lib().xrit_acquire_estimate_device(self._h, C.c_void_p(d_samples_ptr), n_complex, sample_type, int(bool(apply)),
+                                                  C.c_void_p(d_record_ptr), C.c_void_p(stream) if stream else None))
+
+    def mix_device(self, d_samples_ptr, n_complex, sample_type, d_out_ptr, stream=None):
+        """Device pointers; d_out takes n_complex cf32 and may be d_samples for SAMPLE_FLOATIQ.  Asynchronous on stream:
+        it may be queued behind estimate_device and in front of Demodulator.process_device."""
+        _check(lib().xrit_acquire_mix_device(self._h, C.c_void_p(d_samples_ptr), n_complex, sample_type, C.c_void_p(d_out_ptr),
+                                             C.c_void_p(stream) if stream else None))
+
+    def set_frequency(self, hz):
+        """The oscillator's frequency from now on (|hz| < sample_rate / 2); its phase goes on from where it is."""
+        _check(lib().xrit_acquire_set_frequency(self._h, float(hz)))
+
+    def state(self):
+        """acc, inc and the counters after the last call (an ACQUIRE_STATE_DTYPE scalar record); waits for that call."""
+        out = np.zeros(1, ACQUIRE_STATE_DTYPE)
+        _check(lib().xrit_acquire_get_state(self._h, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """Phase, frequency and counters zero."""
+        _check(lib().xrit_acquire_reset(self._h))

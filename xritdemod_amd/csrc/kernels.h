@@ -544,6 +544,19 @@ int launch_canvas(const unsigned char *bytes, const xrit_file_piece *pieces, con
                   const xrit_images_summary *isum, const CanvasBounds &b, const CanvasState &st, CanvasScratch &sc,
                   xrit_canvas_file *canvas_files, xrit_canvas_slot *out_slots, xrit_canvas_summary *summary, hipStream_t s);
 int launch_canvas_release(const CanvasState &st, unsigned slot, hipStream_t s);
+// carrier acquisition (acquire.hip; acquire_host.h has the sizes): the handle's state is one xrit_acquire_state; the scratch
+// of an estimate of M segments
+struct AcquireScratch {
+    float2 *spectra;                // [M][4096] every segment's spectrum, in bin order
+    double *power;                  // [4096] their powers summed
+};
+size_t acquire_scratch_carve(void *p, unsigned segments, AcquireScratch &sc);
+// the mix of n samples with the state's acc and inc, then acc += n * inc (n = 0: that alone)
+int launch_acquire_mix(const void *in, int type, size_t n, float2 *out, xrit_acquire_state *st, hipStream_t s);
+int launch_acquire_set_inc(xrit_acquire_state *st, long long inc, hipStream_t s);
+// segments = acquire_segments(n, ...): below 31 only the record (TOO_SHORT) is written; tw, win: the tables of acquire.cpp
+int launch_acquire_estimate(const void *in, int type, unsigned segments, const xrit_acquire_params &par, const float2 *tw, const float *win,
+                            const AcquireScratch &sc, int apply, xrit_acquire_state *st, xrit_acquire_estimate_record *rec, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

@@ -30,6 +30,9 @@
 //     demodulator.cpp:161-163   the complex symbols (I, Q interleaved) are queued; whenever 1024 are queued and
 //                               10 ms have passed they go out as int8 (x128, clamp, truncation) in one UDP
 //                               datagram from port 9001 to HOST:9000
+//   * demodulator.cpp:285-290,  --tune HZ / --acquire: the reference tunes its source with the `frequency` key of the config file and is
+//     :461                      retuned by hand; a recorded capture is derotated on the device instead (xrit_acquire_*), by a given
+//                               offset or by the one estimated on the capture's first samples
 // Only the C ABI of include/xritdemod_amd.h is used (no HIP headers): this file builds
 // with plain g++.
 #include <arpa/inet.h>
@@ -92,6 +95,10 @@ struct Options {
     size_t canvas_mib = 32;        // --canvas-mib M: MiB per canvas (32: a 5424 x 5424 8-bit image, 29 419 776 bytes, fits)
     bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
     int flywheel = 0;              // --flywheel [N]: the frame lock (xrit_lock_*) in place of framer and decoder, flywheelRecheck = N
+    bool tune = false;             // --tune HZ: the input derotated by tune_hz in front of the chain (xrit_acquire_*)
+    double tune_hz = 0.0;
+    bool acquire = false;          // --acquire: that offset estimated on the first input of at least 65536 * R samples
+    unsigned acquire_presum = 1;   // --acquire-presum R: samples summed in front of the estimator (|offset| < sample rate / 4R)
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -131,6 +138,11 @@ void usage()
                  "                                 16-bit big-endian above 8 bits; without annotation vc{vcid}_img{image_id}_{call}.pgm); what is\n"
                  "                                 incomplete at exit becomes ....partial.pgm.  N canvases (1..64, default 8) of M MiB (default 32:\n"
                  "                                 a 5424 x 5424 8-bit image fits) are held at a time)\n"
+                 "         [--tune HZ]   (a carrier offset of HZ is taken out on the GPU in front of the chain; cf32, s16 or s8 input, one GPU)\n"
+                 "         [--acquire [--acquire-presum R]]   (the carrier offset is estimated on the first input of at least 65536 * R samples --\n"
+                 "                                 further blocks are read ahead if a block is shorter --, printed to stderr with the strength of\n"
+                 "                                 its spectral line and held for the run; unambiguous below sample rate / (4 R), R 1..64,\n"
+                 "                                 default 1; when no line stands out the run goes on untuned.  With --tune the estimate replaces HZ)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -171,6 +183,9 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--canvas-slots") { if (!(v = need("--canvas-slots"))) return false; o.canvas_slots = (unsigned)std::atoi(v); }
         else if (a == "--canvas-mib") { if (!(v = need("--canvas-mib"))) return false; o.canvas_mib = (size_t)std::atoll(v); }
         else if (a == "--stream-sync") o.stream_sync = true;
+        else if (a == "--tune") { if (!(v = need("--tune"))) return false; o.tune = true; o.tune_hz = std::atof(v); }
+        else if (a == "--acquire") o.acquire = true;
+        else if (a == "--acquire-presum") { if (!(v = need("--acquire-presum"))) return false; o.acquire_presum = (unsigned)std::atoi(v); }
         else if (a == "--flywheel") {
             o.flywheel = 4;                 // parameters.h:41
             o.stream_sync = true;
@@ -222,6 +237,10 @@ bool parse(int argc, char **argv, Options &o)
     if (o.canvas && (!o.files_decompress || o.canvas_slots < 1 || o.canvas_slots > XRIT_CANVAS_MAX_SLOTS || o.canvas_mib < 1 ||
                      o.canvas_mib > 4096)) {
         std::fprintf(stderr, "--canvas needs --files DIR --files-decompress; --canvas-slots 1..%d, --canvas-mib 1..4096\n", XRIT_CANVAS_MAX_SLOTS);
+        return false;
+    }
+    if ((o.tune || o.acquire) && (o.gpus > 1 || o.format == "u8" || o.acquire_presum < 1 || o.acquire_presum > 64)) {
+        std::fprintf(stderr, "--tune / --acquire: one GPU; cf32, s16 or s8 input; --acquire-presum 1..64\n");
         return false;
     }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
@@ -1013,6 +1032,47 @@ int main(int argc, char **argv)
 
     FILE *in = std::fopen(o.input.c_str(), "rb");
     if (!in) { std::perror("input"); xrit_demod_destroy(chain); return 1; }
+    // --tune / --acquire: the stage in front of the chain; what the estimate read ahead is handed out again before the file goes on
+    xrit_acquire *acq = nullptr;
+    std::vector<unsigned char> ahead;
+    size_t ahead_pos = 0;
+    auto read_samples = [&](void *dst, size_t count) -> size_t {
+        if (ahead_pos >= ahead.size()) return std::fread(dst, bytes_per_sample, count, in);
+        size_t got = (ahead.size() - ahead_pos) / bytes_per_sample;
+        got = got < count ? got : count;
+        std::memcpy(dst, ahead.data() + ahead_pos, got * bytes_per_sample);
+        ahead_pos += got * bytes_per_sample;
+        if (got < count) got += std::fread(static_cast<unsigned char *>(dst) + got * bytes_per_sample, bytes_per_sample, count - got, in);
+        return got;
+    };
+    if (o.tune || o.acquire) {
+        xrit_acquire_params ap{};
+        ap.sample_rate = o.sample_rate;
+        ap.pre_sum = o.acquire_presum;
+        bool ok = xrit_acquire_create(&acq, &ap, o.device) == XRIT_OK && (!o.tune || xrit_acquire_set_frequency(acq, o.tune_hz) == XRIT_OK);
+        if (ok && o.acquire) {
+            const size_t first = o.fifo ? o.fifo_block : o.block, least = (size_t)65536 * o.acquire_presum;
+            size_t want = first;
+            while (want < least) want += first;         // whole blocks, as many as hold 65536 * R samples
+            ahead.resize(want * bytes_per_sample);
+            ahead.resize(std::fread(ahead.data(), bytes_per_sample, want, in) * bytes_per_sample);
+            xrit_acquire_estimate_record rec{};
+            ok = xrit_acquire_estimate(acq, ahead.data(), ahead.size() / bytes_per_sample, type, 1, &rec) == XRIT_OK;
+            if (ok && rec.status == XRIT_ACQUIRE_OK)
+                std::fprintf(stderr, "acquire: carrier offset %.1f Hz, line ratio %.1f over %u segments\n", rec.hz, rec.ratio, rec.segments);
+            else if (ok && rec.status == XRIT_ACQUIRE_WEAK)
+                std::fprintf(stderr, "acquire: weak: no carrier line stands out (best %.1f Hz, line ratio %.1f over %u segments); not tuned\n",
+                             rec.hz, rec.ratio, rec.segments);
+            else if (ok)
+                std::fprintf(stderr, "acquire: too short: %zu samples, %zu are needed; not tuned\n", ahead.size() / bytes_per_sample, least);
+        }
+        if (!ok) {
+            std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+            if (acq) xrit_acquire_destroy(acq);
+            std::fclose(in); xrit_demod_destroy(chain);
+            return 1;
+        }
+    }
     FrameDecode decode;
     decode.canvas_slots = o.canvas ? o.canvas_slots : 0;
     decode.canvas_bytes = o.canvas_mib << 20;
@@ -1097,7 +1157,7 @@ int main(int argc, char **argv)
         // the source runs until the DSP loop looks again AND finds at least 64 Ki floats (:108-116)
         for (;;) {
             for (int b = 0; b < o.fifo_lag && !fifo_eof; ++b) {
-                const size_t got = std::fread(blockbuf.data(), bytes_per_sample, o.fifo_block, in);
+                const size_t got = read_samples(blockbuf.data(), o.fifo_block);
                 if (got == 0) { fifo_eof = true; break; }
                 if (o.paced) {        // CFileFrontend.cpp:36-47: one callback per block period
                     std::this_thread::sleep_until(t_release);
@@ -1126,10 +1186,11 @@ int main(int argc, char **argv)
     };
     std::vector<float> soft(cap);
     std::vector<int8_t> q(cap);
+    std::vector<float> mixed(acq ? 2 * max_chunk : 0);
     size_t total_in = 0, total_sym = 0;
     int exit_code = 0;
     for (;;) {
-        size_t n = o.fifo ? fifo_chunk() : std::fread(raw.data(), bytes_per_sample, o.block, in);
+        size_t n = o.fifo ? fifo_chunk() : read_samples(raw.data(), o.block);
         if (n == 0) { std::fprintf(stderr, "EOF\n"); break; }
         if (o.paced && !o.fifo) {
             // CFileFrontend.cpp:36-47: one block per block period
@@ -1138,7 +1199,13 @@ int main(int argc, char **argv)
                 std::chrono::duration<double>((double)n / o.sample_rate));
         }
         size_t nsym = 0;
-        rc = xrit_demod_process(chain, raw.data(), n, type, soft.data(), cap, &nsym);
+        if (acq) {
+            rc = xrit_acquire_mix(acq, raw.data(), n, type, mixed.data());
+            if (rc != XRIT_OK) { std::fprintf(stderr, "mix: %s\n", xrit_last_error()); exit_code = 1; break; }
+            rc = xrit_demod_process(chain, mixed.data(), n, XRIT_SAMPLE_FLOATIQ, soft.data(), cap, &nsym);
+        } else {
+            rc = xrit_demod_process(chain, raw.data(), n, type, soft.data(), cap, &nsym);
+        }
         if (rc != XRIT_OK) { std::fprintf(stderr, "process: %s\n", xrit_last_error()); exit_code = 1; break; }
         if (o.drop) {
             queue.add(soft.data(), nsym);         // SymbolManager::add: never waits, may drop
@@ -1185,6 +1252,7 @@ int main(int argc, char **argv)
     sink.close_all();
     decode.close();
     std::fclose(in);
+    if (acq) xrit_acquire_destroy(acq);
     xrit_demod_destroy(chain);
     return exit_code;
 }
