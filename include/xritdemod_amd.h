@@ -1179,6 +1179,96 @@ int xrit_acquire_mix(xrit_acquire *aq, const void *samples, size_t n_complex, in
 int xrit_acquire_get_state(xrit_acquire *aq, xrit_acquire_state *out);
 
 /* ------------------------------------------------------------------------
+ * Link monitor: a stage BEHIND the chain that says how good the link was, and
+ * when: per block of symbols the level, two Es/N0 estimates, how often the int8
+ * sink saturates and how often the sign changes (DESIGN.md section 22;
+ * tests/monitor_spec.py is the specification).  The reference shows a
+ * constellation (DiagManager) and a "signal quality" figure in its decoder; a
+ * recorded capture runs through this library far faster than anyone can watch,
+ * so what is kept is a time series.
+ *  - lattice: every symbol becomes an integer q.  XRIT_SYMBOL_F32:
+ *      q = clamp(rintf(x * 512.0f), -4095, 4095)   -- the product is exact, rintf
+ *    rounds to nearest even; NaN gives q = 0 and counts in `bad`; `clamped`
+ *    counts |rintf(512 x)| > 4095, +-inf included.  XRIT_SYMBOL_I8: q = 4 * s
+ *    (4 * 127 = 508: both types share the level scale to 1 %).
+ *  - a block record holds sums over its n symbols: s1 = sum |q|, s2 = sum q^2,
+ *    s4 = sum q^4, sum = sum q; sat = the symbols the int8 sink saturates
+ *    (F32: |q| > 512, that is |x| > 1; I8: s = 127 or s = -128); neg = q < 0;
+ *    flips = the symbols whose (q < 0) differs from that of the symbol before
+ *    them in the stream -- across blocks and calls; the first symbol after
+ *    create or reset counts none.  All integers: the sums do not depend on their
+ *    order, and rows, summary and state are the specification's word for word
+ *    however a stream is cut into calls.
+ *  - block: a multiple of 64 in 64 .. 32768 (0 selects 16384, one coded frame);
+ *    4095^4 * 32768 < 2^63, so s4 fits with a bit to spare.
+ *  - state, in device memory, all zero after create and reset: the open block's
+ *    partial record, the last symbol's sign and whether there is one, the totals,
+ *    and a cumulative histogram hist[(q + 4096) >> 5] of every symbol pushed.
+ * NO LOCK FLAG.  A carrier that is not locked reads 1.5 .. 2.5 dB from real
+ * soft symbols (a spinning 8 dB carrier: 1.2 .. 2.5 dB), and a working LRIT link
+ * can sit there too: the reading alone cannot tell the two apart.  Lock is the
+ * frame lock's business (xrit_lock_*); what the monitor shows is the reading
+ * against what the user expected.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_monitor xrit_monitor;
+#define XRIT_SYMBOL_F32 0      /* the chain's soft symbols */
+#define XRIT_SYMBOL_I8  1      /* xrit_quantize_i8's output, the TCP sink's bytes */
+#define XRIT_MONITOR_NO_SIGNAL 1     /* 3 s2^2 - n s4 <= 0 (or s1 = 0): no signal power to be found; the dB value is -99 */
+#define XRIT_MONITOR_NO_NOISE  2     /* a noise term <= 0 (every |q| the same): the dB value is +99 */
+typedef struct xrit_monitor_block {
+    uint64_t first;                  /* index in the stream of the block's first symbol */
+    uint32_t n;                      /* symbols in it: the block size (less only in the state's open block) */
+    uint32_t flips;
+    uint64_t s1, s2, s4;             /* sums of |q|, q^2, q^4 */
+    int64_t  sum;                    /* sum of q */
+    uint32_t sat, clamped, bad, neg;
+} xrit_monitor_block;                /* 64 bytes */
+typedef struct xrit_monitor_summary {
+    uint64_t rows;                   /* blocks this call completed and wrote */
+    uint64_t open_n;                 /* symbols in the open block behind it */
+    uint64_t symbols_total, blocks_total;
+} xrit_monitor_summary;              /* 32 bytes */
+typedef struct xrit_monitor_state {
+    xrit_monitor_block open;
+    uint64_t symbols_total, blocks_total, calls;
+    uint32_t last_neg, have_last;
+    uint64_t hist[256];
+} xrit_monitor_state;                /* 2144 bytes */
+typedef struct xrit_monitor_quality {
+    double   level;                  /* sqrt(s2 / n) / 512 (I8: / 508): the rms in soft-symbol units */
+    double   dc;                     /* sum / (512 n) (I8: 508), the same units */
+    double   flip_rate, sat_rate, neg_rate;      /* over n */
+    double   esn0_snv_db;            /* 10 log10(m1^2 / (2 (m2 - m1^2))), m1 = s1 / n, m2 = s2 / n */
+    double   esn0_m2m4_db;           /* d = 3 s2^2 - n s4 exactly; S = sqrt(d / 2) / n, N = m2 - S: 10 log10(S / (2 N)) */
+    uint32_t flags;                  /* XRIT_MONITOR_NO_SIGNAL, XRIT_MONITOR_NO_NOISE */
+    uint32_t reserved;
+} xrit_monitor_quality;              /* 64 bytes */
+
+/* block: a multiple of 64 in 64 .. 32768, 0 selects 16384.  No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_monitor_create(xrit_monitor **m, uint32_t block, int symbol_type, int device);
+int xrit_monitor_destroy(xrit_monitor *m);
+/* the state zero; waits for the handle's last call */
+int xrit_monitor_reset(xrit_monitor *m);
+/* the blocks a push of n symbols will complete: the host keeps symbols_total mod block itself (moved on only by a push
+ * that was enqueued), so no read-back is needed to size d_rows */
+size_t xrit_monitor_rows(const xrit_monitor *m, size_t n);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation, no read-back.  d_symbols is
+ * aligned to one symbol; the 16-byte loads cover the aligned core of every piece whatever the pointer.  The head of the
+ * call completes the open block, every block completed is written to d_rows in stream order (8-byte aligned; may be
+ * null when the call completes none), the tail stays open.  cap_rows below xrit_monitor_rows(m, n): XRIT_E_CAPACITY,
+ * nothing enqueued, the state untouched.  n = 0 is a call like any other; n above 2^30: XRIT_E_INVALID.  d_summary
+ * (8-byte aligned) may be null.  Calls on one handle share its state: keep them in order. */
+int xrit_monitor_push_device(xrit_monitor *m, const void *d_symbols, size_t n, xrit_monitor_block *d_rows, size_t cap_rows,
+                             xrit_monitor_summary *d_summary, void *stream);
+/* host buffers: one upload, one download.  *n_rows: the rows written; with XRIT_E_CAPACITY the rows that were needed */
+int xrit_monitor_push(xrit_monitor *m, const void *symbols, size_t n, xrit_monitor_block *rows, size_t cap_rows, size_t *n_rows);
+/* the state after the handle's last call (waits for it) */
+int xrit_monitor_get_state(xrit_monitor *m, xrit_monitor_state *out);
+/* One record in float64: pure host code, never touches a device.  XRIT_E_INVALID for n = 0, n above 32768 or sums that
+ * no n lattice values give. */
+int xrit_monitor_derive(const xrit_monitor_block *b, int symbol_type, xrit_monitor_quality *q);
+
+/* ------------------------------------------------------------------------
  * Stage objects -- the SatHelper classes one by one, for stage-level parity
  * and for callers that keep the reference's five-Work() structure.
  * in/out are HOST pointers unless the _device variant is used.

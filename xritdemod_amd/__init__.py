@@ -25,4 +25,6 @@ from ._capi import (  # noqa: F401
     ImageCanvas, CANVAS_FILE_DTYPE, CANVAS_SLOT_DTYPE, CANVAS_SEGMENT_DTYPE, CANVAS_KEY_DTYPE, CANVAS_SUMMARY_DTYPE, CANVAS_STATS_DTYPE,
     CANVAS_REASONS,
     CarrierAcquirer, ACQUIRE_PARAMS_DTYPE, ACQUIRE_RECORD_DTYPE, ACQUIRE_STATE_DTYPE, ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK,
+    LinkMonitor, MONITOR_BLOCK_DTYPE, MONITOR_SUMMARY_DTYPE, MONITOR_STATE_DTYPE, MONITOR_QUALITY_DTYPE, SYMBOL_F32, SYMBOL_I8,
+    MONITOR_NO_SIGNAL, MONITOR_NO_NOISE,
 )

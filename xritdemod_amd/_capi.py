@@ -164,6 +164,14 @@ _SIGNATURES = {
     "xrit_acquire_estimate": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_int, _vp]),
     "xrit_acquire_mix": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp]),
     "xrit_acquire_get_state": (C.c_int, [_vp, _vp]),
+    "xrit_monitor_create": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.c_int, C.c_int]),
+    "xrit_monitor_destroy": (C.c_int, [_vp]),
+    "xrit_monitor_reset": (C.c_int, [_vp]),
+    "xrit_monitor_rows": (_sz, [_vp, _sz]),
+    "xrit_monitor_push_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "xrit_monitor_push": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "xrit_monitor_get_state": (C.c_int, [_vp, _vp]),
+    "xrit_monitor_derive": (C.c_int, [_vp, C.c_int, _vp]),
     "xrit_fir_create": (C.c_int, [C.c_uint, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "xrit_fir_work": (C.c_int, [_vp, _vp, _vp, _sz]),
     "xrit_fir_set_exact": (C.c_int, [_vp, C.c_int]),
@@ -1684,3 +1692,76 @@ class CarrierAcquirer(_Handle):
     def reset(self):
         """Phase, frequency and counters zero."""
         _check(lib().xrit_acquire_reset(self._h))
+
+
+# ---- link monitor (DESIGN.md section 22) ----------------------------------------------------------------------------------
+SYMBOL_F32, SYMBOL_I8 = 0, 1
+MONITOR_NO_SIGNAL, MONITOR_NO_NOISE = 1, 2
+# xrit_monitor_block: one block of symbols, sums on the integer lattice
+MONITOR_BLOCK_DTYPE = np.dtype([
+    ("first", np.uint64), ("n", np.uint32), ("flips", np.uint32), ("s1", np.uint64), ("s2", np.uint64), ("s4", np.uint64), ("sum", np.int64),
+    ("sat", np.uint32), ("clamped", np.uint32), ("bad", np.uint32), ("neg", np.uint32)])
+assert MONITOR_BLOCK_DTYPE.itemsize == 64
+# xrit_monitor_summary: what a push leaves for the caller
+MONITOR_SUMMARY_DTYPE = np.dtype([("rows", np.uint64), ("open_n", np.uint64), ("symbols_total", np.uint64), ("blocks_total", np.uint64)])
+assert MONITOR_SUMMARY_DTYPE.itemsize == 32
+# xrit_monitor_state: what the handle carries
+MONITOR_STATE_DTYPE = np.dtype([("open", MONITOR_BLOCK_DTYPE), ("symbols_total", np.uint64), ("blocks_total", np.uint64), ("calls", np.uint64),
+                                ("last_neg", np.uint32), ("have_last", np.uint32), ("hist", np.uint64, (256,))])
+assert MONITOR_STATE_DTYPE.itemsize == 2144
+# xrit_monitor_quality: a block record in float64
+MONITOR_QUALITY_DTYPE = np.dtype([
+    ("level", np.float64), ("dc", np.float64), ("flip_rate", np.float64), ("sat_rate", np.float64), ("neg_rate", np.float64),
+    ("esn0_snv_db", np.float64), ("esn0_m2m4_db", np.float64), ("flags", np.uint32), ("reserved", np.uint32)])
+assert MONITOR_QUALITY_DTYPE.itemsize == 64
+
+
+class LinkMonitor(_Handle):
+    """A stage behind the chain: per block of `block` symbols (a multiple of 64 in 64 .. 32768, 0 selects 16384) the sums
+    from which `derive` gives the level, two Es/N0 estimates and the flip and saturation rates.  symbol_type SYMBOL_F32
+    takes the chain's soft symbols, SYMBOL_I8 the quantiser's bytes.  The state lives in device memory: a stream may be
+    cut into pushes anywhere.  There is no lock flag: an unlocked carrier and a weak link read alike."""
+    _destroy = "xrit_monitor_destroy"
+
+    def __init__(self, block=0, symbol_type=SYMBOL_F32, device=0):
+        super().__init__()
+        self.symbol_type = symbol_type
+        _check(lib().xrit_monitor_create(C.byref(self._h), block, symbol_type, device))
+
+    def rows(self, n):
+        """The blocks a push of n symbols will complete; known on the host."""
+        return lib().xrit_monitor_rows(self._h, n)
+
+    def push(self, symbols):
+        """-> the MONITOR_BLOCK_DTYPE records of the blocks these symbols complete."""
+        a = np.ascontiguousarray(symbols, np.float32 if self.symbol_type == SYMBOL_F32 else np.int8).reshape(-1)
+        rows = np.zeros(self.rows(len(a)), MONITOR_BLOCK_DTYPE)
+        got = _sz()
+        _check(lib().xrit_monitor_push(self._h, _p(a), len(a), _p(rows), len(rows), C.byref(got)))
+        return rows[:got.value]
+
+    def push_device(self, d_symbols_ptr, n, d_rows_ptr, cap_rows, d_summary_ptr=None, stream=None):
+        """Device pointers; rows(n) records go to d_rows, 32 bytes of summary to d_summary when given.  Asynchronous on
+        stream: it may be queued directly behind Demodulator.process_device or quantize_i8_device."""
+        _check(lib().xrit_monitor_push_device(self._h, C.c_void_p(d_symbols_ptr), n, C.c_void_p(d_rows_ptr) if d_rows_ptr else None, cap_rows,
+                                              C.c_void_p(d_summary_ptr) if d_summary_ptr else None, C.c_void_p(stream) if stream else None))
+
+    def state(self):
+        """Totals, the open record, the last sign and the histogram after the last call (a MONITOR_STATE_DTYPE scalar
+        record); waits for that call."""
+        out = np.zeros(1, MONITOR_STATE_DTYPE)
+        _check(lib().xrit_monitor_get_state(self._h, _p(out)))
+        return out[0]
+
+    def reset(self):
+        """The state zero: no open block, no last symbol."""
+        _check(lib().xrit_monitor_reset(self._h))
+
+    @staticmethod
+    def derive(record, symbol_type=SYMBOL_F32):
+        """One block record -> a MONITOR_QUALITY_DTYPE scalar record.  Plain host code: no device is asked for."""
+        b = np.zeros(1, MONITOR_BLOCK_DTYPE)
+        b[0] = record
+        out = np.zeros(1, MONITOR_QUALITY_DTYPE)
+        _check(lib().xrit_monitor_derive(_p(b), symbol_type, _p(out)))
+        return out[0]

@@ -557,6 +557,11 @@ int launch_acquire_set_inc(xrit_acquire_state *st, long long inc, hipStream_t s)
 // segments = acquire_segments(n, ...): below 31 only the record (TOO_SHORT) is written; tw, win: the tables of acquire.cpp
 int launch_acquire_estimate(const void *in, int type, unsigned segments, const xrit_acquire_params &par, const float2 *tw, const float *win,
                             const AcquireScratch &sc, int apply, xrit_acquire_state *st, xrit_acquire_estimate_record *rec, hipStream_t s);
+// link monitor (monitor.hip; monitor_host.h has the plan of a push): the reduce kernel over the plan's pieces (none when
+// n = 0), then the commit kernel.  parts: two scratch records (piece 0 and the tail); rows takes plan.rows records.
+struct MonitorPlan;
+int launch_monitor_push(const void *in, int type, const MonitorPlan &plan, xrit_monitor_block *parts, xrit_monitor_state *st,
+                        xrit_monitor_block *rows, xrit_monitor_summary *summary, hipStream_t s);
 int launch_convert(const void *in, int type, float2 *out, size_t n, hipStream_t s);
 int launch_synth(const xrit_synth_params &p, uint64_t start, size_t n, float2 *out, hipStream_t s);
 int launch_read_bw(const void *buf, size_t bytes, int reps, hipStream_t s, double *gbs);

@@ -33,6 +33,9 @@
 //   * demodulator.cpp:285-290,  --tune HZ / --acquire: the reference tunes its source with the `frequency` key of the config file and is
 //     :461                      retuned by hand; a recorded capture is derotated on the device instead (xrit_acquire_*), by a given
 //                               offset or by the one estimated on the capture's first samples
+//   * DiagManager / the         --monitor FILE: nobody watches a constellation while a recorded capture runs through; per block of
+//     decoder's signal quality  soft symbols the level, two Es/N0 estimates and the flip and saturation rates go to a CSV file
+//                               (xrit_monitor_*), the run's median and its low blocks to stderr at exit
 // Only the C ABI of include/xritdemod_amd.h is used (no HIP headers): this file builds
 // with plain g++.
 #include <arpa/inet.h>
@@ -43,6 +46,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <deque>
@@ -99,6 +103,8 @@ struct Options {
     double tune_hz = 0.0;
     bool acquire = false;          // --acquire: that offset estimated on the first input of at least 65536 * R samples
     unsigned acquire_presum = 1;   // --acquire-presum R: samples summed in front of the estimator (|offset| < sample rate / 4R)
+    std::string monitor;           // --monitor FILE: one CSV line per block of soft symbols (xrit_monitor_*), a summary on stderr at exit
+    unsigned monitor_block = 16384;    // --monitor-block B: symbols per line, a multiple of 64 in 64 .. 32768
 };
 constexpr size_t FIFO_COMPLEX = 1024 * 1024 / 2;      // FIFO_SIZE floats (Parameters.h:57)
 constexpr size_t FIFO_MIN_COMPLEX = 64 * 1024 / 2;    // "Lets wait for more samples" (demodulator.cpp:113)
@@ -143,6 +149,11 @@ void usage()
                  "                                 further blocks are read ahead if a block is shorter --, printed to stderr with the strength of\n"
                  "                                 its spectral line and held for the run; unambiguous below sample rate / (4 R), R 1..64,\n"
                  "                                 default 1; when no line stands out the run goes on untuned.  With --tune the estimate replaces HZ)\n"
+                 "         [--monitor FILE [--monitor-block B]]   (the link monitor on the soft symbols of every call: one CSV line per B symbols --\n"
+                 "                                 first,n,level,dc,esn0_m2m4_db,esn0_snv_db,flip_rate,sat_rate,flags -- and at exit one line on\n"
+                 "                                 stderr: the median Es/N0, the blocks more than 3 dB under it, the share of symbols the int8\n"
+                 "                                 sink saturates.  B a multiple of 64 in 64..32768, default 16384 (a coded frame); one GPU.\n"
+                 "                                 No lock flag: an unlocked carrier reads 1.5 .. 2.5 dB, and so can a weak link)\n"
                  "         [--front-exact [-1|1|2]]   (cfg.front_exact; default 0: the bit-exact front end on blocks of less than a million symbols;\n"
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
@@ -186,6 +197,8 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--tune") { if (!(v = need("--tune"))) return false; o.tune = true; o.tune_hz = std::atof(v); }
         else if (a == "--acquire") o.acquire = true;
         else if (a == "--acquire-presum") { if (!(v = need("--acquire-presum"))) return false; o.acquire_presum = (unsigned)std::atoi(v); }
+        else if (a == "--monitor") { if (!(v = need("--monitor"))) return false; o.monitor = v; }
+        else if (a == "--monitor-block") { if (!(v = need("--monitor-block"))) return false; o.monitor_block = (unsigned)std::atoi(v); }
         else if (a == "--flywheel") {
             o.flywheel = 4;                 // parameters.h:41
             o.stream_sync = true;
@@ -243,8 +256,76 @@ bool parse(int argc, char **argv, Options &o)
         std::fprintf(stderr, "--tune / --acquire: one GPU; cf32, s16 or s8 input; --acquire-presum 1..64\n");
         return false;
     }
+    if (!o.monitor.empty() && (o.gpus > 1 || o.monitor_block < 64 || o.monitor_block > 32768 || o.monitor_block % 64)) {
+        std::fprintf(stderr, "--monitor: one GPU; --monitor-block a multiple of 64 in 64..32768\n");
+        return false;
+    }
     return !o.input.empty() && o.block > 0 && o.decimation >= 1 && o.gpus >= 1;
 }
+
+// ---- --monitor: the link monitor's rows as CSV, and what the run's summary needs ------------------------------------------
+struct MonitorLog {
+    xrit_monitor *mon = nullptr;
+    FILE *csv = nullptr;
+    std::vector<xrit_monitor_block> rows;
+    std::vector<double> esn0;           // esn0_m2m4_db of every block, for the median
+    uint64_t symbols = 0, sat = 0;
+
+    bool open(const std::string &path, unsigned block, int device)
+    {
+        if (xrit_monitor_create(&mon, block, XRIT_SYMBOL_F32, device) != XRIT_OK) {
+            std::fprintf(stderr, "monitor: %s\n", xrit_last_error());
+            return false;
+        }
+        csv = std::fopen(path.c_str(), "w");
+        if (!csv) { std::perror("monitor"); return false; }
+        std::fprintf(csv, "first,n,level,dc,esn0_m2m4_db,esn0_snv_db,flip_rate,sat_rate,flags\n");
+        return true;
+    }
+    bool add(const float *soft, size_t n)
+    {
+        rows.resize(xrit_monitor_rows(mon, n) + 1);
+        size_t got = 0;
+        if (xrit_monitor_push(mon, soft, n, rows.data(), rows.size(), &got) != XRIT_OK) {
+            std::fprintf(stderr, "monitor: %s\n", xrit_last_error());
+            return false;
+        }
+        for (size_t i = 0; i < got; ++i) {
+            xrit_monitor_quality q;
+            if (xrit_monitor_derive(&rows[i], XRIT_SYMBOL_F32, &q) != XRIT_OK) {
+                std::fprintf(stderr, "monitor: %s\n", xrit_last_error());
+                return false;
+            }
+            std::fprintf(csv, "%llu,%u,%.6f,%.6f,%.3f,%.3f,%.6f,%.6f,%u\n", (unsigned long long)rows[i].first, rows[i].n, q.level, q.dc,
+                         q.esn0_m2m4_db, q.esn0_snv_db, q.flip_rate, q.sat_rate, q.flags);
+            esn0.push_back(q.esn0_m2m4_db);
+            symbols += rows[i].n;
+            sat += rows[i].sat;
+        }
+        return true;
+    }
+    // the median over the run (the upper of the two middle blocks), the blocks more than 3 dB under it, the sink's saturation
+    void close()
+    {
+        if (csv) std::fclose(csv);
+        if (mon && csv) {
+            if (esn0.empty()) {
+                std::fprintf(stderr, "monitor: no block completed\n");
+            } else {
+                std::vector<double> sorted(esn0);
+                std::sort(sorted.begin(), sorted.end());
+                const double median = sorted[sorted.size() / 2];
+                size_t low = 0;
+                for (double v : esn0) low += v < median - 3.0;
+                std::fprintf(stderr, "monitor: %zu blocks, median Es/N0 %.2f dB, %zu blocks more than 3 dB under it, %.4f %% of the symbols saturate int8\n",
+                             esn0.size(), median, low, 100.0 * (double)sat / (double)symbols);
+            }
+        }
+        if (mon) xrit_monitor_destroy(mon);
+        mon = nullptr;
+        csv = nullptr;
+    }
+};
 
 // ---- --decode: the decoder's steps per frame (decoder/src/newdecoder.cpp:218-359) on the quantised symbols -------------
 // Whole 16384-symbol windows go through the correlator, the frame fix (HRIT: word forced to 0, NRZ-M takes the phase) and
@@ -1081,6 +1162,11 @@ int main(int argc, char **argv)
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
         return 1;
     }
+    MonitorLog monitor;
+    if (!o.monitor.empty() && !monitor.open(o.monitor, o.monitor_block, o.device)) {
+        monitor.close(); decode.close(); std::fclose(in); xrit_demod_destroy(chain);
+        return 1;
+    }
     Sink sink;
     SymbolQueue queue;
     queue.cap = o.queue_symbols;
@@ -1207,6 +1293,7 @@ int main(int argc, char **argv)
             rc = xrit_demod_process(chain, raw.data(), n, type, soft.data(), cap, &nsym);
         }
         if (rc != XRIT_OK) { std::fprintf(stderr, "process: %s\n", xrit_last_error()); exit_code = 1; break; }
+        if (monitor.mon && !monitor.add(soft.data(), nsym)) { exit_code = 1; break; }
         if (o.drop) {
             queue.add(soft.data(), nsym);         // SymbolManager::add: never waits, may drop
         } else {
@@ -1251,6 +1338,7 @@ int main(int argc, char **argv)
     }
     sink.close_all();
     decode.close();
+    monitor.close();
     std::fclose(in);
     if (acq) xrit_acquire_destroy(acq);
     xrit_demod_destroy(chain);
