@@ -74,6 +74,23 @@ def test_one_call_matches_spec(xa, count, keys):
     fa.close()
 
 
+def test_keys_on_either_side_of_a_tile_edge(xa):
+    """One call whose packets lie on the keys (v, 2047) and (v + 1, 0) alone, several files on each: the last key of one
+    tile of 2048 keys and the first of the next, so the second key's bases are all the first tile's sums."""
+    rng = np.random.default_rng(2047)
+    v, stream = 5, []
+    for key in [(v, 2047), (v + 1, 0)]:
+        stream += fs.random_stream(rng, 3, [key], max_bytes=4000, max_user=200)[0]
+    args = fs.stage_input(stream)
+    fa, st = xa.FileAssembler(), fs.State()
+    want = fs.process(st, *args)
+    for key in [(v, 2047), (v + 1, 0)]:
+        assert int(((want[2]["vcid"] == key[0]) & (want[2]["apid"] == key[1])).sum()) >= 2, key
+    same(fa.process(*args), want)
+    same_state(fa, st)
+    fa.close()
+
+
 def test_long_pieces_in_one_call_and_in_cut_calls(xa):
     """Pieces on either side of the gather's 2048-byte step and of two steps, of 8190 bytes and of 65524 (the generator
     and what it reaches: file_spec.long_piece_stream, checked in test_file_spec.py)."""

@@ -99,7 +99,7 @@ def same_state(xa, pa, st):
 
 
 @pytest.mark.parametrize("mix", ["one", "all", "skewed"])
-@pytest.mark.parametrize("nf", [1, 2, 63, 64, 65, 1023, 1025, 100000])
+@pytest.mark.parametrize("nf", [1, 2, 63, 64, 65, 1023, 1024, 1025, 100000])
 def test_one_call_matches_spec(xa, nf, mix):
     rng = np.random.default_rng(nf * 5 + len(mix))
     vcdu, off = make_case(rng, nf, mix)

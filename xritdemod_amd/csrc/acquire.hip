@@ -12,6 +12,7 @@
 #include "common.h"
 #include "exact_sincos.h"
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
@@ -191,13 +192,6 @@ __global__ void __launch_bounds__(256) acquire_power_kernel(const float2 *__rest
     P[k] = acc;
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    // lane l adds lane l ^ off's value: both of a pair add the same two numbers, so every lane ends with the same bits
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // one wave: the first maximum of P, the phase step of its bin from segment to segment, the record, the state
 __global__ void __launch_bounds__(64) acquire_finish_kernel(const float2 *__restrict__ spectra, const double *__restrict__ P,
                                                             unsigned segments, unsigned pre_sum, double sample_rate, double min_ratio,
@@ -222,7 +216,7 @@ __global__ void __launch_bounds__(64) acquire_finish_kernel(const float2 *__rest
         sum += v;
         if (v > best) { best = v; bk = k; }
     }
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {            // (no wave_max: value and bin together, ties to the lower bin)
         const double ov = __shfl_xor(best, off);
         const unsigned ok = __shfl_xor(bk, off);
         if (ov > best || (ov == best && ok < bk)) { best = ov; bk = ok; }

@@ -15,6 +15,7 @@
 // two summaries on the device.
 #include "canvas_rule.h"
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
@@ -331,11 +332,9 @@ __global__ void __launch_bounds__(64 * WAVES) canvas_commit_kernel(const xrit_im
                 clipped += !fits;
                 faults += fits && ln.status != 0;
             }
-            for (int off = 32; off > 0; off >>= 1) {
-                placed += __shfl_xor(placed, off, 64);
-                clipped += __shfl_xor(clipped, off, 64);
-                faults += __shfl_xor(faults, off, 64);
-            }
+            placed = wave_sum(placed);
+            clipped = wave_sum(clipped);
+            faults = wave_sum(faults);
             o.segment = pl.segment;
             o.start_line = pl.start_line;
             o.start_column = pl.start_column;
@@ -371,11 +370,7 @@ __global__ void __launch_bounds__(256) canvas_finish_kernel(const xrit_files_sum
     if (run) {
         for (unsigned s = w; s < n_slots; s += 4) {
             if (!slots[s].in_use) continue;
-            unsigned placed = segs[s * SEGS + lane].placed, faults = segs[s * SEGS + lane].faults;
-            for (int off = 32; off > 0; off >>= 1) {
-                placed += __shfl_xor(placed, off, 64);
-                faults += __shfl_xor(faults, off, 64);
-            }
+            const unsigned placed = wave_sum(segs[s * SEGS + lane].placed), faults = wave_sum(segs[s * SEGS + lane].faults);
             if (lane == 0) {
                 const unsigned m = slots[s].max_segment;
                 const bool complete = slots[s].done_mask == (m >= 64 ? ~0ull : (1ull << m) - 1);
@@ -397,7 +392,7 @@ __global__ void __launch_bounds__(256) canvas_finish_kernel(const xrit_files_sum
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        for (int off = 32; off > 0; off >>= 1) v[u] += __shfl_xor(v[u], off, 64);
+        v[u] = wave_sum(v[u]);
         if (lane == 0) s_sum[w][u] = v[u];
     }
     __syncthreads();

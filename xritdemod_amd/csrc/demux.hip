@@ -265,7 +265,8 @@ __global__ void __launch_bounds__(1024) demux_scatter_kernel(const xrit_sync_hit
     s_row[tid] = row;
     const long long lost = q.good ? (long long)(int)(q.counter - (unsigned)pred - 1u) : 0ll;
 
-    // workgroup inclusive prefix of the per-frame sums
+    // workgroup inclusive prefix of the per-frame sums.  Written out, not four calls of wave_ops.h's block_incl_scan: with a
+    // barrier per quantity and the totals it has no use for, the stage's call measured 0.0644 ms against 0.0617 ms
     unsigned a = wave_incl_scan((q.valid ? 1u : 0u) | (q.valid && !q.good ? 1u << 16 : 0u), lane);
     unsigned vit = wave_incl_scan(q.verr, lane), rs = wave_incl_scan(q.rs, lane);
     long long ls = wave_incl_scan(lost, lane);

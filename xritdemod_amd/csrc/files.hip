@@ -15,6 +15,7 @@
 // Everything is integer; every launch is sized from the host's bound on the packet count and reads the count itself from
 // pkt_offsets[64] on the device.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
@@ -135,15 +136,8 @@ __global__ void __launch_bounds__(SORT_THREADS) files_sort_kernel(const xrit_pac
                 c[u] = s_run[4 * tid + u];
                 sum += c[u];
             }
-            unsigned inc = sum;
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned y = __shfl_up(inc, off, 64);
-                if ((int)lane >= off) inc += y;
-            }
-            if (lane == 63) s_ws[w] = inc;
-            __syncthreads();
-            unsigned pre = inc - sum;
-            for (unsigned u = 0; u < w; ++u) pre += s_ws[u];
+            unsigned all;
+            unsigned pre = block_incl_scan<SORT_WAVES>(sum, lane, w, s_ws, all) - sum;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned a = 4 * tid + u;
@@ -329,7 +323,8 @@ __global__ void __launch_bounds__(1024) files_tile_kernel(const unsigned *__rest
                                                           unsigned long long *__restrict__ kbytes, const unsigned *__restrict__ kcnt,
                                                           unsigned long long *__restrict__ tsum)
 {
-    __shared__ unsigned long long s_p[16], s_r[16], s_b[16];
+    __shared__ unsigned s_p[16], s_r[16];
+    __shared__ unsigned long long s_b[16];
     __shared__ unsigned s_c[16][NCNT];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     if (offsets[NVC] > max_in) return;
@@ -337,34 +332,16 @@ __global__ void __launch_bounds__(1024) files_tile_kernel(const unsigned *__rest
     constexpr unsigned ROWS = FILES_TILE / 16 / 64;
     const unsigned k0 = blockIdx.x * FILES_TILE + (unsigned)w * ROWS * 64u;
     // (a call holds at most 2^24 packets: the counts fit 32 bits, the bytes do not)
-    unsigned p[ROWS], r[ROWS], ip[ROWS], ir[ROWS];
-    unsigned long long by[ROWS], ib[ROWS];
+    unsigned ep[ROWS], er[ROWS];                        // exclusive inside the wave
+    unsigned long long eb[ROWS];
     unsigned cp = 0, cr = 0;                            // the rows in front, inside the wave
     unsigned long long cb = 0;
 #pragma unroll
     for (unsigned q = 0; q < ROWS; ++q) {
         const unsigned key = k0 + q * 64u + lane;
-        p[q] = kpieces[key];
-        r[q] = krecs[key];
-        by[q] = kbytes[key];
-        unsigned xp = p[q], xr = r[q];
-        unsigned long long xb = by[q];
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned x = __shfl_up(xp, off, 64), y = __shfl_up(xr, off, 64);
-            const unsigned long long z = __shfl_up(xb, off, 64);
-            if (lane >= off) { xp += x; xr += y; xb += z; }
-        }
-        ip[q] = cp + xp;
-        ir[q] = cr + xr;
-        ib[q] = cb + xb;
-        cp += __shfl(xp, 63, 64);
-        cr += __shfl(xr, 63, 64);
-        cb += __shfl(xb, 63, 64);
-    }
-    if (lane == 0) {
-        s_p[w] = cp;
-        s_r[w] = cr;
-        s_b[w] = cb;
+        ep[q] = wave_excl_scan_step(kpieces[key], lane, cp);
+        er[q] = wave_excl_scan_step(krecs[key], lane, cr);
+        eb[q] = wave_excl_scan_step(kbytes[key], lane, cb);
     }
     // the counter increments: the wave's 128 x 7 words are contiguous; word j belongs to counter j mod 7
     {
@@ -377,24 +354,20 @@ __global__ void __launch_bounds__(1024) files_tile_kernel(const unsigned *__rest
         }
 #pragma unroll
         for (unsigned u = 0; u < NCNT; ++u) {
-            unsigned t = tc[u];
-            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+            const unsigned t = wave_sum(tc[u]);
             if (lane == 0) s_c[w][u] = t;
         }
     }
-    __syncthreads();
-    unsigned long long bp = 0, br = 0, bb = 0, ap = 0, ar = 0, ab = 0;
-#pragma nounroll
-    for (int i = 0; i < 16; ++i) {
-        if (i < w) { bp += s_p[i]; br += s_r[i]; bb += s_b[i]; }
-        ap += s_p[i]; ar += s_r[i]; ab += s_b[i];
-    }
+    unsigned ap, ar;
+    unsigned long long ab;
+    const unsigned bp = block_parts_before<16>(cp, lane, w, s_p, ap), br = block_parts_before<16>(cr, lane, w, s_r, ar);
+    const unsigned long long bb = block_parts_before<16>(cb, lane, w, s_b, ab);
 #pragma unroll
     for (unsigned q = 0; q < ROWS; ++q) {
         const unsigned key = k0 + q * 64u + lane;
-        kpieces[key] = (unsigned)bp + ip[q] - p[q];
-        krecs[key] = (unsigned)br + ir[q] - r[q];
-        kbytes[key] = bb + ib[q] - by[q];
+        kpieces[key] = bp + ep[q];
+        krecs[key] = br + er[q];
+        kbytes[key] = bb + eb[q];
     }
     unsigned long long *ts = tsum + (size_t)blockIdx.x * FILES_TSUM;
     if (tid == 0) {
@@ -420,27 +393,18 @@ __global__ void __launch_bounds__(64) files_total_kernel(const unsigned *__restr
     static_assert(FILES_KEYS / FILES_TILE == 64, "one lane per tile");
     const int lane = threadIdx.x;
     const bool run = offsets[NVC] <= max_in;
-    unsigned long long v[FILES_TSUM], inc[3];
+    unsigned long long v[FILES_TSUM], all[3] = {0, 0, 0};
 #pragma unroll
     for (unsigned u = 0; u < FILES_TSUM; ++u) v[u] = run ? tsum[(size_t)lane * FILES_TSUM + u] : 0ull;
 #pragma unroll
     for (unsigned u = 0; u < 3; ++u) {
-        unsigned long long x = v[u];
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        inc[u] = x;
-        if (run) tbase[(size_t)lane * 3 + u] = x - v[u];
+        const unsigned long long before = wave_excl_scan_step(v[u], lane, all[u]);
+        if (run) tbase[(size_t)lane * 3 + u] = before;
     }
-    const unsigned long long ap = __shfl(inc[0], 63, 64), ar = __shfl(inc[1], 63, 64), ab = __shfl(inc[2], 63, 64);
+    const unsigned long long ap = all[0], ar = all[1], ab = all[2];
     unsigned long long c[NCNT];
 #pragma unroll
-    for (unsigned u = 0; u < NCNT; ++u) {
-        unsigned long long x = v[3 + u];
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-        c[u] = x;
-    }
+    for (unsigned u = 0; u < NCNT; ++u) c[u] = wave_sum(v[3 + u]);
     if (lane == 0) {
         xrit_files_counters t = *counters;
         t.files_begun += c[0];

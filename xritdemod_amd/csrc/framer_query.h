@@ -38,6 +38,8 @@ __device__ __forceinline__ FrHit fr_query_span(const FramerPar &par, const unsig
             k1 = max(k1, ((u1 >> 6) << 20) | (0xFFFFFu - (base + 63u - (u1 & 63u))));
         }
     }
+    // (the two words' maxima stay in one written-out butterfly: as a wave maximum each, one behind the other, the frame
+    // lock's 134 rounds over a damaged stream measured 473.8 ms against 472.9 ms)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         k0 = max(k0, (unsigned)__shfl_xor((int)k0, off, 64));

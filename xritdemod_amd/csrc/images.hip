@@ -17,6 +17,7 @@
 #include "image_rule.h"
 #include "kernels.h"
 #include "rice_core.h"
+#include "wave_ops.h"
 
 namespace xrit {
 
@@ -81,34 +82,21 @@ __global__ void __launch_bounds__(IMAGES_TILE) images_tile_kernel(const xrit_fil
         const unsigned l = in ? rlines[f] : 0u;
         const unsigned long long b = in ? rbytes[f] : 0ull;
         const unsigned rice = in ? mark[f].rice : 0u, ev = in ? mark[f].events : 0u;
-        unsigned xl = l;
-        unsigned long long xb = b;
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned y = __shfl_up(xl, off, 64);
-            const unsigned long long z = __shfl_up(xb, off, 64);
-            if ((int)lane >= off) { xl += y; xb += z; }
-        }
         const unsigned c_img = __popcll(__ballot(rice != 0)), c_beg = __popcll(__ballot((ev & IMAGE_BEGUN) != 0)),
                        c_end = __popcll(__ballot((ev & IMAGE_COMPLETED) != 0)), c_abt = __popcll(__ballot((ev & IMAGE_ABORTED) != 0));
         if (lane == 63) {
-            s_l[w] = xl;
-            s_b[w] = xb;
             s_c[w][0] = c_img;
             s_c[w][1] = c_beg;
             s_c[w][2] = c_end;
             s_c[w][3] = c_abt;
         }
-        __syncthreads();
-        unsigned long long bl = 0, bb = 0, al = 0, ab = 0;
-#pragma nounroll
-        for (unsigned i = 0; i < NW; ++i) {
-            if (i < w) { bl += s_l[i]; bb += s_b[i]; }
-            al += s_l[i];
-            ab += s_b[i];
-        }
+        // (the tile's sum of lines in 64 bits: records given by hand may each claim all of the call's pieces)
+        unsigned long long al, ab;
+        const unsigned el = (unsigned)(block_incl_scan<NW>((unsigned long long)l, lane, w, s_l, al) - l);
+        const unsigned long long eb = block_incl_scan<NW>(b, lane, w, s_b, ab) - b;
         if (in) {
-            rlines[f] = (unsigned)bl + xl - l;
-            rbytes[f] = bb + xb - b;
+            rlines[f] = el;
+            rbytes[f] = eb;
         }
         unsigned long long *ts = tsum + (size_t)t * IMAGES_TSUM;
         if (tid == 0) {
@@ -138,14 +126,8 @@ __global__ void __launch_bounds__(64) images_total_kernel(const xrit_files_summa
         const unsigned t = base + lane;
 #pragma unroll
         for (unsigned u = 0; u < IMAGES_TSUM; ++u) {
-            const unsigned long long v = t < T ? tsum[(size_t)t * IMAGES_TSUM + u] : 0ull;
-            unsigned long long x = v;
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned long long y = __shfl_up(x, off, 64);
-                if ((int)lane >= off) x += y;
-            }
-            if (u < 2 && t < T) tbase[(size_t)t * 2 + u] = carry[u] + x - v;
-            carry[u] += __shfl(x, 63, 64);
+            const unsigned long long before = wave_excl_scan_step(t < T ? tsum[(size_t)t * IMAGES_TSUM + u] : 0ull, lane, carry[u]);
+            if (u < 2 && t < T) tbase[(size_t)t * 2 + u] = before;
         }
     }
     if (lane == 0)
@@ -224,7 +206,7 @@ __global__ void __launch_bounds__(64 * WAVES) images_records_kernel(const xrit_f
         if (m.rice) {
             const unsigned first = r.first_piece + r.n_pieces - m.n_lines;      // (mark: the record's pieces are all inside the call's)
             for (unsigned j = lane; j < m.n_lines; j += 64) faults += lstatus[first + j] != 0;
-            for (int off = 32; off > 0; off >>= 1) faults += __shfl_xor(faults, off, 64);
+            faults = wave_sum(faults);
         }
         if (lane == 0) {
             rfaults[f] = faults;
@@ -263,7 +245,7 @@ __global__ void __launch_bounds__(256) images_finish_kernel(const xrit_files_sum
     const bool run = images_counts(fs, max_pieces_in, max_files_in, np, nf);
     unsigned long long faults = 0;
     for (unsigned f = tid; f < nf; f += 256u) faults += rfaults[f];
-    for (int off = 32; off > 0; off >>= 1) faults += __shfl_xor(faults, off, 64);
+    faults = wave_sum(faults);
     if (lane == 0) s_f[tid >> 6] = faults;
     __syncthreads();
     if (tid != 0) return;

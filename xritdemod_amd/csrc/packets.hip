@@ -185,19 +185,8 @@ __global__ void __launch_bounds__(1024) packets_tile_kernel(const unsigned *__re
         c = (ra & 0xFFu) + (span ? 1u : 0u);
         by = ((ra >> 16) & 0x3FFu) + (span ? sp.y : 0u);        // a tile holds less than 2^27 bytes
     }
-    unsigned ci = c, bi = by;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(ci, off, 64), z = __shfl_up(bi, off, 64);
-        if (lane >= off) { ci += y; bi += z; }
-    }
-    if (lane == 63) { s_c[w] = ci; s_b[w] = bi; }
-    __syncthreads();
-    unsigned pc = ci - c, pb = bi - by, tc = 0, tb = 0;
-    for (int i = 0; i < 16; ++i) {
-        if (i < w) { pc += s_c[i]; pb += s_b[i]; }
-        tc += s_c[i];
-        tb += s_b[i];
-    }
+    unsigned tc, tb;
+    const unsigned pc = block_incl_scan<16>(c, lane, w, s_c, tc) - c, pb = block_incl_scan<16>(by, lane, w, s_b, tb) - by;
     if (r < n) {
         plocal[r] = pc;
         blocal[r] = pb;
@@ -237,22 +226,10 @@ __global__ void __launch_bounds__(1024) packets_scan_kernel(const unsigned *__re
         c += x.x;
         by += x.y;
     }
-    unsigned ci = c;
-    unsigned long long bi = by;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(ci, off, 64);
-        const unsigned long long z = __shfl_up(bi, off, 64);
-        if (lane >= off) { ci += y; bi += z; }
-    }
-    if (lane == 63) { s_c[w] = ci; s_b[w] = bi; }
-    __syncthreads();
-    unsigned pc = ci - c, tc = 0;
-    unsigned long long pb = bi - by, tb = 0;
-    for (int i = 0; i < 16; ++i) {
-        if (i < w) { pc += s_c[i]; pb += s_b[i]; }
-        tc += s_c[i];
-        tb += s_b[i];
-    }
+    unsigned tc;
+    unsigned long long tb;
+    unsigned pc = block_incl_scan<16>(c, lane, w, s_c, tc) - c;
+    unsigned long long pb = block_incl_scan<16>(by, lane, w, s_b, tb) - by;
     for (unsigned t = a; t < b; ++t) {
         tbase_c[t] = pc;
         tbase_b[t] = pb;
@@ -362,7 +339,7 @@ __device__ __forceinline__ unsigned emit_packet(const Src &s, unsigned total, un
                 reg = ((reg << 8) & 0xFFFFu) ^ s_tab[(reg >> 8) ^ byte];
             }
 #pragma unroll
-            for (int l = 0; l < 6; ++l) {
+            for (int l = 0; l < 6; ++l) {           // (no wave_ops.h sum: neighbours' CRCs joined in GF(2^16), offsets 1 up to 32)
                 const unsigned o = __shfl_xor(reg, 1 << l, 64), X = s_pw[4 + l];
                 reg = ((lane >> l) & 1) ? (gf_mul(o, X) ^ reg) : (gf_mul(reg, X) ^ o);
             }

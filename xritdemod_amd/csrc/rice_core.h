@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wave_ops.h"
+
 namespace xrit {
 
 constexpr unsigned RICE_MAX_LINE = 1u << 20;        // bytes; longer lines are refused (status 2)
@@ -83,12 +85,7 @@ __device__ __forceinline__ bool fs_section(const unsigned char *p, unsigned len,
         if (cs >= N) return false;
         const unsigned long long W = window_at(p, len, cs + 64u * lane);
         const unsigned c = __popcll(W);
-        unsigned P = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned y = __shfl_up(P, off, 64);
-            if ((int)lane >= off) P += y;
-        }
-        const unsigned T = __shfl(P, 63, 64);
+        const unsigned P = wave_incl_scan(c, (int)lane), T = wave_total(P);
         // this lane's code ends at the chunk's one of rank t (if 0 <= t < T)
         const int ts = (int)lane - (int)first - (int)found;
         const bool mine = lane >= first && lane < first + cnt && ts >= 0 && (unsigned)ts < T;
@@ -189,11 +186,7 @@ __device__ void decode_line_wave(const unsigned char *p, unsigned len, unsigned 
         // the predictor: assume no step is clipped, prefix-sum the steps, let every lane certify its step against the
         // literal rule from the sample in front, repair from the first lane that fails and certify the rest again
         const int D = (delta & 1u) ? -(int)((delta + 1u) >> 1) : (int)(delta >> 1);
-        int Sx = D;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(Sx, off, 64);
-            if ((int)lane >= off) Sx += y;
-        }
+        const int Sx = wave_incl_scan(D, (int)lane);
         int base_lane = ref ? 0 : -1, bv = (int)prev, Sb = ref ? __shfl(Sx, 0, 64) : 0;
         int x = bv + Sx - Sb;
         for (;;) {

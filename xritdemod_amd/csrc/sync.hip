@@ -75,6 +75,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) sync_correlate_kernel(const int8
 #pragma unroll
     for (int n = 0; n < SYNC_MAX_WORDS; ++n) {
         unsigned v = k[n];
+        // (not wave_ops.h's wave_max: the shift-down form, in which only lane 0 ends with the maximum)
         for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_down((int)v, off, 64));
         if (lane == 0) best[n][wave] = v;
     }
