@@ -51,9 +51,28 @@ def test_estimate_is_within_one_hertz(name):
     rec = ac.spec_record(name)
     print(f"case {name}: {rec['hz']:.4f} Hz for {c['carrier_hz']} Hz, off by {rec['hz'] - c['carrier_hz']:+.4f}; ratio {rec['ratio']:.1f}, "
           f"{rec['segments']} segments, bin {rec['k0']}")
-    assert rec["status"] == sp.OK and rec["segments"] == sp.segments_for(c["n"], c["pre_sum"])
+    assert rec["status"] == sp.OK and rec["segments"] == sp.segments_for(c["n"], c["pre_sum"], ac.segments(name))
     assert abs(rec["hz"] - c["carrier_hz"]) <= 1.0
     assert rec["inc"] == sp.inc_from_nu(rec["nu"]) and rec["applied"] == 0
+
+
+def test_the_long_cases_are_what_they_are_for():
+    """h: int8, the fewest segments; i: int16 behind a pre-sum of 4, with samples to spare; j: int8 behind the largest
+    pre-sum, nothing clipped; k: as many segments as a handle takes; l: int8 behind a pre-sum of 4, the samples of a sum
+    distinct.  In each the line stands clear of the next bin, so the device has to name the same bin."""
+    want = {"h": (sp.S8IQ, 1, 31), "i": (sp.S16IQ, 4, 31), "j": (sp.S8IQ, 64, 31), "k": (sp.FLOATIQ, 1, 4095), "l": (sp.S8IQ, 4, 31)}
+    for name, (sample_type, pre_sum, segments) in want.items():
+        rec, P = ac.spec_record(name, detail=True)
+        assert (ac.sample_type(name), ac.CASES[name]["pre_sum"], int(rec["segments"])) == (sample_type, pre_sum, segments)
+        top = np.sort(P)[-2:]
+        assert top[1] > 1.5 * top[0], name
+    j = ac.samples("j")
+    assert int(np.abs(j.astype(np.int64)).max()) == 127 and np.array_equal(j[:128], np.tile(j[:2], 64)) and not np.array_equal(j[:2], j[128:130])
+    assert ac.CASES["i"]["n"] % 4 == 3 and ac.CASES["j"]["n"] % 64 == 63
+    first = ac.samples("l")[:8:2].astype(np.int64)
+    assert len(set(first)) > 1 and np.array_equal(ac.samples("l"), ac.samples("i") >> 8)
+    k, a = ac.samples("k"), ac.samples("a")
+    assert len(k) == 8 * len(a) and np.array_equal(k[-len(a):], a)
 
 
 def test_case_d_sits_half_way_between_two_bins():

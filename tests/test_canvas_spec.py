@@ -7,6 +7,7 @@ import pytest
 import canvas_cases as cc
 import canvas_spec as cs
 import file_spec as fs
+import image_spec as isp
 
 
 def same_final(a, b):
@@ -99,6 +100,86 @@ def test_every_reason():
     # two slots, three images
     run = cc.Run([cc.no_slot_stream()], slots=2)
     assert [int(r) for r in run.calls[0][2][0]["reason"]] == [cs.PLACED, cs.PLACED, cs.NO_SLOT] and run.calls[0][2][2]["no_slot"] == 1
+
+
+def test_a_call_built_by_hand_is_the_stages_call():
+    """canvas_cases.direct_call against the packet, file and image stages: a 10-bit image of two segments on two keys, once
+    through split_image, stream_of and Run, once from its rows by hand -> the same pixels, the same per-record outputs, the
+    same masks and `complete`."""
+    rng = np.random.default_rng(80)
+    img = cs.samples(rng, 10, 32, 13, 7)
+    items = cs.split_image(rng, img, 10, 32, 77, [(3, 20), (3, 21)], [4], name=b"by hand")
+    staged = cc.Run([isp.stream_of(rng, items)])
+    segments, at = [], 0
+    for n, (key, (lo, hi)) in enumerate((((3, 20), (0, 4)), ((3, 21), (4, 7))), 1):
+        entries = []
+        for row in range(hi - lo):
+            body = img[lo + row].astype("<u2").tobytes()
+            entries.append((row, at, body, None, 0))
+            at += (len(body) + 3) & ~3
+        segments.append(cc.seg(key, (77, n, 0, lo, 2, 13, 7), 10, 13, hi - lo, entries, name=b"by hand"))
+    direct = cc.Run([cc.direct_call(segments)], direct=True)
+    (out_a, slots_a, sum_a), (out_b, slots_b, sum_b) = staged.calls[0][2], direct.calls[0][2]
+    assert np.array_equal(staged.state.image(0), img) and np.array_equal(direct.state.image(0), img)
+    assert np.array_equal(staged.state.pixels, direct.state.pixels)
+    assert len(out_a) == len(out_b) == 2
+    for f in ("reason", "slot", "segment", "start_line", "start_column", "lines_placed"):
+        assert np.array_equal(out_a[f], out_b[f]), f
+    assert [int(r) for r in out_b["reason"]] == [cs.PLACED] * 2 and [int(x) for x in out_b["lines_placed"]] == [4, 3]
+    for f in ("begun_mask", "done_mask", "aborted_mask", "complete", "pitch", "lines_placed", "bits", "vcid", "image_id", "name"):
+        assert np.array_equal(slots_a[f], slots_b[f]), f
+    assert int(slots_b[0]["done_mask"]) == 3 and int(slots_b[0]["complete"]) == 1 and sum_a == sum_b
+    # the image stage's own lines lie where the hand-built ones do: padded to 4 bytes, one behind the other
+    assert np.array_equal(staged.calls[0][1][1]["offset"], direct.calls[0][1][1]["offset"])
+    for a, b in zip(staged.calls[0][1][1], direct.calls[0][1][1]):
+        lo, hi = int(a["offset"]), int(a["offset"]) + int(a["length"])
+        assert a["length"] == b["length"] == 26 and np.array_equal(staged.calls[0][1][0][lo:hi], direct.calls[0][1][0][lo:hi])
+
+
+def test_the_hand_built_cases_hold_what_they_are_for():
+    """From the specification alone, without a device: every copy path with more than 64 of its units, the trips of the
+    commit kernel's line loop, 64 segments, the guard's four lines."""
+    call, combos = cc.copy_path_call()
+    assert len(combos) == 64 and len(set(combos)) == 64
+    took = cc.copy_paths(call)
+    assert all(n >= 2 for n in took.values()), took
+    run = cc.Run([call], slots=64, slot_bytes=cc.COPY_SLOT_BYTES, direct=True)
+    out, slots, summ = run.calls[0][2]
+    assert summ["canvases_completed"] == 64 and summ["call_lines_placed"] == 64 * cc.COPY_ROWS and summ["call_lines_clipped"] == 0
+    assert {int(p) % 16 for p in slots["pitch"]} == {12}
+    for trip in cc.tall_counts(cc.tall_entries()):
+        assert all(n > 0 for n in trip), trip
+    one, cut = cc.tall_calls()
+    run = cc.Run([one], direct=True)
+    want = [sum(t[i] for t in cc.tall_counts(cc.tall_entries())) for i in range(3)]
+    o = run.calls[0][2][0][0]
+    assert [int(o["lines_placed"]), int(o["lines_clipped"]), int(o["faults"])] == want and want[0] == cc.TALL_LINES
+    run = cc.Run(cut, direct=True)
+    assert [int(c[2][0][0]["reason"]) for c in run.calls] == [cs.PLACED] * 2 and int(run.state.slots[0]["complete"]) == 1
+    assert int(run.state.slots[0]["lines_placed"]) == cc.TALL_LINES
+    calls, (full, late), part = cc.sixty_four_segment_calls()
+    run = cc.Run(calls, direct=True)
+    st = run.state
+    assert [int(s["done_mask"]) for s in st.slots] == [2 ** 64 - 1, 2 ** 63 - 1, 2 ** 64 - 1, 1 << 63 | 1 << 32 | 4]
+    assert [int(s["complete"]) for s in st.slots] == [1, 1, 1, 0] and int(st.segments[0]["begun"].sum()) == 64
+    assert np.array_equal(st.image(0), full) and np.array_equal(st.image(1), part) and np.array_equal(st.image(2), late)
+    assert [int(s["complete"]) for s in run.calls[2][3].slots] == [1, 1, 0, 0]            # 63 of 64 done: not yet
+    assert [int(r) for r in run.calls[4][2][0]["reason"]] == [cs.DUPLICATE]
+    assert [int(r) for r in run.calls[5][2][0]["reason"]] == [cs.PLACED, cs.PLACED, cs.OVERLAP, cs.OVERLAP, cs.PLACED]
+    run = cc.Run(cc.guard_calls(), direct=True)
+    o = run.calls[1][2][0][0]
+    assert (int(o["lines_placed"]), int(o["lines_clipped"])) == (2, 2)
+    o = run.calls[2][2][0][0]
+    assert (int(o["lines_placed"]), int(o["lines_clipped"])) == (3, 1)
+    img = run.state.image(1)
+    assert img[1:, :4].all() and not img[0, :8].any() and not img[3, 4:].any()            # the long lines ran on into the next rows
+    call, slot_bytes = cc.widest_line_calls()
+    run = cc.Run([call], slots=2, slot_bytes=slot_bytes, direct=True)
+    assert [int(r) for r in run.calls[0][2][0]["reason"]] == [cs.PLACED, cs.TOO_LARGE]
+    s = run.state.slots[0]
+    assert int(s["pitch"]) * int(s["max_row"]) == slot_bytes and run.state.pixels[0, slot_bytes - 3] != 0 and int(s["complete"]) == 1
+    run = cc.Run([call], slots=2, slot_bytes=slot_bytes - 16, direct=True)
+    assert [int(r) for r in run.calls[0][2][0]["reason"]] == [cs.TOO_LARGE] * 2
 
 
 def test_aborted_segment_and_release():

@@ -1,11 +1,13 @@
 """GPU tier: the carrier acquisition stage (xrit_acquire_*, CarrierAcquirer) against the specification of
 tests/acquire_spec.py -- the mix bit for bit (every sample type, the sizes around the 16-byte groups, in place, a stream cut
-into calls, a retune between calls, source offsets that take the one-by-one kernel), the estimate on the cases of
-tests/acquire_cases.py, what `apply` does, the stage in front of the chain on one stream, the host forms, and
+into calls, a retune between calls, source offsets that take the one-by-one kernel, a call longer than the wide kernel's
+grid covers in one trip), the estimate on the cases of tests/acquire_cases.py (cf32, int16 and int8, pre-sums of 1, 4, 16
+and 64, 31 to 4095 segments), what `apply` does, the stage in front of the chain on one stream, the host forms, and
 xrit_demod_host --acquire from IQ to a locked decoder.
 
 The estimate's distance from the specification, |nu_dev - nu_spec| in bins of 1 / (2 N R), measured on an MI355X: at most
-2.6e-10 (a 2.0e-11, b 3.2e-11, c 2.6e-10, d 2.3e-10, e 5.3e-11, f 7.9e-11, g 1.1e-10); the bound is 1e-6."""
+4.3e-10 (a 2.0e-11, b 3.2e-11, c 2.6e-10, d 2.3e-10, e 5.3e-11, f 7.9e-11, g 1.1e-10, h 3.8e-10, i 4.3e-10, j 2.9e-10,
+k 6.9e-12, l 6.6e-11); the bound is 1e-6."""
 import os
 import subprocess
 
@@ -149,6 +151,32 @@ def test_mix_from_unaligned_sources(xa, torch, oracle_mod):
         aq.close()
 
 
+def test_mix_past_the_wide_kernel_s_grid(xa, torch, oracle_mod):
+    """The wide kernel's grid stops at 16384 workgroups of 256 threads, each thread a 16-byte load: 8 388 608 cf32 samples a
+    trip.  n = 2 * 4 194 304 + 2 * 256 * 5 + 1 gives five workgroups a second trip and leaves one sample to the one-by-one
+    kernel.  The specification takes 8 s over the whole array, so it is held on windows, each from its own phase
+    (lo * inc mod 2^64): the first and the last 4096 samples, 4096 either side of the second trip's first, where the second
+    trip ends, and 64 windows of 256 at seeded places; then the state and the bytes behind the output."""
+    per_trip = 16384 * 256 * 2
+    n = per_trip + 2 * 256 * 5 + 1
+    x = np.resize(ac.burst(), n)
+    hz = FREQUENCIES["0.49fs"]
+    inc = sp.inc_from_hz(hz, FS)
+    aq = xa.CarrierAcquirer(FS)
+    aq.set_frequency(hz)
+    got = device_mix(xa, torch, aq, x, sp.FLOATIQ)              # (checks the 16 bytes behind the n samples)
+    rng = np.random.default_rng(31)
+    assert per_trip + 4096 > n                                  # the second trip is short: the window around its first runs to the end
+    windows = [(0, 4096), (per_trip - 4096, n), (n - 4096, n)]
+    windows += [(lo, lo + 256) for lo in (int(v) for v in rng.integers(0, n - 256, 64))]
+    for lo, hi in windows:
+        want, _ = sp.mix(x[lo:hi], (lo * inc) & sp.MASK64, inc)
+        assert same_words(got[lo:hi], want), (lo, hi)
+    st = aq.state()
+    assert int(st["acc"]) == (n * inc) & sp.MASK64 and int(st["samples_mixed"]) == n and int(st["inc"]) == inc
+    aq.close()
+
+
 def test_u8_and_misaligned_pointers_are_refused(xa, torch):
     aq = xa.CarrierAcquirer(FS)
     t = torch.zeros(4096, dtype=torch.uint8, device="cuda:0")
@@ -177,7 +205,7 @@ def device_estimate(xa, torch, aq, a, sample_type, apply=False):
 def test_estimate_follows_the_specification(xa, torch, name):
     c = ac.CASES[name]
     want, P = ac.spec_record(name, detail=True)
-    aq = xa.CarrierAcquirer(c["fs"], pre_sum=c["pre_sum"])
+    aq = xa.CarrierAcquirer(c["fs"], pre_sum=c["pre_sum"], segments=c.get("segments", 0))
     got = device_estimate(xa, torch, aq, ac.samples(name), ac.sample_type(name), apply=True)
     again = device_estimate(xa, torch, aq, ac.samples(name), ac.sample_type(name), apply=True)
     bins = abs(float(got["nu"]) - float(want["nu"])) * 2 * sp.N * c["pre_sum"]

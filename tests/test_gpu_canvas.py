@@ -2,8 +2,15 @@
 outputs, slot table, segment tables, key states, counters and every byte of every slot's pixels, after every call: mixed
 images in one call, the stream cut into small calls, every reason, an aborted segment, a release under an open file,
 refused calls, reset and two handles, the device path behind packets, files and images on one stream, calls tiled over
-4 097 keys, faulted lines; and xrit_demod_host --canvas from IQ to .pgm files.
-Images of at most 64 x 48 pixels, slots of 16 KiB.  Every comparison is exact."""
+4 097 keys, faulted lines; and xrit_demod_host --canvas from IQ to .pgm files.  Those streams hold images of at most
+64 x 48 pixels for slots of 16 KiB.
+At real sizes, from calls built by hand (canvas_cases.direct_call) and one real-size stream: every copy path of the place
+kernel past a wave's first 64 units (lines of 1051 and 5568 bytes from every residue mod 16 to every residue), the image
+bytes 4, 8 and 12 bytes off a 16-byte boundary in device memory, a line of 131070 bytes into a slot filled to its last
+byte and TOO_LARGE on either side of that, records of 135 lines in one call and cut in two, images of 64 and of 63
+segments (bit 63, the upper lanes of the rectangle test, DUPLICATE and OVERLAP there), lines at and behind the end of
+the image bytes, lines longer than their segment; 2784 x 140 at 10 bit and 1051 x 130 through the stages in front.
+Every comparison is exact."""
 import functools
 
 import numpy as np
@@ -306,6 +313,140 @@ def test_faulted_lines_are_placed_as_the_image_stage_wrote_them(xa, torch):
     cv = xa.ImageCanvas(2, cc.SLOT_BYTES)
     same(cv.process(*inputs(xa, files_out, images_out)), want)
     same_state(torch, cv, st)
+    cv.close()
+
+
+# ---- calls built by hand (canvas_cases.direct_call): what the stages in front never vary ---------------------------------
+@functools.lru_cache(maxsize=None)
+def copy_run():
+    """canvas_cases.copy_path_call and the specification's run of it: shared, never changed."""
+    call, _ = cc.copy_path_call()
+    return call, cc.Run([call], slots=64, slot_bytes=cc.COPY_SLOT_BYTES, direct=True)
+
+
+def device_call(xa, torch, cv, files_out, images_out, pad=0):
+    """One process_device on the call's arrays, the image bytes uploaded behind `pad` bytes -> what process returns."""
+    fin, iin = inputs(xa, files_out, images_out)
+    dev = torch.device("cuda:0")
+    up = lambda a, lead=0: torch.from_numpy(np.concatenate([np.zeros(lead, np.uint8), np.ascontiguousarray(a).view(np.uint8).reshape(-1)])).to(dev)
+    d_bytes, d_pieces, d_files, d_fsum = (up(a) for a in fin)
+    d_img, d_lines, d_ifiles, d_isum = up(iin[0], pad), up(iin[1]), up(iin[2]), up(iin[3])
+    assert d_img.data_ptr() % 16 == 0
+    nf = len(fin[2])
+    d_cf, d_slots, d_sum = (torch.zeros(n, dtype=torch.uint8, device=dev) for n in (nf * 32, cv.slots * 136, 168))
+    cv.process_device(d_bytes.data_ptr(), len(fin[0]), d_pieces.data_ptr(), len(fin[1]), d_files.data_ptr(), nf, d_fsum.data_ptr(),
+                      d_img.data_ptr() + pad, len(iin[0]), d_lines.data_ptr(), len(iin[1]), d_ifiles.data_ptr(), d_isum.data_ptr(),
+                      d_cf.data_ptr(), d_slots.data_ptr(), d_sum.data_ptr())
+    torch.cuda.synchronize()
+    return (d_cf.cpu().numpy().view(xa.CANVAS_FILE_DTYPE), d_slots.cpu().numpy().view(xa.CANVAS_SLOT_DTYPE),
+            d_sum.cpu().numpy().view(xa.CANVAS_SUMMARY_DTYPE)[0])
+
+
+def test_every_copy_path_on_its_second_trip(xa, torch):
+    """Lines of 1051 bytes (16 * 65 + 4 * 2 + 3) and of 5568 (2784 samples of two bytes) from every residue mod 16 of the
+    image bytes the stages in front never produce (they pad to 4) to rows whose first bytes fall on every residue a pitch
+    of 12 mod 16 gives: the 16-byte loop with its dword and byte tails, dwords alone, dword loads with byte stores, and
+    bytes, each past its wave's first 64."""
+    call, run = copy_run()
+    took = cc.copy_paths(call)                                  # from the call's own numbers, before the device is touched
+    assert took["16"] >= 4 and took["16, 4, 1"] >= 2 and took["4"] >= 32 and took["4 to bytes"] >= 32 and took["bytes"] >= 32, took
+    assert run.calls[0][2][2]["call_lines_placed"] == 256 and run.state.slots["complete"].all()
+    cv = drive(xa, torch, run)
+    info, img = cv.image(63)
+    assert int(info["bits"]) == 10 and np.array_equal(img, run.state.image(63))
+    cv.close()
+
+
+@pytest.mark.parametrize("pad", (4, 8, 12))
+def test_image_bytes_4_8_and_12_bytes_off_a_16_byte_boundary(xa, torch, pad):
+    """The library asks 4-byte alignment of the image bytes, and the place kernel picks its path from the addresses: the
+    same call from device memory with the image bytes moved, so that other lines take the 16-byte path."""
+    call, run = copy_run()
+    files_out, images_out, want, st = run.calls[0]
+    moved, there = cc.copy_paths(call, image_base=pad), cc.copy_paths(call)
+    assert moved != there and all(n >= 2 for n in moved.values()), moved
+    cv = xa.ImageCanvas(64, cc.COPY_SLOT_BYTES)
+    same(device_call(xa, torch, cv, files_out, images_out, pad), want)
+    same_state(torch, cv, st)
+    cv.close()
+
+
+def test_the_widest_line_fills_a_slot_to_its_last_byte(xa, torch):
+    """65535 columns of 16 bits: lines of 131070 bytes, 128 trips of the 16-byte loop, in a slot of exactly pitch * max_row
+    bytes; the same image with a third row declared is TOO_LARGE there, and both are in a slot 16 bytes smaller."""
+    call, slot_bytes = cc.widest_line_calls()
+    run = cc.Run([call], slots=2, slot_bytes=slot_bytes, direct=True)
+    assert [int(r) for r in run.calls[0][2][0]["reason"]] == [cs.PLACED, cs.TOO_LARGE]
+    assert int(run.state.slots[0]["pitch"]) * 2 == slot_bytes and run.state.pixels[0, slot_bytes - 3] != 0
+    cv = drive(xa, torch, run)
+    info, img = cv.image(0)
+    assert img.shape == (2, 65535) and np.array_equal(img, run.state.image(0)) and img[1, 65534] != 0
+    cv.close()
+    run = cc.Run([call], slots=2, slot_bytes=slot_bytes - 16, direct=True)
+    assert [int(r) for r in run.calls[0][2][0]["reason"]] == [cs.TOO_LARGE] * 2 and not run.state.slots["in_use"].any()
+    drive(xa, torch, run).close()
+
+
+def test_records_of_more_lines_than_a_wave_has_lanes(xa, torch):
+    """135 lines in one record, permuted, some faulted, some beyond the segment's 129 declared lines: every trip of the commit
+    kernel's loop adds to placed, clipped and faults.  Then the same file cut after 65 lines into a record that begins and
+    one that only continues and ends."""
+    trips = cc.tall_counts(cc.tall_entries())
+    assert len(trips) == 3 and all(n > 0 for t in trips for n in t)
+    one, cut = cc.tall_calls()
+    run = cc.Run([one], direct=True)
+    o = run.calls[0][2][0][0]
+    assert [int(o["lines_placed"]), int(o["lines_clipped"]), int(o["faults"])] == [sum(t[i] for t in trips) for i in range(3)]
+    drive(xa, torch, run).close()
+    run = cc.Run(cut, direct=True)
+    assert [int(c[2][0][0]["lines_placed"]) for c in run.calls] == [63, 66] and int(run.state.slots[0]["complete"]) == 1
+    assert int(run.calls[1][0][2][0]["flags"]) == fs.ENDS
+    drive(xa, torch, run).close()
+
+
+def test_images_of_64_and_63_segments(xa, torch):
+    """Bit 63 of the masks, lanes 32 to 63 of the rectangle test, `complete` at 64 segments and at 63
+    (canvas_cases.sixty_four_segment_calls)."""
+    calls, (full, late), part = cc.sixty_four_segment_calls()
+    run = cc.Run(calls, direct=True)
+    assert [int(s["done_mask"]) for s in run.state.slots] == [2 ** 64 - 1, 2 ** 63 - 1, 2 ** 64 - 1, 1 << 63 | 1 << 32 | 4]
+    assert [int(s["complete"]) for s in run.calls[2][3].slots] == [1, 1, 0, 0] and [int(s["complete"]) for s in run.state.slots] == [1, 1, 1, 0]
+    assert [int(r) for r in run.calls[4][2][0]["reason"]] == [cs.DUPLICATE]
+    assert [int(r) for r in run.calls[5][2][0]["reason"]] == [cs.PLACED, cs.PLACED, cs.OVERLAP, cs.OVERLAP, cs.PLACED]
+    cv = drive(xa, torch, run)
+    assert int(cv.segments(0)["begun"].sum()) == 64 and int(cv.segments(1)["begun"].sum()) == 63
+    for slot, want in ((0, full), (1, part), (2, late)):
+        assert np.array_equal(cv.image(slot)[1], want)
+    cv.close()
+
+
+def test_lines_at_the_end_of_the_image_bytes_and_lines_too_long(xa, torch):
+    """canvas_line_dst's guard on inputs the stages in front never emit: a line that ends on the last image byte, one that
+    ends one behind it, an empty one at the end, an offset of 2^63; lines longer than their segment is wide."""
+    run = cc.Run(cc.guard_calls(), direct=True)
+    o = run.calls[1][2][0][0]
+    assert (int(o["lines_placed"]), int(o["lines_clipped"])) == (2, 2) and len(run.calls[1][1][0]) == 64
+    assert [int(x) for x in run.calls[1][1][1]["offset"]] == [56, 57, 64, 1 << 63]
+    o = run.calls[2][2][0][0]
+    assert (int(o["lines_placed"]), int(o["lines_clipped"])) == (3, 1) and run.state.image(1)[1:, :4].all()
+    drive(xa, torch, run).close()
+
+
+def test_real_line_and_segment_sizes_through_the_stages(xa, torch):
+    """A 10-bit image of 2784 x 140 in two segments on two keys and an 8-bit image of 1051 x 130 cut 2 x 2, through the
+    specifications of the packet, file and image stages, the stream cut into two calls."""
+    stream, images = cc.real_size_stream()
+    half = len(stream) // 2
+    run = cc.Run([stream[:half], stream[half:]], slots=2, slot_bytes=cc.REAL_SLOT_BYTES)
+    lines = np.concatenate([c[1][1] for c in run.calls])
+    assert {int(x) % 16 for x in lines["offset"]} == {0, 4, 8, 12} and {int(x) for x in lines["length"]} >= {5568, 523, 528}
+    assert max(int(x) for c in run.calls for x in c[1][2]["n_lines"]) > 64
+    assert run.state.slots["complete"].all() and run.calls[1][2][2]["lines_placed"] == 140 + 2 * 130
+    cv = drive(xa, torch, run)
+    for slot in range(2):
+        info, img = cv.image(slot)
+        assert np.array_equal(img, images[int(info["image_id"])])
+    assert bytes(cv.read(int(np.flatnonzero(run.state.slots["image_id"] == 500)[0]))[0]["name"]).rstrip(b"\0") == b"full width, 10 bit"
     cv.close()
 
 

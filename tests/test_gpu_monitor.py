@@ -1,8 +1,10 @@
 """GPU tier: the link monitor (xrit_monitor_*, LinkMonitor) against the specification of tests/monitor_spec.py.  Everything
 the stage sums is an integer, so every comparison here is np.array_equal on the rows, the summary and the state, the
-histogram included: both symbol types, blocks of 64 (a wave per piece), 16384 and 32768 (a workgroup per piece), the sizes
-around a block, source offsets that move the 16-byte core against the block boundaries, constructed values (NaN, infinities,
-signed zeros, the clamp's edges, ties, a denormal, s4 next to 2^63), a stream cut into calls, reset, two handles, a refused
+histogram included: both symbol types, blocks of 64, 192 and 1984 (a wave per piece), 2048, 16384, 32704 and 32768 (a
+workgroup per piece), the sizes around a block, source offsets that move the 16-byte core against the block boundaries, a
+push of 4100 pieces on the workgroup path's grid of 2048, constructed values (NaN, infinities, signed zeros, the clamp's
+edges, ties, a denormal, s4 next to 2^63), each of them in front of a 16-byte group's first symbol, of a block's first and
+of a call's first, a stream cut into calls, reset, two handles, a refused
 call, the stage behind the chain and behind the quantiser on one stream, the host forms and xrit_demod_host --monitor."""
 import os
 import subprocess
@@ -15,7 +17,9 @@ import monitor_spec as sp
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BLOCKS = (64, 16384, 32768)
+# 192: 12 int8 groups for a wave's 64 lanes; 1984 and 2048: either side of the switch from a wave to a workgroup per piece (1984:
+# 7.75 trips of the wave's 16-byte loop); 32704: the largest block that is no power of two
+BLOCKS = (64, 192, 1984, 2048, 16384, 32704, 32768)
 LEADS = {sp.F32: (0, 4, 12), sp.I8: (0, 1, 3, 15)}
 N_STREAM = 100003
 _STREAMS = {}
@@ -118,6 +122,22 @@ def test_pushes_equal_the_specification(xa, torch, symbol_type, block):
     mon.close()
 
 
+def test_a_push_beyond_the_workgroup_grid(xa, torch):
+    """Blocks of 2048 take a workgroup per piece on a grid of at most 2048: 37 symbols are open, then one push of
+    2048 * (2 * 2048 + 3) - 17 symbols is 4100 pieces (the head of 2011, 4098 whole blocks, a tail of 20), so workgroups 0 to 3
+    take three pieces and the others two, each trip through both barriers and the shared partials."""
+    block = 2048
+    n = block * (2 * 2048 + 3) - 17
+    x = np.resize(stream(sp.F32), 37 + n)
+    mon, ref = xa.LinkMonitor(block, sp.F32), sp.Monitor(block, sp.F32)
+    check_push(xa, torch, mon, ref, x[:37], 0)
+    assert sp.piece_count(37, n, block) == 2 * 2048 + 4 and sp.pieces_for(37, n, block)[-1] == (n - 20, n)
+    rows = check_push(xa, torch, mon, ref, x[37:], 4)
+    assert len(rows) == 2 * 2048 + 3
+    check_state(mon, ref)
+    mon.close()
+
+
 # ---- constructed values ----------------------------------------------------------------------------------------------------------
 def constructed_f32():
     tiny = np.array([1], np.uint32).view(np.float32)[0]                    # the smallest denormal
@@ -143,6 +163,48 @@ def test_constructed_float_values(xa, torch, lead):
     want, _ = loop.push(x)
     assert same(rows, want)
     mon.close()
+
+
+def in_front(values, follow, period, at):
+    """`follow` everywhere but at period * j + at, where values[j] stands: every value with `follow` on both sides."""
+    x = np.full(period * (len(values) + 1), follow, values.dtype)
+    x[at:period * len(values):period] = values
+    return x
+
+
+def each_value_in_front(xa, torch, symbol_type, values, follow, lead, turn):
+    """Block 64.  The sign in front of a lane's first symbol is taken from the symbol before it (the device has a function of
+    its own for that, apart from the one that takes a symbol in), and from the state in front of a call's first.  Every value
+    stands in front of a 16-byte group's first symbol (at every place of a group, so wherever `lead` puts the groups), in
+    front of a block's first, and at the end of a call whose successor begins with `follow`."""
+    per = 4 if symbol_type == sp.F32 else 16
+    mon, ref = xa.LinkMonitor(64, symbol_type), sp.Monitor(64, symbol_type)
+    for at in range(per):
+        check_push(xa, torch, mon, ref, in_front(values, follow, per, at), lead)
+    x = in_front(values, follow, 64, 63 - int(ref.st["open"]["n"]))          # the open symbols shift the blocks
+    check_push(xa, torch, mon, ref, x, lead)
+    for j, v in enumerate(values):
+        check_push(xa, torch, mon, ref, np.array([follow] * (1 + (j + turn) % 5) + [v], values.dtype), lead)
+    check_push(xa, torch, mon, ref, np.array([follow], values.dtype), lead)
+    check_state(mon, ref)
+    mon.close()
+
+
+@pytest.mark.parametrize("follow", (0.3, -0.3))
+def test_every_constructed_float_value_in_front_of_a_group_a_block_and_a_call(xa, torch, follow):
+    v = constructed_f32()
+    # from the specification alone: for some of them the sign of the lattice value is not the sign of the float
+    q = sp.lattice(v, sp.F32)[0]
+    assert int(np.sum((q < 0) != (v < 0))) >= 2 and int(np.sum((q < 0) != np.signbit(v))) >= 3
+    for turn in range(4):
+        each_value_in_front(xa, torch, sp.F32, np.roll(v, turn), np.float32(follow), 4 * turn, turn)
+
+
+@pytest.mark.parametrize("follow", (40, -40))
+def test_every_int8_edge_value_in_front_of_a_group_a_block_and_a_call(xa, torch, follow):
+    v = np.array([-128, -1, 0, 1, 127], np.int8)
+    for turn, lead in enumerate(LEADS[sp.I8]):
+        each_value_in_front(xa, torch, sp.I8, np.roll(v, turn), np.int8(follow), lead, turn)
 
 
 def test_s4_next_to_two_to_the_63(xa, torch):
