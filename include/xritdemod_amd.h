@@ -1089,6 +1089,115 @@ int xrit_canvas_stats(xrit_canvas *cv, xrit_canvas_counters *out);
 /* the slot free again: pixels, record and segments zero, generation + 1 (so a file still open on it stops being
  * placed).  Queued on the stream of the handle's last call; no host synchronisation. */
 int xrit_canvas_release(xrit_canvas *cv, unsigned slot);
+/* the base of the slot's pixels in device memory (a canvas is its first pitch * max_row bytes), so that a stage behind
+ * (xrit_product_process_device) reads a canvas in place.  Nothing is queued and nothing waited for: the caller orders
+ * what reads the pixels behind the handle's last call, as with xrit_canvas_read_device. */
+int xrit_canvas_pixels_device(xrit_canvas *cv, unsigned slot, const uint8_t **d_pixels);
+
+/* ------------------------------------------------------------------------
+ * Image products: what a ground station shows of an image -- a histogram, a
+ * tone curve from it, the toned 8-bit image, a thumbnail that ignores missing
+ * rows, and a two-channel false-colour composite -- made on the device from
+ * pixels that are already there, a canvas slot above all (DESIGN.md section 23;
+ * tests/product_spec.py is the specification).  Integer arithmetic throughout:
+ * the device equals the specification byte for byte.
+ *
+ *  - an image (xrit_product_image): `rows` rows of `columns` samples of `bits`
+ *    (1 .. 16) bits, `pitch` bytes from row to row; a sample is one byte for
+ *    bits <= 8 and a little-endian uint16 above, as the image and canvas stages
+ *    write them.  pitch >= columns * width; for width 2 pitch is even and d_pixels
+ *    2-byte aligned; no other alignment is asked for.  columns, rows >= 1 and
+ *    columns * rows <= 2^31.  Bytes of a row behind columns * width are never read.
+ *  - a sample above 2^bits - 1 is taken as 2^bits - 1 (for the bin and for the tone
+ *    table) and counted in out_of_range.  Value 0 is "no data": a free canvas is
+ *    all zero, so rows of missing segments are zeros.
+ *  - histogram: hist[v], uint32, 2^bits entries, over rows x columns.  With
+ *    c[v] = hist[1] + .. + hist[v] and N = c[2^bits - 1]: min_nz and max_nz are the
+ *    smallest and the largest v >= 1 with a count (0 if none).
+ *  - tone table, 2^bits bytes, by params.tone:
+ *      LINEAR    v >> (bits - 8) for bits >= 8, else v << (8 - bits).
+ *      TABLE     the caller's d_table_in (2^bits bytes), copied.
+ *      EQUALISE  lut[0] = 0; with cmin = c[min_nz], D = N - cmin: lut[v] = 1 for
+ *                1 <= v < min_nz, 1 + (254 * (c[v] - cmin) + D / 2) / D from min_nz on
+ *                (64-bit): data on 1 .. 255, no data stays 0.
+ *      STRETCH   p_lo, p_hi per myriad, 0 <= p_lo < p_hi <= 10000: lo the smallest
+ *                v >= 1 with c[v] > 0 and 10000 * c[v] >= p_lo * N, hi the smallest
+ *                v >= 1 with 10000 * c[v] >= p_hi * N; lut[0] = 0, lut[v] = 1 for
+ *                v <= lo, 255 for v >= hi, else
+ *                1 + (254 * (v - lo) + (hi - lo) / 2) / (hi - lo).
+ *    EQUALISE with D == 0, STRETCH with N == 0 or hi <= lo: LINEAR instead, and
+ *    summary.fallback = 1.  lo and hi are in the summary: 0 where no STRETCH
+ *    table was made.
+ *  - toned image: rows x columns bytes, tight: lut[v].
+ *  - thumbnail, params.factor f = 1 .. 64 (0: none): ceil(rows / f) x
+ *    ceil(columns / f) bytes, tight.  Over the part of each f x f block inside the
+ *    image, cnt the pixels with v != 0 and sum the sum of their lut[v]: the byte is
+ *    0 for cnt == 0, else (2 * sum + cnt) / (2 * cnt).  Missing rows do not darken
+ *    their neighbours.
+ *  - composite: two toned 8-bit images of one size and the caller's table of
+ *    256 x 256 x 3 bytes: rgb[y][x][k] = table[(a * 256 + b) * 3 + k], tight,
+ *    interleaved (goesdump's false-colour lookup; no table is shipped).
+ *  - the handle owns only scratch (a histogram, a tone table, a counter): no state
+ *    between calls.  Calls on one handle share the scratch: keep them in order.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_product xrit_product;
+#define XRIT_TONE_LINEAR    0
+#define XRIT_TONE_TABLE     1
+#define XRIT_TONE_EQUALISE  2
+#define XRIT_TONE_STRETCH   3
+#define XRIT_PRODUCT_MAX_FACTOR 64
+typedef struct xrit_product_image {
+    const uint8_t *d_pixels;         /* device memory (host memory for xrit_product_process) */
+    uint32_t columns, rows, pitch, bits;
+} xrit_product_image;                /* 24 bytes */
+typedef struct xrit_product_params {
+    uint32_t tone;                   /* XRIT_TONE_* */
+    uint32_t p_lo, p_hi;             /* STRETCH: per myriad; ignored otherwise */
+    uint32_t factor;                 /* thumbnail: 0 (none) or 1 .. 64 */
+} xrit_product_params;               /* 16 bytes */
+typedef struct xrit_product_summary {
+    uint64_t total;                  /* rows * columns */
+    uint64_t zeros;                  /* hist[0] */
+    uint64_t out_of_range;           /* samples above 2^bits - 1 (counted in the last bin) */
+    uint32_t min_nz, max_nz;
+    uint32_t lo, hi;
+    uint32_t fallback;               /* 1: EQUALISE or STRETCH had nothing to work on, the table is LINEAR's */
+    uint32_t tone;                   /* the tone asked for */
+    uint32_t tone_columns, tone_rows;
+    uint32_t small_columns, small_rows;      /* 0, 0 for factor 0 */
+} xrit_product_summary;              /* 64 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_product_create(xrit_product **pr, int device);
+int xrit_product_destroy(xrit_product *pr);
+/* waits for the handle's last call; there is no state to clear */
+int xrit_product_reset(xrit_product *pr);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_canvas_process_device.  Outputs: d_hist (2^bits uint32, 4-byte aligned), d_lut (2^bits bytes), d_tone
+ * (rows x columns bytes), d_small (factor > 0: ceil(rows / f) x ceil(columns / f) bytes), d_summary (8-byte aligned);
+ * each but d_summary may be NULL and is then not written.  d_table_in (2^bits bytes) is read for XRIT_TONE_TABLE only.
+ * Anything outside the bounds above, TABLE without a table, p_lo >= p_hi or p_hi > 10000, factor > 64:
+ * XRIT_E_INVALID, nothing queued, nothing written. */
+int xrit_product_process_device(xrit_product *pr, const xrit_product_image *image, const xrit_product_params *params,
+                                const uint8_t *d_table_in, uint32_t *d_hist, uint8_t *d_lut, uint8_t *d_tone, uint8_t *d_small,
+                                xrit_product_summary *d_summary, void *stream);
+/* host buffers (one upload, one download): image->d_pixels and every other pointer are host memory */
+int xrit_product_process(xrit_product *pr, const xrit_product_image *image, const xrit_product_params *params,
+                         const uint8_t *table_in, uint32_t *hist, uint8_t *lut, uint8_t *tone, uint8_t *small,
+                         xrit_product_summary *summary);
+/* the image in device memory where it lies (a canvas slot: xrit_canvas_pixels_device, once the canvas handle's last call
+ * has finished), every other pointer host memory: nothing is uploaded but TABLE's table, only the outputs asked for
+ * are downloaded.  Runs on the handle's own stream and waits. */
+int xrit_product_process_resident(xrit_product *pr, const xrit_product_image *image, const xrit_product_params *params,
+                                  const uint8_t *table_in, uint32_t *hist, uint8_t *lut, uint8_t *tone, uint8_t *small,
+                                  xrit_product_summary *summary);
+/* d_a, d_b: 8-bit images of columns x rows (>= 1, columns * rows <= 2^31), pitch_a, pitch_b >= columns; d_table
+ * 256 * 256 * 3 bytes; d_rgb rows x columns x 3 bytes.  Asynchronous on `stream`, no host synchronisation. */
+int xrit_product_composite_device(xrit_product *pr, const uint8_t *d_a, uint32_t pitch_a, const uint8_t *d_b, uint32_t pitch_b,
+                                  uint32_t columns, uint32_t rows, const uint8_t *d_table, uint8_t *d_rgb, void *stream);
+/* host buffers */
+int xrit_product_composite(xrit_product *pr, const uint8_t *a, uint32_t pitch_a, const uint8_t *b, uint32_t pitch_b, uint32_t columns,
+                           uint32_t rows, const uint8_t *table, uint8_t *rgb);
 
 /* ------------------------------------------------------------------------
  * Carrier acquisition: a stage IN FRONT of the chain that finds a large carrier

@@ -24,6 +24,8 @@ from ._capi import (  # noqa: F401
     ImageDecoder, IMAGE_LINE_DTYPE, IMAGE_FILE_DTYPE, IMAGES_SUMMARY_DTYPE, IMAGES_STATS_DTYPE, IMAGE_KEY_DTYPE, images_max_bytes,
     ImageCanvas, CANVAS_FILE_DTYPE, CANVAS_SLOT_DTYPE, CANVAS_SEGMENT_DTYPE, CANVAS_KEY_DTYPE, CANVAS_SUMMARY_DTYPE, CANVAS_STATS_DTYPE,
     CANVAS_REASONS,
+    ImageProduct, PRODUCT_IMAGE_DTYPE, PRODUCT_PARAMS_DTYPE, PRODUCT_SUMMARY_DTYPE, PRODUCT_TONES, PRODUCT_MAX_FACTOR,
+    TONE_LINEAR, TONE_TABLE, TONE_EQUALISE, TONE_STRETCH,
     CarrierAcquirer, ACQUIRE_PARAMS_DTYPE, ACQUIRE_RECORD_DTYPE, ACQUIRE_STATE_DTYPE, ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK,
     LinkMonitor, MONITOR_BLOCK_DTYPE, MONITOR_SUMMARY_DTYPE, MONITOR_STATE_DTYPE, MONITOR_QUALITY_DTYPE, SYMBOL_F32, SYMBOL_I8,
     MONITOR_NO_SIGNAL, MONITOR_NO_NOISE,

@@ -155,6 +155,15 @@ _SIGNATURES = {
     "xrit_canvas_key": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
     "xrit_canvas_stats": (C.c_int, [_vp, _vp]),
     "xrit_canvas_release": (C.c_int, [_vp, C.c_uint]),
+    "xrit_canvas_pixels_device": (C.c_int, [_vp, C.c_uint, C.POINTER(_vp)]),
+    "xrit_product_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_product_destroy": (C.c_int, [_vp]),
+    "xrit_product_reset": (C.c_int, [_vp]),
+    "xrit_product_process_device": (C.c_int, [_vp] * 10),
+    "xrit_product_process": (C.c_int, [_vp] * 9),
+    "xrit_product_process_resident": (C.c_int, [_vp] * 9),
+    "xrit_product_composite_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "xrit_product_composite": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "xrit_acquire_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int]),
     "xrit_acquire_destroy": (C.c_int, [_vp]),
     "xrit_acquire_reset": (C.c_int, [_vp]),
@@ -1614,6 +1623,124 @@ class ImageCanvas(_Handle):
     def reset(self):
         """Every slot free, every key without placement, counters and pixels zero."""
         _check(lib().xrit_canvas_reset(self._h))
+
+    def pixels_device(self, slot):
+        """The device address of the slot's pixels, for a stage that reads a canvas in place (ImageProduct.process_device);
+        the caller orders what reads them behind the last call."""
+        out = C.c_void_p()
+        _check(lib().xrit_canvas_pixels_device(self._h, slot, C.byref(out)))
+        return int(out.value)
+
+
+# ---- image products (DESIGN.md section 23) ------------------------------------------------------------------------------
+TONE_LINEAR, TONE_TABLE, TONE_EQUALISE, TONE_STRETCH = 0, 1, 2, 3
+PRODUCT_TONES = ("linear", "table", "equalise", "stretch")
+PRODUCT_MAX_FACTOR = 64
+# xrit_product_image with its pointer as an integer, xrit_product_params, xrit_product_summary
+PRODUCT_IMAGE_DTYPE = np.dtype([("d_pixels", np.uint64), ("columns", np.uint32), ("rows", np.uint32), ("pitch", np.uint32), ("bits", np.uint32)])
+assert PRODUCT_IMAGE_DTYPE.itemsize == 24
+PRODUCT_PARAMS_DTYPE = np.dtype([("tone", np.uint32), ("p_lo", np.uint32), ("p_hi", np.uint32), ("factor", np.uint32)])
+assert PRODUCT_PARAMS_DTYPE.itemsize == 16
+PRODUCT_SUMMARY_DTYPE = np.dtype([("total", np.uint64), ("zeros", np.uint64), ("out_of_range", np.uint64)] +
+                                 [(k, np.uint32) for k in ("min_nz", "max_nz", "lo", "hi", "fallback", "tone", "tone_columns", "tone_rows",
+                                                           "small_columns", "small_rows")])
+assert PRODUCT_SUMMARY_DTYPE.itemsize == 64
+
+
+def _tone_code(tone):
+    return PRODUCT_TONES.index(tone) if isinstance(tone, str) else int(tone)
+
+
+def _product_args(pixels_ptr, columns, rows, pitch, bits, tone, p_lo, p_hi, factor):
+    image = np.zeros(1, PRODUCT_IMAGE_DTYPE)
+    image[0] = (pixels_ptr, columns, rows, pitch, bits)
+    params = np.zeros(1, PRODUCT_PARAMS_DTYPE)
+    params[0] = (_tone_code(tone), p_lo, p_hi, factor)
+    return image, params
+
+
+class ImageProduct(_Handle):
+    """What is shown of an image, made on the device: the histogram, a tone table from it (linear, the caller's, equalised,
+    or stretched between two percentiles), the toned 8-bit image, a thumbnail that leaves pixels without data (value 0)
+    out of its means, and the false-colour composite of two toned images through the caller's 256 x 256 x 3 table.  The
+    handle owns scratch only; tests/product_spec.py is the specification."""
+    _destroy = "xrit_product_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_product_create(C.byref(self._h), device))
+
+    def process(self, image, bits, tone="equalise", p_lo=0, p_hi=10000, factor=0, table=None, outputs=("hist", "lut", "tone", "small")):
+        """image: 2-D, uint8 for bits <= 8, uint16 above (its row stride is taken as the pitch).  -> dict with a
+        PRODUCT_SUMMARY_DTYPE record under "summary" and, of `outputs`, "hist" (uint32, 2^bits), "lut" (uint8, 2^bits),
+        "tone" (uint8, rows x columns) and, for factor > 0, "small"."""
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != (np.uint8 if bits <= 8 else np.uint16) or image.strides[1] != image.itemsize or image.strides[0] < 0:
+            raise ValueError("a 2-D image of uint8 (bits <= 8) or uint16 samples, contiguous along its rows")
+        rows, columns = image.shape
+        return self._to_host(lib().xrit_product_process, image.ctypes.data, columns, rows,
+                             image.strides[0] if rows > 1 else columns * image.itemsize, bits, tone, p_lo, p_hi, factor, table, outputs)
+
+    def process_resident(self, d_pixels_ptr, columns, rows, pitch, bits, tone="equalise", p_lo=0, p_hi=10000, factor=0, table=None,
+                         outputs=("hist", "lut", "tone", "small")):
+        """As process, on an image that lies in device memory (ImageCanvas.pixels_device, once the canvas's last call has
+        finished): nothing is uploaded, only `outputs` are downloaded."""
+        return self._to_host(lib().xrit_product_process_resident, d_pixels_ptr, columns, rows, pitch, bits, tone, p_lo, p_hi, factor, table,
+                             outputs)
+
+    def _to_host(self, fn, pixels_ptr, columns, rows, pitch, bits, tone, p_lo, p_hi, factor, table, outputs):
+        img, params = _product_args(pixels_ptr, columns, rows, pitch, bits, tone, p_lo, p_hi, factor)
+        tab = None if table is None else np.ascontiguousarray(table, np.uint8).reshape(-1)
+        if tab is not None and len(tab) != 1 << bits:
+            raise ValueError("a table of 2^bits bytes")
+        out = {}
+        if "hist" in outputs:
+            out["hist"] = np.zeros(1 << bits, np.uint32)
+        if "lut" in outputs:
+            out["lut"] = np.zeros(1 << bits, np.uint8)
+        if "tone" in outputs:
+            out["tone"] = np.zeros((rows, columns), np.uint8)
+        if "small" in outputs and factor:
+            out["small"] = np.zeros(((rows + factor - 1) // factor, (columns + factor - 1) // factor), np.uint8)
+        summary = np.zeros(1, PRODUCT_SUMMARY_DTYPE)
+        ptr = lambda k: _p(out[k]) if k in out else None
+        _check(fn(self._h, _p(img), _p(params), None if tab is None else _p(tab), ptr("hist"), ptr("lut"), ptr("tone"), ptr("small"),
+                  _p(summary)))
+        out["summary"] = summary[0]
+        return out
+
+    def process_device(self, d_pixels_ptr, columns, rows, pitch, bits, d_summary_ptr, tone="equalise", p_lo=0, p_hi=10000, factor=0,
+                       d_table_in_ptr=None, d_hist_ptr=None, d_lut_ptr=None, d_tone_ptr=None, d_small_ptr=None, stream=None):
+        """Device pointers; the outputs that are None are not written (the summary always is, 64 bytes).  Asynchronous on
+        stream, no host synchronisation: may be queued behind ImageCanvas.process_device on a slot's pixels_device()."""
+        img, params = _product_args(d_pixels_ptr, columns, rows, pitch, bits, tone, p_lo, p_hi, factor)
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_product_process_device(self._h, _p(img), _p(params), v(d_table_in_ptr), v(d_hist_ptr), v(d_lut_ptr), v(d_tone_ptr),
+                                                 v(d_small_ptr), v(d_summary_ptr), v(stream)))
+
+    def composite(self, a, b, table):
+        """a, b: toned 8-bit images of one shape; table: 256 * 256 * 3 bytes -> uint8 (rows, columns, 3)."""
+        a, b = np.asarray(a), np.asarray(b)
+        if a.ndim != 2 or a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8 or a.strides[1] != 1 or b.strides[1] != 1:
+            raise ValueError("two 2-D uint8 images of one shape, contiguous along their rows")
+        tab = np.ascontiguousarray(table, np.uint8).reshape(-1)
+        if len(tab) != 256 * 256 * 3:
+            raise ValueError("a table of 256 * 256 * 3 bytes")
+        rows, columns = a.shape
+        rgb = np.zeros((rows, columns, 3), np.uint8)
+        pitch = lambda x: x.strides[0] if rows > 1 else columns
+        _check(lib().xrit_product_composite(self._h, _p(a), pitch(a), _p(b), pitch(b), columns, rows, _p(tab), _p(rgb)))
+        return rgb
+
+    def composite_device(self, d_a_ptr, pitch_a, d_b_ptr, pitch_b, columns, rows, d_table_ptr, d_rgb_ptr, stream=None):
+        """Device pointers; rgb rows x columns x 3 bytes.  Asynchronous on stream."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_product_composite_device(self._h, v(d_a_ptr), pitch_a, v(d_b_ptr), pitch_b, columns, rows, v(d_table_ptr),
+                                                   v(d_rgb_ptr), v(stream)))
+
+    def reset(self):
+        """Waits for the last call; there is no state."""
+        _check(lib().xrit_product_reset(self._h))
 
 
 # ---- carrier acquisition (DESIGN.md section 21) -------------------------------------------------------------------------

@@ -199,6 +199,13 @@ int xrit_canvas_read_device(xrit_canvas *cv, unsigned slot, uint8_t *d_out, size
     return XRIT_OK;
 }
 
+int xrit_canvas_pixels_device(xrit_canvas *cv, unsigned slot, const uint8_t **d_pixels)
+{
+    XR_TRY(check_slot(cv, slot, d_pixels));
+    *d_pixels = cv->st().pixels + (size_t)slot * cv->slot_bytes;
+    return XRIT_OK;
+}
+
 int xrit_canvas_read(xrit_canvas *cv, unsigned slot, uint8_t *out, size_t max_bytes, xrit_canvas_slot *info)
 {
     XR_TRY(check_slot(cv, slot, info));

@@ -544,6 +544,14 @@ int launch_canvas(const unsigned char *bytes, const xrit_file_piece *pieces, con
                   const xrit_images_summary *isum, const CanvasBounds &b, const CanvasState &st, CanvasScratch &sc,
                   xrit_canvas_file *canvas_files, xrit_canvas_slot *out_slots, xrit_canvas_summary *summary, hipStream_t s);
 int launch_canvas_release(const CanvasState &st, unsigned slot, hipStream_t s);
+// product stage (product.hip): the whole call -- hist (2^bits uint32) and over_count zeroed, histogram, tone table and
+// summary, then the toned image and the thumbnail where asked for (NULL: not written).  hist, over_count and lut are the
+// caller's or the handle's scratch, never NULL.
+int launch_product(const xrit_product_image &im, const xrit_product_params &pp, const unsigned char *table_in, uint32_t *hist,
+                   unsigned long long *over_count, unsigned char *lut, unsigned char *tone, unsigned char *small,
+                   xrit_product_summary *summary, hipStream_t s);
+int launch_product_composite(const unsigned char *a, uint32_t pitch_a, const unsigned char *b, uint32_t pitch_b, uint32_t columns,
+                             uint32_t rows, const unsigned char *table, unsigned char *rgb, hipStream_t s);
 // carrier acquisition (acquire.hip; acquire_host.h has the sizes): the handle's state is one xrit_acquire_state; the scratch
 // of an estimate of M segments
 struct AcquireScratch {

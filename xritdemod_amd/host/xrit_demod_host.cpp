@@ -97,6 +97,9 @@ struct Options {
     bool canvas = false;           // --canvas: the segment files' lines joined into full images on the device, DIR/<name>.pgm
     unsigned canvas_slots = 8;     // --canvas-slots N: canvases held at a time
     size_t canvas_mib = 32;        // --canvas-mib M: MiB per canvas (32: a 5424 x 5424 8-bit image, 29 419 776 bytes, fits)
+    bool products = false;         // --products: with --canvas, every canvas written also as DIR/<name>.view.pgm and .thumb.pgm (xrit_product_*)
+    bool product_flags = false;    // --product-tone or --product-factor was given
+    xrit_product_params product{XRIT_TONE_EQUALISE, 0, 10000, 8};      // --product-tone linear|equalise|stretch[:LO:HI], --product-factor F
     bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
     int flywheel = 0;              // --flywheel [N]: the frame lock (xrit_lock_*) in place of framer and decoder, flywheelRecheck = N
     bool tune = false;             // --tune HZ: the input derotated by tune_hz in front of the chain (xrit_acquire_*)
@@ -144,6 +147,11 @@ void usage()
                  "                                 16-bit big-endian above 8 bits; without annotation vc{vcid}_img{image_id}_{call}.pgm); what is\n"
                  "                                 incomplete at exit becomes ....partial.pgm.  N canvases (1..64, default 8) of M MiB (default 32:\n"
                  "                                 a 5424 x 5424 8-bit image fits) are held at a time)\n"
+                 "         [--products [--product-tone linear|equalise|stretch[:LO:HI]] [--product-factor F]]   (with --canvas: every canvas that\n"
+                 "                                 is written is also toned to 8 bits on the GPU from its histogram -- equalise (default), linear, or\n"
+                 "                                 stretch between the percentiles LO and HI per myriad (default 200:9800), value 0 being \"no data\" --\n"
+                 "                                 and written as DIR/<name>.view.pgm, and reduced F times (1..64, default 8; pixels without data\n"
+                 "                                 left out of the means) as DIR/<name>.thumb.pgm; only these two are downloaded)\n"
                  "         [--tune HZ]   (a carrier offset of HZ is taken out on the GPU in front of the chain; cf32, s16 or s8 input, one GPU)\n"
                  "         [--acquire [--acquire-presum R]]   (the carrier offset is estimated on the first input of at least 65536 * R samples --\n"
                  "                                 further blocks are read ahead if a block is shorter --, printed to stderr with the strength of\n"
@@ -158,6 +166,32 @@ void usage()
                  "                                  -1: the fast one always; 1: the Costas loop's final pass warmed up, ~12 %% slower on big blocks;\n"
                  "                                  2: filters, AGC and Costas loop bit for bit a CPU chain's -- soft symbols within 1e-4 rms of it\n"
                  "                                  on every configuration, ~3 x slower on big blocks)\n");
+}
+
+// --product-tone: linear | equalise | stretch | stretch:LO:HI (per myriad, 0 <= LO < HI <= 10000; plain stretch is 200:9800)
+bool parse_tone(const char *v, xrit_product_params &p)
+{
+    const std::string t = v;
+    if (t == "linear") { p.tone = XRIT_TONE_LINEAR; return true; }
+    if (t == "equalise") { p.tone = XRIT_TONE_EQUALISE; return true; }
+    if (t == "stretch") { p.tone = XRIT_TONE_STRETCH; p.p_lo = 200; p.p_hi = 9800; return true; }
+    if (t.rfind("stretch:", 0) == 0) {
+        char *end = nullptr;
+        const char *q = v + 8;
+        const long lo = std::strtol(q, &end, 10);
+        if (end != q && *end == ':') {
+            const char *r = end + 1;
+            const long hi = std::strtol(r, &end, 10);
+            if (end != r && *end == '\0' && lo >= 0 && lo < hi && hi <= 10000) {
+                p.tone = XRIT_TONE_STRETCH;
+                p.p_lo = (uint32_t)lo;
+                p.p_hi = (uint32_t)hi;
+                return true;
+            }
+        }
+    }
+    std::fprintf(stderr, "--product-tone %s: linear, equalise, stretch or stretch:LO:HI with 0 <= LO < HI <= 10000\n", v);
+    return false;
 }
 
 bool parse(int argc, char **argv, Options &o)
@@ -193,6 +227,19 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--canvas") o.canvas = true;
         else if (a == "--canvas-slots") { if (!(v = need("--canvas-slots"))) return false; o.canvas_slots = (unsigned)std::atoi(v); }
         else if (a == "--canvas-mib") { if (!(v = need("--canvas-mib"))) return false; o.canvas_mib = (size_t)std::atoll(v); }
+        else if (a == "--products") o.products = true;
+        else if (a == "--product-tone") { if (!(v = need("--product-tone")) || !parse_tone(v, o.product)) return false; o.product_flags = true; }
+        else if (a == "--product-factor") {
+            if (!(v = need("--product-factor"))) return false;
+            char *end = nullptr;
+            const long f = std::strtol(v, &end, 10);
+            if (*v == '\0' || *end != '\0' || f < 1 || f > XRIT_PRODUCT_MAX_FACTOR) {
+                std::fprintf(stderr, "--product-factor %s: 1..%d\n", v, XRIT_PRODUCT_MAX_FACTOR);
+                return false;
+            }
+            o.product.factor = (uint32_t)f;
+            o.product_flags = true;
+        }
         else if (a == "--stream-sync") o.stream_sync = true;
         else if (a == "--tune") { if (!(v = need("--tune"))) return false; o.tune = true; o.tune_hz = std::atof(v); }
         else if (a == "--acquire") o.acquire = true;
@@ -250,6 +297,10 @@ bool parse(int argc, char **argv, Options &o)
     if (o.canvas && (!o.files_decompress || o.canvas_slots < 1 || o.canvas_slots > XRIT_CANVAS_MAX_SLOTS || o.canvas_mib < 1 ||
                      o.canvas_mib > 4096)) {
         std::fprintf(stderr, "--canvas needs --files DIR --files-decompress; --canvas-slots 1..%d, --canvas-mib 1..4096\n", XRIT_CANVAS_MAX_SLOTS);
+        return false;
+    }
+    if ((o.products && !o.canvas) || (o.product_flags && !o.products)) {
+        std::fprintf(stderr, "--products needs --canvas; --product-tone and --product-factor need --products\n");
         return false;
     }
     if ((o.tune || o.acquire) && (o.gpus > 1 || o.format == "u8" || o.acquire_presum < 1 || o.acquire_presum > 64)) {
@@ -373,6 +424,11 @@ struct FrameDecode {
     std::vector<uint8_t> cv_pixels, cv_row;
     xrit_canvas_summary cv_summary{};
     size_t canvases_written = 0;
+    bool products = false;          // --products (set it and product before open())
+    xrit_product_params product{};
+    xrit_product *pr = nullptr;
+    std::vector<uint8_t> pr_tone, pr_small;
+    size_t products_written = 0, product_fallbacks = 0;
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
     std::vector<xrit_frame_stats> records;
@@ -451,6 +507,10 @@ struct FrameDecode {
                 }
                 cv_slots.assign(canvas_slots, xrit_canvas_slot{});
                 cv_pixels.resize(canvas_bytes);
+                if (products && xrit_product_create(&pr, device) != XRIT_OK) {
+                    std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                    return false;
+                }
             }
         }
         return true;
@@ -713,6 +773,33 @@ struct FrameDecode {
         std::fclose(f);
         if (!ok) { std::perror(path.c_str()); return false; }
         ++canvases_written;
+        return !pr || write_products(s, info, file_dir + "/" + name + (partial ? ".partial" : ""));
+    }
+    // --products: the slot's pixels toned and reduced where they lie; the two products are what is downloaded
+    bool write_products(unsigned s, const xrit_canvas_slot &info, const std::string &stem)
+    {
+        if (!info.max_column || !info.max_row) return true;
+        xrit_product_image image{nullptr, info.max_column, info.max_row, info.pitch, info.bits};
+        if (xrit_canvas_pixels_device(cv, s, &image.d_pixels) != XRIT_OK) return fail("canvas pixels");
+        const uint32_t f = product.factor, small_columns = (info.max_column + f - 1) / f, small_rows = (info.max_row + f - 1) / f;
+        pr_tone.resize((size_t)info.max_column * info.max_row);
+        pr_small.resize((size_t)small_columns * small_rows);
+        xrit_product_summary summary{};
+        if (xrit_product_process_resident(pr, &image, &product, nullptr, nullptr, nullptr, pr_tone.data(), pr_small.data(), &summary) != XRIT_OK)
+            return fail("products");
+        product_fallbacks += summary.fallback;
+        const struct { const char *ext; const std::vector<uint8_t> *bytes; uint32_t columns, rows; } outs[] = {
+            {".view.pgm", &pr_tone, summary.tone_columns, summary.tone_rows}, {".thumb.pgm", &pr_small, summary.small_columns, summary.small_rows}};
+        for (const auto &o : outs) {
+            const std::string path = stem + o.ext;
+            FILE *f = std::fopen(path.c_str(), "wb");
+            if (!f) { std::perror(path.c_str()); return false; }
+            const bool ok = std::fprintf(f, "P5\n%u %u\n255\n", o.columns, o.rows) > 0 &&
+                            std::fwrite(o.bytes->data(), 1, o.bytes->size(), f) == o.bytes->size();
+            std::fclose(f);
+            if (!ok) { std::perror(path.c_str()); return false; }
+        }
+        ++products_written;
         return true;
     }
     void close_packet_files()
@@ -788,6 +875,12 @@ struct FrameDecode {
                              (unsigned long long)cv_summary.lines_placed, (unsigned long long)cv_summary.lines_clipped,
                              (unsigned long long)(cv_summary.bad_segment + cv_summary.too_large + cv_summary.duplicate + cv_summary.overlap +
                                                   cv_summary.no_slot + cv_summary.no_placement));
+                if (pr) {
+                    std::fprintf(stderr, "products: %zu canvases toned and reduced %u times, %zu of them by the linear fallback\n", products_written,
+                                 product.factor, product_fallbacks);
+                    xrit_product_destroy(pr);
+                    pr = nullptr;
+                }
                 xrit_canvas_destroy(cv);
                 cv = nullptr;
             }
@@ -1157,6 +1250,8 @@ int main(int argc, char **argv)
     FrameDecode decode;
     decode.canvas_slots = o.canvas ? o.canvas_slots : 0;
     decode.canvas_bytes = o.canvas_mib << 20;
+    decode.products = o.products;
+    decode.product = o.product;
     if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
         !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync, o.flywheel)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
