@@ -2,7 +2,10 @@
 the count and the counters of every call compared exactly: the table of streams on which the flywheel shows, pushed whole
 (a stop for an RS outcome and a second round) and cut (the outcome comes from the committed state), HRIT, a short hit
 below the acceptance, empty and tiny calls, segment lengths and resident windows, reset, recheck = 1 against
-FrameSynchroniser followed by FrameDecoder, the device path with the demultiplexer behind it, the error paths."""
+FrameSynchroniser followed by FrameDecoder, the device path with the demultiplexer behind it, the error paths; and a long
+damaged stream (192 frames, up to 10 rounds in a call) at recheck 2, 3, 4, 5, 255 and 1, whole, with other segments, cut
+into calls, as HRIT and on the device path, its rounds within the bounds the specification's rows set; whole batches of 64
+frames in lock at eight rechecks, and in front of a planted chunk that shows the fc they left."""
 import ctypes as C
 
 import numpy as np
@@ -249,8 +252,8 @@ def test_error_paths(xa, oracle_mod):
 
 def test_hundreds_of_frames_in_lock_with_whole_waves_of_records(xa, oracle_mod):
     """600 aligned frames (8 coded frames tiled) with walker segments of 128 chunks, so that joints and commit take 64
-    rows at a time: recheck 1 against FrameSynchroniser followed by FrameDecoder, recheck 4 with the same rows and the
-    modes of a stream in lock."""
+    rows at a time: recheck 1 against FrameSynchroniser followed by FrameDecoder, every other recheck with the same rows
+    and the modes of a stream in lock."""
     frames, _ = fc.coded_frames(8, np.random.default_rng(3))
     n = 600
     stream = np.tile(frames.reshape(-1), n // 8)
@@ -258,7 +261,9 @@ def test_hundreds_of_frames_in_lock_with_whole_waves_of_records(xa, oracle_mod):
     w = sync.push(stream, trim=False)
     w_cadu, w_block, w_info = dec.decode(w[0], w[1])
     assert w[4] == n and int(w_info["ok"].sum()) == n
-    for recheck in (1, 4):
+    # 3, 5, 7: a whole batch of 64 does not return fc to where it was; 255: fc == recheck falls once, inside a batch; 64: on
+    # a batch's edge
+    for recheck in (1, 2, 3, 4, 5, 7, 64, 255):
         lock = xa.FrameLock("lrit", flywheel=recheck, segment=128)
         frames_, valid, hits, start, mode, cadu, block, info, count = lock.push(stream, trim=False)
         st = lock.stats()
@@ -350,3 +355,170 @@ def test_recheck_1_counts_the_first_chunk_behind_a_reset_sensitive(xa, oracle_mo
         st = check_stats(lock, spec)
         assert int(st["sensitive_chunks"]) == 1 and int(st["rounds"]) == int(st["calls"]) == len(cuts) + 1
         lock.close()
+
+
+# ---- the long damaged stream (lock_cases.long_stream): many rounds in a call, whole batches of records between them ----
+def long_pair(xa, ref, recheck, **kw):
+    return xa.FrameLock("hrit" if ref["hrit"] else "lrit", flywheel=recheck, **kw), lc.long_lock(ref, recheck)
+
+
+def check_how_it_went(st, rows, bounds, recheck, calls=1):
+    """The device's own counters: rounds within the bounds the specification's rows give, every row walked or adopted."""
+    rounds, rewalked, adopted = int(st["rounds"]), int(st["rewalked_chunks"]), int(st["adopted_chunks"])
+    print("recheck", recheck, "rounds", rounds, "bounds", bounds, "rewalked", rewalked, "adopted", adopted, "rows", len(rows))
+    if recheck == 1:
+        assert rounds == calls
+    else:
+        assert bounds[0] <= rounds <= bounds[1]
+    assert rewalked + adopted == len(rows) and int(st["calls"]) == calls
+
+
+@pytest.mark.parametrize("recheck", [2, 3, 4, 5, 255, 1])
+def test_long_damaged_stream_pushed_whole(xa, oracle_mod, recheck):
+    ref = lc.long_reference(recheck)
+    lock, spec = long_pair(xa, ref, recheck)
+    got = push_and_compare(lock, spec, [ref["stream"]])
+    assert got.same_as(ref["rows"])
+    st = check_stats(lock, spec)
+    check_how_it_went(st, got, ref["bounds"], recheck)
+    assert int(st["rewalked_chunks"]) > 0 and int(st["adopted_chunks"]) > 64
+    lock.close()
+
+
+@pytest.mark.parametrize("kw", [dict(segment=1), dict(segment=7), dict(segment=128), dict(windows=1)], ids=str)
+@pytest.mark.parametrize("recheck", [4, 3])
+def test_long_damaged_stream_whatever_the_walkers_segments(xa, oracle_mod, recheck, kw):
+    """Segments of 1 chunk (every record a single step), of 7 (records entered in their middle behind a rewalk), of 128
+    (batches of 64 records that mix good, bad and dropped frames, MISS and SHORT chunks), and one resident window."""
+    ref = lc.long_reference(recheck)
+    lock, spec = long_pair(xa, ref, recheck, **kw)
+    got = push_and_compare(lock, spec, [ref["stream"]])
+    assert got.same_as(ref["rows"])
+    check_how_it_went(check_stats(lock, spec), got, ref["bounds"], recheck)
+    lock.close()
+
+
+def sensitive_cuttings(ref):
+    """Cuts at rows that only a known ok = true decides (SHORT at position 0 against a whole-chunk hit elsewhere, behind
+    a valid row): 100 symbols behind the row's chunk, on the chunk's first symbol, in the middle of the frame before it --
+    each alone at one such row, and the three in one cutting at three such rows."""
+    rows, flags = ref["rows"], lc.nz_s0(ref["rows"], ref["cache"])
+    at = [i for i, (nz, s0) in enumerate(flags) if nz and s0 and (int(rows.mode[i]) & 3) == ls.SHORT and rows.valid[i - 1]]
+    a, b, c = (lc.chunk_of(rows, i) for i in (at[0], at[len(at) // 2], at[-1]))
+    assert a + 2 * F < b < c - 2 * F
+    return [[b + F + 100], [b], [b - F // 2], [a + F + 100, b, c - F // 2]]
+
+
+@pytest.mark.parametrize("recheck", [4, 5])
+def test_long_damaged_stream_cut_into_calls(xa, oracle_mod, recheck):
+    ref = lc.long_reference(recheck)
+    stream = ref["stream"]
+    lock = xa.FrameLock("lrit", flywheel=recheck)
+    for cuts in lc.long_cuttings(len(stream)) + sensitive_cuttings(ref):
+        lock.reset()
+        spec = lc.long_lock(ref, recheck)
+        pieces, parts, lower, upper, rounds = pieces_of(stream, cuts), [], 0, 0, 0
+        for piece in pieces:
+            parts.append(push_and_compare(lock, spec, [piece]))
+            st = check_stats(lock, spec)
+            stop = lc.stop_of(spec)
+            lc.fill_short_hits(ref, [] if stop is None else [stop])
+            lo, hi = lc.round_bounds(parts[-1], ref["cache"], stop)
+            assert lo <= int(st["rounds"]) - rounds <= hi, (cuts, len(parts))
+            lower, upper, rounds = lower + lo, upper + hi, int(st["rounds"])
+        got = ls.Rows.concat(parts, F)
+        assert got.same_as(ref["rows"]), cuts
+        print("cuts", len(cuts), "rounds", rounds, "bounds", (lower, upper))
+        assert lower <= rounds <= upper and int(st["calls"]) == len(pieces)
+        assert int(st["rewalked_chunks"]) + int(st["adopted_chunks"]) == len(got)
+    lock.close()
+
+
+def test_long_damaged_stream_hrit(xa, oracle_mod):
+    ref = lc.long_reference(4, n=96, hrit=True)
+    stream = ref["stream"]
+    assert ref["stats"]["sensitive_chunks"] >= 2 and ref["stats"]["short_missed"] >= 2 and ref["bounds"][0] >= 2
+    for cuts in ([], [len(stream) // 2 + 4321]):
+        lock, spec = long_pair(xa, ref, 4)
+        pieces = pieces_of(stream, cuts)
+        got = push_and_compare(lock, spec, pieces)
+        assert got.same_as(ref["rows"])
+        st = check_stats(lock, spec)
+        assert int(st["calls"]) == len(pieces) and int(st["rewalked_chunks"]) + int(st["adopted_chunks"]) == len(got)
+        if not cuts:
+            check_how_it_went(st, got, ref["bounds"], 4)
+        lock.close()
+
+
+def test_long_damaged_stream_on_the_device_path_with_the_demultiplexer_behind_it(xa, oracle_mod):
+    """Many rounds with a stage waiting behind them: push_device at recheck 4 on a side stream into poisoned buffers,
+    xrit_demux_process_device queued behind it on all rows_cap rows; the demultiplexer's outputs against those it gives
+    on the host path's rows."""
+    torch = pytest.importorskip("torch")
+    ref = lc.long_reference(4)
+    stream = ref["stream"]
+    dev = torch.device("cuda:0")
+    lock, dm, dm2 = xa.FrameLock("lrit", flywheel=4), xa.ChannelDemux(), xa.ChannelDemux()
+    host = xa.FrameLock("lrit", flywheel=4)
+    s = torch.cuda.Stream(device=dev)
+    d_sym = torch.from_numpy(stream.view(np.uint8).copy()).to(dev)
+    torch.cuda.synchronize()
+    n, cap = len(stream), lock.rows(len(stream))
+    sizes = dict(frames=cap * F, valid=cap, hits=cap * 16, start=cap * 8, mode=cap, cadu=cap * 1024, block=cap * 1020,
+                 info=cap * 40, count=4, vcdu=cap * 892, off=65 * 4, rec=cap * 88)
+    b = {k: torch.full((v,), 0xAB, dtype=torch.uint8, device=dev) for k, v in sizes.items()}
+    with torch.cuda.stream(s):
+        lock.push_device(d_sym.data_ptr(), n, *(b[k].data_ptr() for k in ("frames", "valid", "hits", "start", "mode", "cadu",
+                                                                          "block", "info", "count")), stream=s.cuda_stream)
+        dm.process_device(b["hits"].data_ptr(), b["cadu"].data_ptr(), b["block"].data_ptr(), b["info"].data_ptr(), cap,
+                          b["vcdu"].data_ptr(), b["off"].data_ptr(), b["rec"].data_ptr(), stream=s.cuda_stream)
+    s.synchronize()
+    want = host.push(stream, trim=False)
+    rows = ref["rows"]
+    assert want[8] == len(rows) and all(np.array_equal(w[:len(rows)], getattr(rows, f)) for f, w in zip(ls.FIELDS[:7], want))
+    dtypes = dict(frames=np.int8, hits=np.uint32, start=np.uint64, info=xa.FRAME_INFO_DTYPE)
+    for k, w in zip(ls.FIELDS, want):
+        assert b[k].cpu().numpy().view(dtypes.get(k, np.uint8)).reshape(w.shape).tobytes() == w.tobytes(), k
+    assert int(b["count"].cpu().numpy().view(np.uint32)[0]) == want[8]
+    st = lock.stats()
+    assert ref["bounds"][0] <= int(st["rounds"]) <= ref["bounds"][1] and int(st["rounds"]) == int(host.stats()["rounds"])
+    w_vcdu, w_off, w_rec = dm2.process(want[2], want[5], want[6], want[7])
+    good = ref["stats"]["frames_ok"]
+    off = b["off"].cpu().numpy().view(np.uint32)
+    assert np.array_equal(off, w_off) and int(off[64]) == good == len(w_vcdu)
+    assert np.array_equal(b["vcdu"].cpu().numpy()[:good * 892].reshape(good, 892), w_vcdu)
+    rec = b["rec"].cpu().numpy().view(xa.FRAME_STATS_DTYPE)
+    for f in rec.dtype.names:
+        if f != "reserved":
+            assert np.array_equal(rec[f], w_rec[f]), f
+    a, c = dm.stats(), dm2.stats()
+    for f in a.dtype.names:
+        if f not in ("start_time", "reserved"):              # start_time: when each handle was made
+            assert np.array_equal(a[f], c[f]), f
+    for h in (lock, host, dm, dm2):
+        h.close()
+
+
+# a whole batch of 64 records in lock, then a planted chunk: (recheck, the planted frame, whether fc == recheck at its entry)
+BATCH_CASES = [(2, 64, True), (4, 64, True), (64, 64, True), (3, 66, True), (5, 65, True), (7, 70, True),
+               (3, 64, False), (5, 64, False), (255, 64, False), (4, 65, False), (64, 65, False)]
+
+
+@pytest.mark.parametrize("recheck,at,due", BATCH_CASES)
+def test_fc_behind_a_whole_batch_in_lock_decides_a_planted_chunk(xa, oracle_mod, recheck, at, due):
+    """Walker segments of 128 chunks: the first 64 rows are adopted as a whole batch with fc in closed form, in the joints
+    and in the commit.  The planted chunk behind them shows what fc the joints came out with.  Where fc == recheck at its
+    entry, step 1 clears ok: the chunk is decided without the RS outcome of the row before it and the call is ONE round
+    (fc is known: no chunk before it has a whole-chunk hit off position 0) -- a joints' fc that is not recheck there stops
+    the round.  Everywhere else the chunk hangs on that RS outcome and the call is TWO rounds (round_bounds gives 2, 2) -- a
+    joints' fc that is recheck there takes the plant, and the commit's replay refuses the round."""
+    ref = lc.batch_reference(recheck, at)
+    lock, spec = long_pair(xa, ref, recheck, segment=128)
+    got = push_and_compare(lock, spec, [ref["stream"]])
+    assert got.same_as(ref["rows"])
+    st = check_stats(lock, spec)
+    want_mode = (ls.FULL | ls.RECHECK) if due else ls.SHORT
+    assert int(got.mode[at]) == want_mode and int(got.hits[at][1]) == (lc.PLANT_AT if due else 0)
+    assert ref["bounds"] == ((1, 2) if due else (2, 2)) and int(st["rounds"]) == (1 if due else 2)
+    assert int(st["rewalked_chunks"]) + int(st["adopted_chunks"]) == len(got) and int(st["adopted_chunks"]) >= 64
+    lock.close()

@@ -1,6 +1,7 @@
 """CPU tier: the frame lock's specification (tests/lock_spec.py) -- the consequences DESIGN.md section 18 states, the table
-of streams on which the flywheel shows, recheck = 1 against the framer's and the decoder's own specifications, and the
-state machine alone on small frames with a cheap stand-in for the decoder."""
+of streams on which the flywheel shows, recheck = 1 against the framer's and the decoder's own specifications, the long
+damaged stream of the GPU tier (that it reaches what it is there for, from the specification alone), and the state
+machine alone on small frames with a cheap stand-in for the decoder."""
 import numpy as np
 import pytest
 
@@ -18,9 +19,9 @@ def modes(rows):
     return [int(m) for m in rows.mode]
 
 
-def decoded_like_the_decoder(rows, hrit):
+def decoded_like_the_decoder(rows, hrit, carry=None):
     """cadu, block and info of the rows against ccsds's stages run over all rows at once (the decoder's own spec)."""
-    w, idx, _ = ccsds.windows(rows.frames, rows.valid)
+    w, idx, _ = ccsds.windows(rows.frames, rows.valid, carry)
     cadu = np.zeros((len(rows), ccsds.CADU_BYTES), np.uint8)
     block = np.zeros((len(rows), ccsds.BLOCK_BYTES), np.uint8)
     info = np.array([ls.absent_info()] * len(rows), ls.INFO_DTYPE)
@@ -126,6 +127,65 @@ def test_recheck_1_is_the_framer_then_the_decoder(oracle_mod):
     assert decoded_like_the_decoder(rows, False)
     assert {k: lk.stats()[k] for k in fs.STATS} == fr.stats()
     assert modes(rows) == [0] + [R1] * 11
+
+
+# ---- the long damaged stream of the GPU tier: does it reach what it is there for? --------------------------------------
+@pytest.mark.parametrize("recheck", [2, 3, 4, 5, 255])
+def test_long_stream_earns_its_place(oracle_mod, recheck):
+    """Conditions on lock_cases.long_stream() pushed whole, from the specification alone: enough chunks of every kind, more
+    rows than two batches of 64, and at least four rounds that no device can avoid (round_bounds' lower bound)."""
+    ref = lc.long_reference(recheck)
+    rows, st, cache = ref["rows"], ref["stats"], ref["cache"]
+    fck0 = lc.fck0_rows(rows, cache)
+    print("recheck", recheck, "rows", len(rows), {k: st[k] for k in ls.STATS}, "bounds", ref["bounds"], "fck0", fck0)
+    assert st["sensitive_chunks"] >= 4 and st["short_missed"] >= 4 and st["frames_bad"] >= 6
+    assert st["dropped_chunks"] >= 3 and st["resyncs"] >= 15 and len(rows) > 128
+    lower, upper = ref["bounds"]
+    assert 4 <= lower <= upper
+    assert {ls.FULL, ls.SHORT, ls.MISS} <= set(m & 3 for m in modes(rows))
+    if recheck == 4:
+        assert len(fck0) >= 2                   # fc not known at a chunk that hangs on it, twice at the least
+        plain = lc.long_reference(1)            # ... and the flywheel shows: other rows, more good frames
+        assert not np.array_equal(rows.start[:len(plain["rows"])], plain["rows"].start[:len(rows)])
+        assert st["frames_ok"] > plain["stats"]["frames_ok"] and plain["bounds"][0] == 1
+
+
+def test_long_stream_memoised_decode_is_the_decoder(oracle_mod):
+    """The rows of the long stream are decoded through lock_cases.memo_decode; the 30 rows up to two behind the first dropped
+    chunk (frames that fail RS among them) against the decoder's stages run over them at once, behind the carry of the row
+    before them."""
+    rows = lc.long_reference(4)["rows"]
+    b = int(np.flatnonzero(rows.valid == 0)[0]) + 3
+    part = ls.Rows(F, **{f: getattr(rows, f)[b - 30:b] for f in ls.FIELDS})
+    assert rows.valid[b - 31] and not part.info["ok"][part.valid != 0].all()
+    assert decoded_like_the_decoder(part, False, rows.frames[b - 31][-ccsds.CARRY:])
+
+
+@pytest.mark.parametrize("recheck", [4, 3])
+def test_long_stream_rows_do_not_depend_on_the_cutting(oracle_mod, recheck):
+    ref = lc.long_reference(recheck)
+    for cuts in lc.long_cuttings(len(ref["stream"])):
+        spec = lc.long_lock(ref, recheck)
+        per_call = [spec.push(p) for p in lc.pieces_of(ref["stream"], cuts)]
+        assert ls.Rows.concat(per_call, F).same_as(ref["rows"]), cuts
+        assert spec.stats() == ref["stats"], cuts
+        assert all(1 <= lo <= hi for lo, hi in (lc.round_bounds(r, ref["cache"]) for r in per_call))
+
+
+@pytest.mark.parametrize("recheck,at,due", [(4, 64, True), (3, 66, True), (3, 64, False), (255, 64, False)])
+def test_planted_chunk_behind_64_frames_in_lock(oracle_mod, recheck, at, due):
+    """lock_cases.batch_reference: 64 good frames at position 0, then a planted chunk entered with fc == recheck (step 1
+    fires, the whole chunk is correlated, the plant is followed) or not (SHORT at position 0, and only ok decides it)."""
+    ref = lc.batch_reference(recheck, at)
+    rows = ref["rows"]
+    assert rows.valid[:at].all() and rows.info["ok"][:at].all() and not rows.hits[:at, 1].any()
+    assert modes(rows)[:at] == [4 if i and (i - 1) % recheck + 1 == recheck else (1 if i else 0) for i in range(at)]
+    if due:
+        assert modes(rows)[at] == R1 and rows.hits[at, 1] == lc.PLANT_AT and not rows.info["ok"][at]
+        assert ref["stats"]["sensitive_chunks"] == 0 and ref["bounds"] == (1, 2)
+    else:
+        assert modes(rows)[at] == ls.SHORT and rows.hits[at, 1] == 0 and rows.info["ok"].all() and len(rows) == at + 6
+        assert ref["stats"]["sensitive_chunks"] == 1 and ref["bounds"] == (2, 2)
 
 
 # ---- the state machine alone: frames of 2048 symbols, a stand-in for the decoder --------------------------------------
