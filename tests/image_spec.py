@@ -174,12 +174,17 @@ class Rows:
 
 
 # ---- generator ------------------------------------------------------------------------------------------------------
-def image_file(rng, n, J, cols, rows, kinds=rs.KINDS, spoil=None, force=None):
+def image_file(rng, n, J, cols, rows, kinds=rs.KINDS, spoil=None, force=None, coded=None):
     """A rice-coded image file -> (samples (rows, cols), file bytes, cuts): the cuts put the headers alone into the first
     packet and one coded line into each one behind it.  spoil(rng, line) damages a coded line before it is packed;
-    force is rs.encode's."""
-    img = np.stack([rs.samples(rng, kinds[int(rng.integers(0, len(kinds)))], n, J, cols) for _ in range(rows)])
-    coded = [rs.encode(row, n, J, force=force) for row in img]
+    force is rs.encode's.  coded: the `rows` lines to pack instead of rs.encode's (lines of another encoder); no
+    samples are drawn then and None is returned for them."""
+    if coded is None:
+        img = np.stack([rs.samples(rng, kinds[int(rng.integers(0, len(kinds)))], n, J, cols) for _ in range(rows)])
+        coded = [rs.encode(row, n, J, force=force) for row in img]
+    else:
+        assert len(coded) == rows and force is None
+        img, coded = None, list(coded)
     if spoil is not None:
         coded = [spoil(rng, c) for c in coded]
     head = fs.lrit_file(b"", image=(n, cols, rows, 1), rice=(int(rng.integers(0, 65536)), J, 1),

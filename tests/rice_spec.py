@@ -4,13 +4,15 @@ and sample generators (test infrastructure).
 The reference tree ends at the VCDU, so this layer is specified here, from the CCSDS lossless data compression
 recommendation (CCSDS 121.0-B: the adaptive entropy coder with its zero-block, second-extension, split-sample and
 no-compression options and the unit-delay predictor with its mapper): `decode` is the serial statement, one block at a
-time, and the device must equal it sample for sample and status for status.  No libaec and no recorded downlink was at
-hand to hold it against; DESIGN.md lists what is unverified.
+time, and the device must equal it sample for sample and status for status.  tests/test_rice_libaec.py holds decoder
+and encoder against libaec 1.0.4 (tests/aec_ref.py); no recorded downlink was at hand, and DESIGN.md lists what stays
+open.
 
 One line = one byte string = one reference-sample interval, bits MSB first.  n bits per sample (1 .. 16), J in
 {8, 16, 32, 64} samples per block, S samples per line (1 .. 65535), B = ceil(S / J) blocks; the encoder pads the last
 block with repeats of the last sample and the decoder drops them.  The option ID has 3 bits for n <= 8, else 4."""
 import math
+import os
 
 import numpy as np
 
@@ -64,14 +66,20 @@ class _Bits:
         return [int(v) for v in vals]
 
 
-def decode(data, n, J, S):
+def decode(data, n, J, S, stats=None):
     """One line.  -> (samples (S,) int64, status): status 1 on a fault, the samples of the blocks decoded in front of it
-    kept and the rest 0."""
+    kept and the rest 0.  stats, a dict, counts the options met, under encode's keys, and under "long" the zero-block
+    codes of five blocks and more that are not the rest-of-segment code."""
     check_params(n, J, S)
     B, L, xmax = -(-S // J), id_bits(n), (1 << n) - 1
     out = np.zeros(B * J, np.int64)
     rd = _Bits(data)
     status, b, prev = 0, 0, 0
+
+    def count(key):
+        if stats is not None:
+            stats[key] = stats.get(key, 0) + 1
+
     try:
         while b < B:
             ref = b == 0
@@ -82,6 +90,7 @@ def decode(data, n, J, S):
                 second = rd.get(1)
                 r = rd.get(n) if ref else None
                 if second:
+                    count(SE)
                     dl = []
                     for g in rd.fs(J // 2):
                         beta = (math.isqrt(8 * g + 1) - 1) // 2
@@ -93,18 +102,24 @@ def decode(data, n, J, S):
                         dl = dl[1:]
                 else:
                     v = rd.fs(1)[0]
+                    count(ZERO)
                     if v == 4:
+                        count("rest")
                         nb = min(B, (b // SEGMENT + 1) * SEGMENT) - b
                     else:
                         nb = v + 1 if v < 4 else v
+                        if v > 4:
+                            count("long")
                     if b + nb > B:
                         raise _Fault
                     dl = [0] * (nb * J - (1 if ref else 0))
             elif ident == (1 << L) - 1:
+                count(RAW)
                 r = rd.get(n) if ref else None
                 dl = [rd.get(n) for _ in range(cnt)]
             else:
                 k = ident - 1
+                count(k)
                 r = rd.get(n) if ref else None
                 hi = rd.fs(cnt)
                 dl = [(h << k) | rd.get(k) for h in hi]
@@ -415,6 +430,24 @@ def se_long_lines():
 
 
 MAX_LINE = 1 << 20                # bytes: the device refuses longer lines (status 2, all zero)
+
+LIBAEC_LINES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rice_libaec_lines.npz")
+
+
+def libaec_groups():
+    """The lines of tests/golden/rice_libaec_lines.npz, encoded by libaec 1.0.4 (source 0) and by its libsz under option
+    mask 49 (source 1), not by `encode` (tests/golden/make_rice_golden.py) -> [(n, J, S, source, [bytes], samples
+    (lines, S) uint16)]."""
+    with np.load(LIBAEC_LINES) as z:
+        a = {k: z[k] for k in z.files}
+    data, off, out, at = a["data"].tobytes(), a["offsets"], [], 0
+    for g in range(len(a["n"])):
+        n, J, S, lo, hi = int(a["n"][g]), int(a["J"][g]), int(a["S"][g]), int(a["first"][g]), int(a["first"][g + 1])
+        lines = [data[int(off[i]):int(off[i + 1])] for i in range(lo, hi)]
+        out.append((n, J, S, int(a["source"][g]), lines, a["samples"][at:at + (hi - lo) * S].reshape(hi - lo, S)))
+        at += (hi - lo) * S
+    assert at == len(a["samples"]) and int(off[-1]) == len(data)
+    return out
 
 
 def pack(lines):

@@ -5,7 +5,8 @@ path behind lock, demultiplexer, packet and file assembler on one stream, the pe
 pieces that lie outside the bytes; calls tiled over up to 65 537 keys (image_spec.tile_call) with 63 to 524 289
 records -- full waves and tiles, second tiles, every kernel's grid cap and the stride behind it, a second round of the
 scan over the tiles --, two such calls on one handle, the device-pointer path with bounds four times the counts,
-capacities that cut in a later tile, and lines with long codes.
+capacities that cut in a later tile, lines with long codes, and image files whose lines libaec encoded
+(tests/golden/rice_libaec_lines.npz) against the samples they were made from.
 Every comparison is exact."""
 import functools
 
@@ -463,6 +464,65 @@ def test_pieces_outside_the_bytes_are_status_2(xa, mixed):
     im = xa.ImageDecoder()
     same(im.process(data[:cut], pieces, files, files_summary(xa, summ)), want)
     im.close()
+
+
+def test_image_files_of_lines_encoded_by_libaec(xa):
+    """An 8-bit and a 10-bit image file whose lines libaec 1.0.4 encoded (tests/golden/rice_libaec_lines.npz; columns no
+    multiple of the block, so the last block of every line is padded libaec's way), through the file assembler and this
+    stage: the host-buffer form, and the device form on a side stream.  The rows are the samples the lines were made
+    from; neither rs.encode nor rs.decode is in the chain."""
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(47)
+    groups = [g for g in rs.libaec_groups() if g[3] == 0]
+    items, images = [], {}
+    for key, bits in (((3, 8), 8), ((3, 10), 10)):
+        n, J, S, _, lines, samples = next(g for g in groups if g[0] == bits and g[2] > 1 and max(len(ln) for ln in g[4]) <= 8190)
+        assert S % J and len(lines) >= 20
+        _, data, cuts = isp.image_file(rng, n, J, S, len(lines), coded=lines)
+        items.append((key, data, cuts, 8190))
+        images[key] = samples
+    stream = isp.stream_of(rng, items)
+    fa, im = xa.FileAssembler(), xa.ImageDecoder()
+    data, pieces, files, fsum = fa.process(*fs.stage_input(stream))
+    assert len(files) == 2 and (files["flags"] == fs.BEGINS | fs.ENDS | fs.LENGTH_MATCH).all()
+    got = im.process(data, pieces, files, fsum)
+
+    def rows_are_the_fixture_s(out, lines):
+        assert len(lines) == sum(len(s) for s in images.values()) and not lines["status"].any()
+        rows = isp.Rows()
+        rows.add(out, lines, files)
+        for (v, a), samples in images.items():
+            x, status = rows.image(v, a, 0)
+            assert not status.any() and np.array_equal(x, samples), (v, a)
+
+    assert [int(x) for x in got[2]["rice"]] == [1, 1] and int(got[3]["images_completed"]) == 2 and int(got[3]["total_faults"]) == 0
+    rows_are_the_fixture_s(got[0], got[1])
+    # the device form on a side stream: the same bytes
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(np.atleast_1d(a)).view(np.uint8).reshape(-1).copy()).to(dev)
+    d_data, d_pieces, d_files, d_fsum = up(data), up(pieces), up(files), up(fsum)
+    nb = xa.images_max_bytes(files)
+    d_out, d_lines = (torch.full((k,), 0xA5, dtype=torch.uint8, device=dev) for k in (nb, len(pieces) * 32))
+    d_ifiles, d_sum = (torch.full((k,), 0xA5, dtype=torch.uint8, device=dev) for k in (len(files) * 48, 80))
+    im2 = xa.ImageDecoder()
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        im2.process_device(d_data.data_ptr(), len(data), d_pieces.data_ptr(), len(pieces), d_files.data_ptr(), len(files),
+                           d_fsum.data_ptr(), d_out.data_ptr(), nb, d_lines.data_ptr(), len(pieces), d_ifiles.data_ptr(),
+                           d_sum.data_ptr(), stream=s.cuda_stream)
+    s.synchronize()
+    isum = d_sum.cpu().numpy().view(xa.IMAGES_SUMMARY_DTYPE)[0]
+    assert isum.tobytes() == got[3].tobytes()
+    nl, nbytes = int(isum["lines"]), int(isum["bytes"])
+    lines = d_lines.cpu().numpy().view(xa.IMAGE_LINE_DTYPE)[:nl]
+    assert lines.tobytes() == got[1].tobytes() and d_ifiles.cpu().numpy().tobytes() == got[2].tobytes()
+    assert np.array_equal(d_out.cpu().numpy()[:nbytes], got[0])
+    rows_are_the_fixture_s(d_out.cpu().numpy()[:nbytes], lines)
+    for h in (fa, im, im2):
+        h.close()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
 
 
 # ---- calls beyond one tile ---------------------------------------------------------------------------------------------

@@ -4,7 +4,11 @@ damaged lines (status and kept prefix), descriptors outside the bytes, the strid
 descriptor arrays, the device-pointer path, and decode_file_lines on the file assembler's output; valid lines with long
 codes (uniform samples under a forced low k: zero runs across 64-bit windows, 4096-bit chunks and many chunks; codes
 that end on a chunk's edge and on the line's last bit; values at the limit; second-extension codes up to 2^23) and the
-line limit of 2^20 bytes.  Every comparison is exact."""
+line limit of 2^20 bytes; lines encoded by libaec and libsz, not by rice_spec (tests/golden/rice_libaec_lines.npz),
+against the samples they were made from, and damaged copies of them against the specification.  Every comparison is
+exact."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -243,6 +247,40 @@ def test_second_extension_with_large_codes(xa):
     assert not check(xa, [line for line, _, _ in lines], 16, 8, 8).any()
     out, _ = xa.RiceDecoder(16, 8, 8).decode(*rs.pack([line for line, _, _ in lines]))
     assert np.array_equal(out, np.stack([x for _, x, _ in lines]))
+
+
+# ---- lines that our own encoder did not make -----------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def libaec_groups():
+    """tests/golden/rice_libaec_lines.npz (shared, never changed): lines encoded by libaec 1.0.4 and by its libsz under
+    mask 49, with the samples they were made from.  Two fifths of them are other bytes than rs.encode's."""
+    return rs.libaec_groups()
+
+
+def test_lines_encoded_by_libaec(xa):
+    """libaec -> kernel, with neither rs.encode nor rs.decode in the chain: one batch per group of the fixture against
+    the fixture's samples.  Both ID lengths, n = 1 and 4, every J, lines whose last block libaec padded, S = 1, lines of
+    more than 64 blocks, the line of 4096 blocks."""
+    groups = libaec_groups()
+    assert len(groups) >= 11 and max(-(-S // J) for _, J, S, *_ in groups) == 4096
+    for n, J, S, source, lines, samples in groups:
+        out, status = xa.RiceDecoder(n, J, S).decode(*rs.pack(lines))
+        assert out.dtype == (np.uint8 if n <= 8 else np.uint16) and out.shape == samples.shape, (n, J, S, source)
+        assert not status.any(), (n, J, S, source, np.flatnonzero(status))
+        assert np.array_equal(out, samples), (n, J, S, source, np.flatnonzero((out != samples).any(1)))
+
+
+def test_libaec_lines_truncated_and_damaged(xa):
+    """Each group's lines in one batch with a truncated copy and a copy with one to three flipped bits of each: statuses
+    and kept prefixes against the specification."""
+    rng = np.random.default_rng(8)
+    faults = 0
+    for n, J, S, source, lines, samples in libaec_groups():
+        batch = list(lines) + [rs.truncate(rng, ln) for ln in lines] + [rs.flip(rng, ln, int(rng.integers(1, 4))) for ln in lines]
+        status = check(xa, batch, n, J, S)
+        assert not status[:len(lines)].any() and status[len(lines):2 * len(lines)].all(), (n, J, S)     # every cut line faults
+        faults += int(status.sum())
+    assert faults > 200
 
 
 def test_the_line_limit(xa):
