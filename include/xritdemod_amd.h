@@ -1200,6 +1200,148 @@ int xrit_product_composite(xrit_product *pr, const uint8_t *a, uint32_t pitch_a,
                            uint32_t rows, const uint8_t *table, uint8_t *rgb);
 
 /* ------------------------------------------------------------------------
+ * Image projection: an image in the instrument's scan geometry -- a canvas slot
+ * above all -- resampled onto a latitude / longitude grid on the device, so that
+ * it can be laid over a map, cut by coordinates or tiled (DESIGN.md section 24;
+ * tests/geo_spec.py is the specification, csrc/geo_rule.h the rule both the
+ * kernels and the host check are built from).  The geometry is the normalised
+ * geostationary projection of the CGMS LRIT/HRIT Global Specification, 4.4.3.2,
+ * with its constants as double literals: H = 42164.0, RPOL = 6356.5838, 0.993243,
+ * E2 = 0.00675701, K = 1.006803 (the squared ratio of the radii),
+ * R2D = 57.29577951308232.  The device equals the specification byte for byte:
+ * per pixel there is only + - * / sqrt floor in IEEE double, in the order written
+ * below, without FMA and without reciprocal or rsqrt substitution, and two
+ * arctangents stated as a fixed polynomial.
+ *
+ *  - navigation (xrit_geo_nav): cfac, lfac, coff, loff are the four integers of
+ *    the image navigation record (header type 2), either sign of the factors;
+ *    origin is the number the first column and line carry (CGMS: 1);
+ *    sub_lon_deg the sub-satellite longitude.
+ *  - output grid: any cylindrical grid, as four tables of doubles in device
+ *    memory that the handle holds.  Per output row i, with c_lat =
+ *    atan(0.993243 * tan(lat_i)) and rl = RPOL / sqrt(1 - E2 * cos^2(c_lat)):
+ *    A[i] = rl * cos(c_lat), B[i] = rl * sin(c_lat).  Per output column j:
+ *    C[j] = cos(lon_j - sub_lon), S[j] = sin(lon_j - sub_lon).
+ *    xrit_geo_set_grid makes them on the host with the C library (xrit_geo_grid_tables,
+ *    which needs no device) and uploads them:
+ *      XRIT_GEO_EQUIRECT  lon_j = lon0 + j * step_lon, lat_i = lat0 - i * step_lat
+ *      XRIT_GEO_MERCATOR  the same longitudes; lat_i = atan(sinh(y0 - i * step_y)),
+ *                         y0 and step_y being lat0_deg and step_lat_deg taken as
+ *                         Mercator ordinates in radians
+ *    columns and rows are 1 .. 16384.  xrit_geo_set_tables takes the caller's own.
+ *  - the map, for output pixel (i, j):
+ *      ac = A[i]*C[j];  r1 = H - ac;  r2 = -(A[i]*S[j]);  r3 = B[i]
+ *      vis = r1 > 0 and H*ac >= r2*r2 + K*(r3*r3)
+ *      u = -r2 / r1;    v = -r3 / sqrt(r1*r1 + r2*r2)
+ *      x = atan_small(u) * R2D;   y = atan_small(v) * R2D
+ *      fc = (double)(coff - origin) + x * ((double)cfac / 65536.0)
+ *      fl = (double)(loff - origin) + y * ((double)lfac / 65536.0)
+ *      qx = floor(fc*256.0 + 0.5);  qy = floor(fl*256.0 + 0.5)
+ *    (qx, qy) is the source position in 1/256 pixel.  atan_small(t) = t * P(t*t), P
+ *    the Horner form of sum_{k=0..9} (-1)^k / (2k+1) * z^k taken from k = 9 down,
+ *    its coefficients the double literals 1.0 / (2k+1).  Visible points have
+ *    |u|, |v| < 0.154; on |t| <= 0.2 the polynomial is within 1.2e-16 of atan.
+ *    (r1 > 0 holds for every real table, ac being at most 6378.2: it is there so
+ *    that a table holding +inf or 1e300 in C gives "off the disc" and not the
+ *    sub-satellite pixel.)  A pixel that is not vis, or whose fc*256 or fl*256 is not below 2^30 in
+ *    magnitude (NaN included), is off the disc: the map entry
+ *    {INT32_MIN, INT32_MIN}.  That test stands in front of every index.
+ *  - sampling: the source is an xrit_product_image (same layout and alignment
+ *    rules); value 0 is "no data".  The output has the source's sample width,
+ *    out_pitch bytes from row to row; bytes of a row behind columns * width are not
+ *    written.
+ *      XRIT_GEO_NEAREST   the sample at ((qx+128)>>8, (qy+128)>>8), 0 outside.
+ *      XRIT_GEO_BILINEAR  x0 = qx>>8, fx = qx&255, y0 = qy>>8, fy = qy&255; the taps
+ *                         (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) carry the
+ *                         integer weights (256-fx | fx) * (256-fy | fy).  Taps
+ *                         outside the image or of value 0 are left out.  W and V
+ *                         the sums of weights and of weight * value over the taps
+ *                         kept (64 bits): 0 for W = 0, else (2V + W) / (2W).  Data
+ *                         never becomes 0 and missing rows do not darken their
+ *                         neighbours: the thumbnail's rule.
+ *    The summary counts total, off_disc, outside (visible, none of the taps -- the
+ *    one of NEAREST, the four of BILINEAR whatever their weights -- inside the
+ *    image), no_data (a tap inside, W = 0; NEAREST: the sample is 0) and written.
+ *  - the handle owns the tables and the host-buffer forms' staging: no other state.
+ *    Calls on one handle are kept in order.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_geo xrit_geo;
+#define XRIT_GEO_EQUIRECT   0
+#define XRIT_GEO_MERCATOR   1
+#define XRIT_GEO_NEAREST    0
+#define XRIT_GEO_BILINEAR   1
+#define XRIT_GEO_MAX_DIM    16384
+typedef struct xrit_geo_nav {
+    int32_t cfac, lfac, coff, loff;
+    int32_t origin;                  /* the number of the first column and line: CGMS says 1 */
+    int32_t reserved;
+    double  sub_lon_deg;
+} xrit_geo_nav;                      /* 32 bytes */
+typedef struct xrit_geo_grid {
+    uint32_t kind;                   /* XRIT_GEO_EQUIRECT, XRIT_GEO_MERCATOR */
+    uint32_t columns, rows;
+    uint32_t reserved;
+    double   lon0_deg, lat0_deg, step_lon_deg, step_lat_deg;
+} xrit_geo_grid;                     /* 48 bytes */
+typedef struct xrit_geo_point {
+    int32_t qx, qy;                  /* 1/256 pixel; both INT32_MIN: off the disc */
+} xrit_geo_point;                    /* 8 bytes */
+typedef struct xrit_geo_summary {
+    uint64_t total;                  /* rows * columns of the grid */
+    uint64_t off_disc, outside, no_data, written;   /* they add up to total */
+    uint32_t columns, rows;          /* the grid's */
+    uint32_t width;                  /* bytes per sample */
+    uint32_t mode;
+} xrit_geo_summary;                  /* 56 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path". */
+int xrit_geo_create(xrit_geo **g, int device);
+int xrit_geo_destroy(xrit_geo *g);
+/* waits for the handle's last call; the tables stay */
+int xrit_geo_reset(xrit_geo *g);
+/* the four tables of a grid, made on the host with the C library: A, B of grid->rows doubles, C, S of grid->columns.
+ * Pure host code, never touches a device.  kind above 1, columns or rows outside 1 .. 16384: XRIT_E_INVALID. */
+int xrit_geo_grid_tables(const xrit_geo_grid *grid, double sub_lon_deg, double *A, double *B, double *C, double *S);
+/* xrit_geo_grid_tables, uploaded.  Waits for the handle's last call and for the upload: once per geometry. */
+int xrit_geo_set_grid(xrit_geo *g, const xrit_geo_grid *grid, double sub_lon_deg);
+/* the caller's own tables (host memory), whatever they hold; waits likewise */
+int xrit_geo_set_tables(xrit_geo *g, uint32_t columns, uint32_t rows, const double *A, const double *B, const double *C, const double *S);
+/* the tables in effect, read back from the device (waits); *columns, *rows: the grid's.  A table pointer may be NULL.
+ * No tables set: XRIT_E_INVALID. */
+int xrit_geo_tables(xrit_geo *g, uint32_t *columns, uint32_t *rows, double *A, double *B, double *C, double *S);
+/* The calls below are asynchronous on `stream` (0: the null stream) with no host synchronisation.  No tables set, a mode
+ * other than the two, an image outside the bounds of "Image products", out_pitch below columns * width or odd for
+ * two-byte samples (d_out likewise), a NULL pointer, d_map not 8-byte aligned, d_summary not 8-byte aligned:
+ * XRIT_E_INVALID, nothing queued, nothing written. */
+/* the map of the grid: rows x columns entries, tight */
+int xrit_geo_map_device(xrit_geo *g, const xrit_geo_nav *nav, xrit_geo_point *d_map, void *stream);
+/* a map applied to an image: one geometry, many channels.  The entries may hold anything; nothing outside the image is
+ * read. */
+int xrit_geo_resample_device(xrit_geo *g, const xrit_product_image *image, const xrit_geo_point *d_map, uint32_t mode, uint8_t *d_out,
+                             uint32_t out_pitch, xrit_geo_summary *d_summary, void *stream);
+/* fused: the map is never stored; the output and the summary are those of map-then-resample byte for byte.  It may be
+ * queued directly behind xrit_canvas_process_device on a slot's xrit_canvas_pixels_device. */
+int xrit_geo_project_device(xrit_geo *g, const xrit_geo_nav *nav, const xrit_product_image *image, uint32_t mode, uint8_t *d_out,
+                            uint32_t out_pitch, xrit_geo_summary *d_summary, void *stream);
+/* host buffers (one upload, one download): image->d_pixels, out and summary are host memory */
+int xrit_geo_project(xrit_geo *g, const xrit_geo_nav *nav, const xrit_product_image *image, uint32_t mode, uint8_t *out, uint32_t out_pitch,
+                     xrit_geo_summary *summary);
+/* the image in device memory where it lies, out and summary host memory.  Runs on the handle's own stream and waits. */
+int xrit_geo_project_resident(xrit_geo *g, const xrit_geo_nav *nav, const xrit_product_image *image, uint32_t mode, uint8_t *out,
+                              uint32_t out_pitch, xrit_geo_summary *summary);
+/* Host helpers: plain C++, never touch a device. */
+/* A file's header records (the primary header first), walked as the file stage walks them for the first record of type 2
+ * and length 51: 32 bytes of projection name, then big-endian int32 CFAC, LFAC, COFF, LOFF.  The name must begin
+ * "GEOS(" or "geos("; sub_lon_deg is the number between the parentheses; origin = 1.  Anything else (no such record, a
+ * truncated header, another name, no number): XRIT_E_INVALID.  UNVERIFIED, our reading of the CGMS document, no recorded
+ * downlink at hand: that layout, and that the name carries the longitude as a plain decimal number. */
+int xrit_geo_parse_navigation(const uint8_t *header_bytes, size_t n, xrit_geo_nav *nav);
+/* the inverse of the map (CGMS 4.4.3.2), with the C library, for choosing a grid: the longitude and latitude of the
+ * point that (column, line), numbered from nav->origin, looks at.  Returns 0, 1 when it looks at space (nothing
+ * written), or XRIT_E_INVALID. */
+int xrit_geo_pixel_to_lonlat(const xrit_geo_nav *nav, double column, double line, double *lon_deg, double *lat_deg);
+
+/* ------------------------------------------------------------------------
  * Carrier acquisition: a stage IN FRONT of the chain that finds a large carrier
  * offset and takes it out on the device (DESIGN.md section 21;
  * tests/acquire_spec.py is the specification).  The reference has no such

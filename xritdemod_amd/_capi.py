@@ -164,6 +164,20 @@ _SIGNATURES = {
     "xrit_product_process_resident": (C.c_int, [_vp] * 9),
     "xrit_product_composite_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "xrit_product_composite": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "xrit_geo_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_geo_destroy": (C.c_int, [_vp]),
+    "xrit_geo_reset": (C.c_int, [_vp]),
+    "xrit_geo_grid_tables": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "xrit_geo_set_grid": (C.c_int, [_vp, _vp, C.c_double]),
+    "xrit_geo_set_tables": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "xrit_geo_tables": (C.c_int, [_vp] * 7),
+    "xrit_geo_map_device": (C.c_int, [_vp] * 4),
+    "xrit_geo_resample_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "xrit_geo_project_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "xrit_geo_project": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    "xrit_geo_project_resident": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    "xrit_geo_parse_navigation": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "xrit_geo_pixel_to_lonlat": (C.c_int, [_vp, C.c_double, C.c_double, _vp, _vp]),
     "xrit_acquire_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int]),
     "xrit_acquire_destroy": (C.c_int, [_vp]),
     "xrit_acquire_reset": (C.c_int, [_vp]),
@@ -1741,6 +1755,157 @@ class ImageProduct(_Handle):
     def reset(self):
         """Waits for the last call; there is no state."""
         _check(lib().xrit_product_reset(self._h))
+
+
+# ---- image projection (DESIGN.md section 24) ---------------------------------------------------------------------------
+GEO_EQUIRECT, GEO_MERCATOR = 0, 1
+GEO_NEAREST, GEO_BILINEAR = 0, 1
+GEO_KINDS = ("equirect", "mercator")
+GEO_MODES = ("nearest", "bilinear")
+GEO_MAX_DIM = 16384
+GEO_OFF = -(1 << 31)
+# xrit_geo_nav, xrit_geo_grid, xrit_geo_point, xrit_geo_summary
+GEO_NAV_DTYPE = np.dtype([("cfac", np.int32), ("lfac", np.int32), ("coff", np.int32), ("loff", np.int32), ("origin", np.int32),
+                          ("reserved", np.int32), ("sub_lon_deg", np.float64)])
+assert GEO_NAV_DTYPE.itemsize == 32
+GEO_GRID_DTYPE = np.dtype([("kind", np.uint32), ("columns", np.uint32), ("rows", np.uint32), ("reserved", np.uint32), ("lon0_deg", np.float64),
+                           ("lat0_deg", np.float64), ("step_lon_deg", np.float64), ("step_lat_deg", np.float64)])
+assert GEO_GRID_DTYPE.itemsize == 48
+GEO_POINT_DTYPE = np.dtype([("qx", np.int32), ("qy", np.int32)])
+assert GEO_POINT_DTYPE.itemsize == 8
+GEO_SUMMARY_DTYPE = np.dtype([(k, np.uint64) for k in ("total", "off_disc", "outside", "no_data", "written")] +
+                             [(k, np.uint32) for k in ("columns", "rows", "width", "mode")])
+assert GEO_SUMMARY_DTYPE.itemsize == 56
+
+
+def _geo_mode(mode):
+    return GEO_MODES.index(mode) if isinstance(mode, str) else int(mode)
+
+
+def geo_nav(cfac, lfac, coff, loff, origin=1, sub_lon_deg=0.0):
+    """One xrit_geo_nav record (a GEO_NAV_DTYPE array of one element)."""
+    nav = np.zeros(1, GEO_NAV_DTYPE)
+    nav[0] = (cfac, lfac, coff, loff, origin, 0, sub_lon_deg)
+    return nav
+
+
+def _geo_nav_arg(nav):
+    if isinstance(nav, dict):
+        return geo_nav(nav["cfac"], nav["lfac"], nav["coff"], nav["loff"], nav.get("origin", 1), nav.get("sub_lon", nav.get("sub_lon_deg", 0.0)))
+    return np.ascontiguousarray(np.asarray(nav, GEO_NAV_DTYPE).reshape(1))
+
+
+def _geo_grid_arg(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg):
+    grid = np.zeros(1, GEO_GRID_DTYPE)
+    grid[0] = (GEO_KINDS.index(kind) if isinstance(kind, str) else int(kind), columns, rows, 0, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg)
+    return grid
+
+
+def geo_grid_tables(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg, sub_lon_deg):
+    """The library's tables of a grid, made on the host (no device): (A, B of `rows` float64, C, S of `columns`)."""
+    grid = _geo_grid_arg(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg)
+    n_r, n_c = max(int(rows), 0), max(int(columns), 0)
+    A, B, Cc, S = np.zeros(n_r), np.zeros(n_r), np.zeros(n_c), np.zeros(n_c)
+    _check(lib().xrit_geo_grid_tables(_p(grid), float(sub_lon_deg), _p(A), _p(B), _p(Cc), _p(S)))
+    return A, B, Cc, S
+
+
+def geo_parse_navigation(header):
+    """The navigation record (type 2) of a file's header bytes -> a GEO_NAV_DTYPE record; XritError -1 without one."""
+    b = np.frombuffer(bytes(header), np.uint8)
+    nav = np.zeros(1, GEO_NAV_DTYPE)
+    _check(lib().xrit_geo_parse_navigation(_p(b) if len(b) else None, len(b), _p(nav)))
+    return nav[0]
+
+
+def geo_pixel_to_lonlat(nav, column, line):
+    """The inverse of the map: (lon_deg, lat_deg) of what (column, line) looks at, None for space."""
+    nav = _geo_nav_arg(nav)
+    lon, lat = C.c_double(), C.c_double()
+    rc = lib().xrit_geo_pixel_to_lonlat(_p(nav), float(column), float(line), C.byref(lon), C.byref(lat))
+    if rc == 1:
+        return None
+    _check(rc)
+    return lon.value, lat.value
+
+
+class ImageProjector(_Handle):
+    """An image in the instrument's scan geometry resampled onto a latitude / longitude grid on the device.  The handle
+    holds the grid as four tables (set_grid, set_tables); project is the fused call, map + resample the pair for one
+    geometry with many channels.  tests/geo_spec.py is the specification."""
+    _destroy = "xrit_geo_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        _check(lib().xrit_geo_create(C.byref(self._h), device))
+        self.columns = self.rows = 0
+
+    def set_grid(self, kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg, sub_lon_deg):
+        grid = _geo_grid_arg(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg)
+        _check(lib().xrit_geo_set_grid(self._h, _p(grid), float(sub_lon_deg)))
+        self.columns, self.rows = int(columns), int(rows)
+
+    def set_tables(self, A, B, Cc, S):
+        A, B, Cc, S = (np.ascontiguousarray(x, np.float64).reshape(-1) for x in (A, B, Cc, S))
+        if len(A) != len(B) or len(Cc) != len(S):
+            raise ValueError("A and B per row, C and S per column")
+        _check(lib().xrit_geo_set_tables(self._h, len(Cc), len(A), _p(A), _p(B), _p(Cc), _p(S)))
+        self.columns, self.rows = len(Cc), len(A)
+
+    def tables(self):
+        """The tables in effect, read back from the device: (A, B, C, S)."""
+        c, r = C.c_uint32(), C.c_uint32()
+        _check(lib().xrit_geo_tables(self._h, C.byref(c), C.byref(r), None, None, None, None))
+        A, B, Cc, S = np.zeros(r.value), np.zeros(r.value), np.zeros(c.value), np.zeros(c.value)
+        _check(lib().xrit_geo_tables(self._h, None, None, _p(A), _p(B), _p(Cc), _p(S)))
+        return A, B, Cc, S
+
+    def _image(self, pixels_ptr, columns, rows, pitch, bits):
+        image = np.zeros(1, PRODUCT_IMAGE_DTYPE)
+        image[0] = (pixels_ptr or 0, columns, rows, pitch, bits)
+        return image
+
+    def map_device(self, nav, d_map_ptr, stream=None):
+        """rows x columns GEO_POINT_DTYPE entries to device memory.  Asynchronous on stream."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_geo_map_device(self._h, _p(_geo_nav_arg(nav)), v(d_map_ptr), v(stream)))
+
+    def resample_device(self, d_pixels_ptr, columns, rows, pitch, bits, d_map_ptr, mode, d_out_ptr, out_pitch, d_summary_ptr, stream=None):
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_geo_resample_device(self._h, _p(self._image(d_pixels_ptr, columns, rows, pitch, bits)), v(d_map_ptr), _geo_mode(mode),
+                                              v(d_out_ptr), out_pitch, v(d_summary_ptr), v(stream)))
+
+    def project_device(self, nav, d_pixels_ptr, columns, rows, pitch, bits, mode, d_out_ptr, out_pitch, d_summary_ptr, stream=None):
+        """Fused; may be queued behind ImageCanvas.process_device on a slot's pixels_device().  Asynchronous on stream."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_geo_project_device(self._h, _p(_geo_nav_arg(nav)), _p(self._image(d_pixels_ptr, columns, rows, pitch, bits)),
+                                             _geo_mode(mode), v(d_out_ptr), out_pitch, v(d_summary_ptr), v(stream)))
+
+    def _to_host(self, fn, nav, pixels_ptr, columns, rows, pitch, bits, mode):
+        out = np.zeros((self.rows, self.columns), np.uint8 if bits <= 8 else np.uint16)
+        summary = np.zeros(1, GEO_SUMMARY_DTYPE)
+        _check(fn(self._h, _p(_geo_nav_arg(nav)), _p(self._image(pixels_ptr, columns, rows, pitch, bits)), _geo_mode(mode), _p(out),
+                  self.columns * out.itemsize, _p(summary)))
+        return out, summary[0]
+
+    def project(self, nav, image, bits, mode="bilinear"):
+        """image: 2-D, uint8 for bits <= 8, uint16 above (its row stride is the pitch) -> (the projected image, a
+        GEO_SUMMARY_DTYPE record)."""
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != (np.uint8 if bits <= 8 else np.uint16) or image.strides[1] != image.itemsize or image.strides[0] < 0:
+            raise ValueError("a 2-D image of uint8 (bits <= 8) or uint16 samples, contiguous along its rows")
+        rows, columns = image.shape
+        return self._to_host(lib().xrit_geo_project, nav, image.ctypes.data, columns, rows,
+                             image.strides[0] if rows > 1 else columns * image.itemsize, bits, mode)
+
+    def project_resident(self, nav, d_pixels_ptr, columns, rows, pitch, bits, mode="bilinear"):
+        """As project, on an image that lies in device memory (ImageCanvas.pixels_device, once the canvas's last call has
+        finished)."""
+        return self._to_host(lib().xrit_geo_project_resident, nav, d_pixels_ptr, columns, rows, pitch, bits, mode)
+
+    def reset(self):
+        """Waits for the last call; the tables stay."""
+        _check(lib().xrit_geo_reset(self._h))
 
 
 # ---- carrier acquisition (DESIGN.md section 21) -------------------------------------------------------------------------

@@ -552,6 +552,17 @@ int launch_product(const xrit_product_image &im, const xrit_product_params &pp, 
                    xrit_product_summary *summary, hipStream_t s);
 int launch_product_composite(const unsigned char *a, uint32_t pitch_a, const unsigned char *b, uint32_t pitch_b, uint32_t columns,
                              uint32_t rows, const unsigned char *table, unsigned char *rgb, hipStream_t s);
+// projection stage (geo.hip; geo_rule.h is the rule per pixel): the grid's tables in device memory (A, B: rows doubles;
+// C, S: columns), then the three calls.  launch_geo_resample and launch_geo_project zero the summary first.
+struct GeoTables {
+    const double *A, *B, *C, *S;
+    uint32_t columns, rows;
+};
+int launch_geo_map(const GeoTables &t, const xrit_geo_nav &nav, xrit_geo_point *map, hipStream_t s);
+int launch_geo_resample(const GeoTables &t, const xrit_product_image &im, const xrit_geo_point *map, uint32_t mode, unsigned char *out,
+                        uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
+int launch_geo_project(const GeoTables &t, const xrit_geo_nav &nav, const xrit_product_image &im, uint32_t mode, unsigned char *out,
+                       uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
 // carrier acquisition (acquire.hip; acquire_host.h has the sizes): the handle's state is one xrit_acquire_state; the scratch
 // of an estimate of M segments
 struct AcquireScratch {

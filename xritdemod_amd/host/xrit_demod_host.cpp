@@ -100,6 +100,11 @@ struct Options {
     bool products = false;         // --products: with --canvas, every canvas written also as DIR/<name>.view.pgm and .thumb.pgm (xrit_product_*)
     bool product_flags = false;    // --product-tone or --product-factor was given
     xrit_product_params product{XRIT_TONE_EQUALISE, 0, 10000, 8};      // --product-tone linear|equalise|stretch[:LO:HI], --product-factor F
+    bool project = false;          // --project: with --canvas, every canvas written also on a latitude / longitude grid, DIR/<name>.geo.pgm (xrit_geo_*)
+    bool project_flags = false;    // --project-grid or --project-mode was given
+    bool project_grid_given = false;   // --project-grid LON0:LAT0:STEP:COLUMNS:ROWS; otherwise the disc's bounding box at 0.05 degrees
+    xrit_geo_grid project_grid{XRIT_GEO_EQUIRECT, 0, 0, 0, 0.0, 0.0, 0.05, 0.05};
+    uint32_t project_mode = XRIT_GEO_BILINEAR;     // --project-mode nearest|bilinear
     bool stream_sync = false;      // --stream-sync: the stream frame synchroniser (xrit_framer_*) in front of the frame decoder
     int flywheel = 0;              // --flywheel [N]: the frame lock (xrit_lock_*) in place of framer and decoder, flywheelRecheck = N
     bool tune = false;             // --tune HZ: the input derotated by tune_hz in front of the chain (xrit_acquire_*)
@@ -152,6 +157,14 @@ void usage()
                  "                                 stretch between the percentiles LO and HI per myriad (default 200:9800), value 0 being \"no data\" --\n"
                  "                                 and written as DIR/<name>.view.pgm, and reduced F times (1..64, default 8; pixels without data\n"
                  "                                 left out of the means) as DIR/<name>.thumb.pgm; only these two are downloaded)\n"
+                 "         [--project [--project-grid LON0:LAT0:STEP:COLUMNS:ROWS] [--project-mode nearest|bilinear]]   (with --canvas: every canvas\n"
+                 "                                 that is written is also resampled on the GPU onto a latitude / longitude grid, from the image\n"
+                 "                                 navigation record (type 2) of its segment file at line 0, column 0, and written as\n"
+                 "                                 DIR/<name>.geo.pgm: column j is LON0 + j * STEP degrees east, row i LAT0 - i * STEP degrees north\n"
+                 "                                 (COLUMNS, ROWS 1..16384; default: the earth's disc around the sub-satellite point at 0.05\n"
+                 "                                 degrees); bilinear (default; pixels without data left out of the means) or nearest.  A canvas\n"
+                 "                                 without such a record is skipped with a line on stderr.  With --products the projected image\n"
+                 "                                 is toned too: DIR/<name>.geo.view.pgm)\n"
                  "         [--tune HZ]   (a carrier offset of HZ is taken out on the GPU in front of the chain; cf32, s16 or s8 input, one GPU)\n"
                  "         [--acquire [--acquire-presum R]]   (the carrier offset is estimated on the first input of at least 65536 * R samples --\n"
                  "                                 further blocks are read ahead if a block is shorter --, printed to stderr with the strength of\n"
@@ -191,6 +204,22 @@ bool parse_tone(const char *v, xrit_product_params &p)
         }
     }
     std::fprintf(stderr, "--product-tone %s: linear, equalise, stretch or stretch:LO:HI with 0 <= LO < HI <= 10000\n", v);
+    return false;
+}
+
+// --project-grid LON0:LAT0:STEP:COLUMNS:ROWS
+bool parse_project_grid(const char *v, xrit_geo_grid &g)
+{
+    double lon0 = 0, lat0 = 0, step = 0;
+    long columns = 0, rows = 0;
+    int used = 0;
+    if (std::sscanf(v, "%lf:%lf:%lf:%ld:%ld%n", &lon0, &lat0, &step, &columns, &rows, &used) == 5 && v[used] == '\0' && step > 0.0 &&
+        lon0 >= -360.0 && lon0 <= 360.0 && lat0 >= -90.0 && lat0 <= 90.0 && columns >= 1 && columns <= XRIT_GEO_MAX_DIM && rows >= 1 &&
+        rows <= XRIT_GEO_MAX_DIM) {
+        g = xrit_geo_grid{XRIT_GEO_EQUIRECT, (uint32_t)columns, (uint32_t)rows, 0, lon0, lat0, step, step};
+        return true;
+    }
+    std::fprintf(stderr, "--project-grid %s: LON0:LAT0:STEP:COLUMNS:ROWS with STEP > 0, COLUMNS and ROWS 1..%d\n", v, XRIT_GEO_MAX_DIM);
     return false;
 }
 
@@ -239,6 +268,18 @@ bool parse(int argc, char **argv, Options &o)
             }
             o.product.factor = (uint32_t)f;
             o.product_flags = true;
+        }
+        else if (a == "--project") o.project = true;
+        else if (a == "--project-grid") {
+            if (!(v = need("--project-grid")) || !parse_project_grid(v, o.project_grid)) return false;
+            o.project_flags = o.project_grid_given = true;
+        }
+        else if (a == "--project-mode") {
+            if (!(v = need("--project-mode"))) return false;
+            if (std::string(v) == "nearest") o.project_mode = XRIT_GEO_NEAREST;
+            else if (std::string(v) == "bilinear") o.project_mode = XRIT_GEO_BILINEAR;
+            else { std::fprintf(stderr, "--project-mode %s: nearest or bilinear\n", v); return false; }
+            o.project_flags = true;
         }
         else if (a == "--stream-sync") o.stream_sync = true;
         else if (a == "--tune") { if (!(v = need("--tune"))) return false; o.tune = true; o.tune_hz = std::atof(v); }
@@ -301,6 +342,10 @@ bool parse(int argc, char **argv, Options &o)
     }
     if ((o.products && !o.canvas) || (o.product_flags && !o.products)) {
         std::fprintf(stderr, "--products needs --canvas; --product-tone and --product-factor need --products\n");
+        return false;
+    }
+    if ((o.project && !o.canvas) || (o.project_flags && !o.project)) {
+        std::fprintf(stderr, "--project needs --canvas; --project-grid and --project-mode need --project\n");
         return false;
     }
     if ((o.tune || o.acquire) && (o.gpus > 1 || o.format == "u8" || o.acquire_presum < 1 || o.acquire_presum > 64)) {
@@ -429,6 +474,17 @@ struct FrameDecode {
     xrit_product *pr = nullptr;
     std::vector<uint8_t> pr_tone, pr_small;
     size_t products_written = 0, product_fallbacks = 0;
+    bool project = false;           // --project (set it, project_grid, project_grid_given and project_mode before open())
+    bool project_grid_given = false;
+    xrit_geo_grid project_grid{};
+    uint32_t project_mode = XRIT_GEO_BILINEAR;
+    xrit_geo *geo = nullptr;
+    struct SlotNav { int state = 0; xrit_geo_nav nav{}; };      // 0: no file at (0, 0) yet; 1: its record parsed; 2: it did not
+    std::vector<SlotNav> geo_nav;   // per canvas slot
+    bool geo_grid_set = false;
+    double geo_grid_lon = 0.0;      // the sub-satellite longitude the tables in effect were made for
+    std::vector<uint8_t> geo_out, geo_tone;
+    size_t projected = 0, projections_skipped = 0;
     std::vector<xrit_sync_hit> raw_hits;
     std::vector<uint8_t> vcdu, wire;
     std::vector<xrit_frame_stats> records;
@@ -511,6 +567,11 @@ struct FrameDecode {
                     std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
                     return false;
                 }
+                if (project && xrit_geo_create(&geo, device) != XRIT_OK) {
+                    std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                    return false;
+                }
+                geo_nav.assign(canvas_slots, SlotNav{});
             }
         }
         return true;
@@ -736,13 +797,29 @@ struct FrameDecode {
                                 &f_summary, img.data(), im_summary.bytes, im_lines.data(), im_summary.lines, im_files.data(), &im_summary,
                                 cv_files.data(), cv_slots.data(), &cv_summary) != XRIT_OK)
             return fail("canvas");
+        if (geo) note_navigation();
         for (unsigned s = 0; cv_summary.completed && s < canvas_slots; ++s) {
             if (!cv_slots[s].in_use || !cv_slots[s].complete) continue;
             if (!write_canvas(s, false)) return false;
             if (xrit_canvas_release(cv, s) != XRIT_OK) return fail("canvas release");
             cv_slots[s] = xrit_canvas_slot{};
+            if (geo) geo_nav[s] = SlotNav{};
         }
         return true;
+    }
+    // --project: a canvas's navigation is that of its segment file at line 0, column 0 -- the record in that file's first piece
+    void note_navigation()
+    {
+        for (size_t i = 0; i < f_summary.files; ++i) {
+            const xrit_file_record &r = f_recs[i];
+            const xrit_canvas_file &c = cv_files[i];
+            if (!(r.flags & XRIT_FILE_BEGINS) || c.reason != XRIT_CANVAS_PLACED || c.slot < 0 || (unsigned)c.slot >= canvas_slots ||
+                c.start_line || c.start_column || !r.n_pieces)
+                continue;
+            const xrit_file_piece &first = f_pieces[r.first_piece];
+            SlotNav &n = geo_nav[(unsigned)c.slot];
+            n.state = xrit_geo_parse_navigation(f_bytes.data() + first.offset, first.length, &n.nav) == XRIT_OK ? 1 : 2;
+        }
     }
     // one canvas as binary PGM: DIR/<the annotation text reduced to [A-Za-z0-9._-]>.pgm, or vc<vcid>_img<image_id>_<born_call>
     bool write_canvas(unsigned s, bool partial)
@@ -773,7 +850,68 @@ struct FrameDecode {
         std::fclose(f);
         if (!ok) { std::perror(path.c_str()); return false; }
         ++canvases_written;
-        return !pr || write_products(s, info, file_dir + "/" + name + (partial ? ".partial" : ""));
+        const std::string stem = file_dir + "/" + name + (partial ? ".partial" : "");
+        return (!pr || write_products(s, info, stem)) && (!geo || write_projection(s, info, stem));
+    }
+    bool write_pgm(const std::string &path, const uint8_t *pixels, uint32_t columns, uint32_t rows, uint32_t bits)
+    {
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::perror(path.c_str()); return false; }
+        const size_t width = bits <= 8 ? 1 : 2, row_bytes = (size_t)columns * width;
+        bool ok = std::fprintf(f, "P5\n%u %u\n%u\n", columns, rows, (1u << bits) - 1u) > 0;
+        cv_row.resize(row_bytes);
+        for (size_t r = 0; ok && r < rows; ++r) {
+            const uint8_t *src = pixels + r * row_bytes;
+            if (width == 2) {           // little-endian samples, PGM wants the high byte first
+                for (size_t i = 0; i < row_bytes; i += 2) { cv_row[i] = src[i + 1]; cv_row[i + 1] = src[i]; }
+                src = cv_row.data();
+            }
+            ok = std::fwrite(src, 1, row_bytes, f) == row_bytes;
+        }
+        std::fclose(f);
+        if (!ok) std::perror(path.c_str());
+        return ok;
+    }
+    // --project: the slot's pixels resampled where they lie; the projected image is what is downloaded
+    bool write_projection(unsigned s, const xrit_canvas_slot &info, const std::string &stem)
+    {
+        if (!info.max_column || !info.max_row) return true;
+        const SlotNav &n = geo_nav[s];
+        if (n.state != 1) {
+            std::fprintf(stderr, "project: %s: %s, not projected\n", stem.c_str(),
+                         n.state ? "the image navigation record of its file at line 0, column 0 does not parse" : "no segment file at line 0, column 0");
+            ++projections_skipped;
+            return true;
+        }
+        if (!geo_grid_set || geo_grid_lon != n.nav.sub_lon_deg) {           // once per geometry
+            xrit_geo_grid g = project_grid;
+            if (!project_grid_given) {      // the earth's disc as the satellite sees it: 81.3 degrees either way
+                g.columns = g.rows = 3253;
+                g.lon0_deg = n.nav.sub_lon_deg - 81.3;
+                g.lat0_deg = 81.3;
+            }
+            if (xrit_geo_set_grid(geo, &g, n.nav.sub_lon_deg) != XRIT_OK) return fail("project grid");
+            project_grid = g;
+            geo_grid_set = true;
+            geo_grid_lon = n.nav.sub_lon_deg;
+        }
+        xrit_product_image image{nullptr, info.max_column, info.max_row, info.pitch, info.bits};
+        if (xrit_canvas_pixels_device(cv, s, &image.d_pixels) != XRIT_OK) return fail("canvas pixels");
+        const uint32_t columns = project_grid.columns, rows = project_grid.rows, width = info.bits <= 8 ? 1 : 2;
+        geo_out.resize((size_t)columns * rows * width);
+        xrit_geo_summary summary{};
+        if (xrit_geo_project_resident(geo, &n.nav, &image, project_mode, geo_out.data(), columns * width, &summary) != XRIT_OK)
+            return fail("project");
+        if (!write_pgm(stem + ".geo.pgm", geo_out.data(), columns, rows, info.bits)) return false;
+        ++projected;
+        if (!pr) return true;
+        // --products: the projected image toned like the canvas
+        const xrit_product_image flat{geo_out.data(), columns, rows, columns * width, info.bits};
+        geo_tone.resize((size_t)columns * rows);
+        xrit_product_summary toned{};
+        if (xrit_product_process(pr, &flat, &product, nullptr, nullptr, nullptr, geo_tone.data(), nullptr, &toned) != XRIT_OK)
+            return fail("products of the projection");
+        return write_pgm(stem + ".geo.view.pgm", geo_tone.data(), columns, rows, 8);
     }
     // --products: the slot's pixels toned and reduced where they lie; the two products are what is downloaded
     bool write_products(unsigned s, const xrit_canvas_slot &info, const std::string &stem)
@@ -880,6 +1018,12 @@ struct FrameDecode {
                                  product.factor, product_fallbacks);
                     xrit_product_destroy(pr);
                     pr = nullptr;
+                }
+                if (geo) {
+                    std::fprintf(stderr, "project: %zu canvases projected onto %u x %u (%s), %zu skipped\n", projected, project_grid.columns,
+                                 project_grid.rows, project_mode == XRIT_GEO_NEAREST ? "nearest" : "bilinear", projections_skipped);
+                    xrit_geo_destroy(geo);
+                    geo = nullptr;
                 }
                 xrit_canvas_destroy(cv);
                 cv = nullptr;
@@ -1252,6 +1396,10 @@ int main(int argc, char **argv)
     decode.canvas_bytes = o.canvas_mib << 20;
     decode.products = o.products;
     decode.product = o.product;
+    decode.project = o.project;
+    decode.project_grid = o.project_grid;
+    decode.project_grid_given = o.project_grid_given;
+    decode.project_mode = o.project_mode;
     if ((!o.decode.empty() || !o.channels.empty() || !o.decoder_stats.empty() || !o.packets.empty() || !o.files.empty()) &&
         !decode.open(o.decode, o.channels, o.decoder_stats, o.packets, o.files, o.files_decompress, o.mode == "hrit", o.device, o.stream_sync, o.flywheel)) {
         decode.close(); std::fclose(in); xrit_demod_destroy(chain);
