@@ -1191,6 +1191,11 @@ int xrit_product_process(xrit_product *pr, const xrit_product_image *image, cons
 int xrit_product_process_resident(xrit_product *pr, const xrit_product_image *image, const xrit_product_params *params,
                                   const uint8_t *table_in, uint32_t *hist, uint8_t *lut, uint8_t *tone, uint8_t *small,
                                   xrit_product_summary *summary);
+/* Where the handle's last xrit_product_process or xrit_product_process_resident left the toned image and the thumbnail in
+ * device memory (tight rows; NULL for one that call did not make, and before any such call): for a stage that goes on
+ * with them there, xrit_jpeg_encode_resident above all.  They stay until the handle's next host-buffer call.  Nothing is
+ * queued and nothing waited for. */
+int xrit_product_outputs_device(xrit_product *pr, const uint8_t **d_tone, const uint8_t **d_small);
 /* d_a, d_b: 8-bit images of columns x rows (>= 1, columns * rows <= 2^31), pitch_a, pitch_b >= columns; d_table
  * 256 * 256 * 3 bytes; d_rgb rows x columns x 3 bytes.  Asynchronous on `stream`, no host synchronisation. */
 int xrit_product_composite_device(xrit_product *pr, const uint8_t *d_a, uint32_t pitch_a, const uint8_t *d_b, uint32_t pitch_b,
@@ -1340,6 +1345,100 @@ int xrit_geo_parse_navigation(const uint8_t *header_bytes, size_t n, xrit_geo_na
  * point that (column, line), numbered from nav->origin, looks at.  Returns 0, 1 when it looks at space (nothing
  * written), or XRIT_E_INVALID. */
 int xrit_geo_pixel_to_lonlat(const xrit_geo_nav *nav, double column, double line, double *lon_deg, double *lat_deg);
+
+/* ------------------------------------------------------------------------
+ * JPEG: an 8-bit image in device memory -- the product stage's toned image,
+ * its thumbnail, its composite, a projected image -- becomes a complete
+ * baseline JFIF file in device memory, so that only the file's bytes cross to
+ * the host (tests/jpeg_spec.py is the specification).
+ * The file is the one libjpeg writes for the same pixels and parameters: the
+ * device equals the specification byte for byte, and so does Pillow's libjpeg.
+ *
+ *  - input: `rows` rows of `columns` pixels, `pitch` bytes from row to row.  One
+ *    component: one byte per pixel, pitch >= columns.  Three: interleaved R, G, B
+ *    as xrit_product_composite_device writes them, pitch >= 3 * columns.
+ *    1 <= columns, rows <= 65535; no alignment is asked of d_pixels or pitch;
+ *    bytes of a row behind the image are never read.  (The bits field of
+ *    xrit_product_image is ignored.)
+ *  - the stage takes at most XRIT_JPEG_MAX_BLOCKS (2^22) 8 x 8 blocks of all
+ *    components in one call: ceil(columns / 8) * ceil(rows / 8) * components.  A
+ *    larger shape is XRIT_E_INVALID and xrit_jpeg_bound is 0 for it.  (The scratch
+ *    holds 400 bytes per block; inside the stage bit and byte offsets are 64 and
+ *    32 bits wide, and 2^22 blocks stay below 2^32 bytes at 208 bytes a block.)
+ *  - quantisation: either quality 1 .. 100, libjpeg's scaling of the Annex K
+ *    tables (s = 5000 / q below 50, else 200 - 2 q; entry (base * s + 50) / 100,
+ *    clamped to 1 .. 255), or the caller's two tables of 64 bytes in natural
+ *    (row-major) order, entries 1 .. 255.  One component uses table 0 only.
+ *  - restart, in MCUs: 0 none; 1 .. 65535 a DRI segment and RSTm between the
+ *    intervals, m counting modulo 8.
+ *  - colour: libjpeg's 16-bit fixed point RGB -> YCbCr, 4:4:4; an MCU is the Y,
+ *    Cb, Cr blocks of one 8 x 8 position.  Y: table 0 and the luminance Huffman
+ *    tables; Cb, Cr: table 1 and the chrominance ones.
+ *  - blocks: the image padded to multiples of 8 by repeating the last column,
+ *    then the last row; 128 subtracted; jfdctint (13-bit constants, PASS1_BITS
+ *    2, rows then columns); with qv = q << 3 the level (|c| + (qv >> 1)) / qv,
+ *    sign restored.
+ *  - entropy code: baseline Huffman, the Annex K tables as they stand; the DC
+ *    predictor is zero at every restart; ZRL for runs above 15, EOB unless
+ *    coefficient 63 is non-zero.  Most significant bit first, every 0xFF data
+ *    byte followed by 0x00, the last byte in front of a marker filled with
+ *    1-bits (and stuffed if that makes it 0xFF).
+ *  - the file: SOI, APP0 (JFIF 1.01, no density), DQT per table, SOF0, one DHT
+ *    per table, DRI if restart > 0, SOS, the scan, EOI.
+ *  - d_result (xrit_jpeg_result, 8-byte aligned): size is the file's length
+ *    whether or not it fitted, status 1 if size > cap.  No byte at or behind
+ *    d_out + cap is ever written; with status 1 the bytes in front are unspecified.
+ *  - the bound of a file (xrit_jpeg_bound): a block is at most 22 + 63 * 26 bits
+ *    (the longest DC code, 11 bits in the chrominance table -- the luminance
+ *    table's longest has 9 -- and 11 magnitude bits, 63 times a 16-bit code and 10
+ *    bits); an interval's bits are rounded up to a byte; every byte may be 0xFF
+ *    and stuffed, which doubles it; 2 bytes of marker between intervals, the
+ *    header and EOI on top:  header + 2 * (ceil(blocks * 1660 / 8) + intervals)
+ *    + 2 * (intervals - 1) + 2.
+ *  - the handle owns only scratch and the parameters: no state between calls.
+ *    Calls on one handle share the scratch: keep them in order.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_jpeg xrit_jpeg;
+#define XRIT_JPEG_MAX_BLOCKS (1u << 22)
+typedef struct xrit_jpeg_result {
+    uint64_t size;                   /* the file's length */
+    uint32_t status;                 /* 1: size > cap, the file did not fit */
+    uint32_t restarts;               /* restart markers in the file */
+} xrit_jpeg_result;                  /* 16 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path".  A new handle has quality 90, restart 0. */
+int xrit_jpeg_create(xrit_jpeg **j, int device);
+int xrit_jpeg_destroy(xrit_jpeg *j);
+/* waits for the handle's last call; the parameters stay */
+int xrit_jpeg_reset(xrit_jpeg *j);
+/* quality 1 .. 100, restart 0 .. 65535; anything else XRIT_E_INVALID, nothing changed */
+int xrit_jpeg_set_quality(xrit_jpeg *j, uint32_t quality, uint32_t restart);
+/* tables128: table 0 then table 1, natural order, every entry 1 .. 255 */
+int xrit_jpeg_set_tables(xrit_jpeg *j, const uint8_t *tables128, uint32_t restart);
+/* Host only, no device is touched: the bytes SOI .. SOS that the device will write for that shape with the handle's
+ * parameters.  *n is their number; they are written to out when n <= cap (out may be NULL with cap 0). */
+int xrit_jpeg_header(const xrit_jpeg *j, uint32_t components, uint32_t columns, uint32_t rows, uint8_t *out, size_t cap, size_t *n);
+/* Host only, without a handle: the two tables that xrit_jpeg_set_quality selects (128 bytes, natural order), and the
+ * header for given tables and restart. */
+int xrit_jpeg_quality_tables(uint32_t quality, uint8_t *tables128);
+int xrit_jpeg_header_for(const uint8_t *tables128, uint32_t restart, uint32_t components, uint32_t columns, uint32_t rows, uint8_t *out,
+                         size_t cap, size_t *n);
+/* Host only: the largest file any input of that shape can produce (the derivation is above); 0 for a shape or a restart
+ * that the stage refuses. */
+uint64_t xrit_jpeg_bound(uint32_t components, uint32_t columns, uint32_t rows, uint32_t restart);
+/* device pointers, asynchronous on `stream` (0: the null stream), no host synchronisation: it may be queued directly
+ * behind xrit_product_process_device, xrit_product_composite_device and xrit_geo_*.  components 1 or 3.  Components
+ * other than 1 or 3, a zero or too large dimension, a pitch too small, a NULL d_out or d_result (cap = 0 too):
+ * XRIT_E_INVALID, nothing queued, nothing written. */
+int xrit_jpeg_encode_device(xrit_jpeg *j, const xrit_product_image *image, uint32_t components, uint8_t *d_out, size_t cap,
+                            xrit_jpeg_result *d_result, void *stream);
+/* host buffers (one upload, one download of min(size, cap) bytes): image->d_pixels, out and result are host memory.
+ * XRIT_E_CAPACITY when the file did not fit (result says how long it is). */
+int xrit_jpeg_encode(xrit_jpeg *j, const xrit_product_image *image, uint32_t components, uint8_t *out, size_t cap, xrit_jpeg_result *result);
+/* the pixels in device memory where they lie, out and result host memory: nothing is uploaded, only the file's bytes are
+ * downloaded.  Runs on the handle's own stream and waits. */
+int xrit_jpeg_encode_resident(xrit_jpeg *j, const xrit_product_image *image, uint32_t components, uint8_t *out, size_t cap,
+                              xrit_jpeg_result *result);
 
 /* ------------------------------------------------------------------------
  * Carrier acquisition: a stage IN FRONT of the chain that finds a large carrier

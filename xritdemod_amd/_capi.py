@@ -162,6 +162,7 @@ _SIGNATURES = {
     "xrit_product_process_device": (C.c_int, [_vp] * 10),
     "xrit_product_process": (C.c_int, [_vp] * 9),
     "xrit_product_process_resident": (C.c_int, [_vp] * 9),
+    "xrit_product_outputs_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "xrit_product_composite_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "xrit_product_composite": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "xrit_geo_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -178,6 +179,18 @@ _SIGNATURES = {
     "xrit_geo_project_resident": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "xrit_geo_parse_navigation": (C.c_int, [_vp, C.c_size_t, _vp]),
     "xrit_geo_pixel_to_lonlat": (C.c_int, [_vp, C.c_double, C.c_double, _vp, _vp]),
+    "xrit_jpeg_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_jpeg_destroy": (C.c_int, [_vp]),
+    "xrit_jpeg_reset": (C.c_int, [_vp]),
+    "xrit_jpeg_set_quality": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "xrit_jpeg_set_tables": (C.c_int, [_vp, _vp, C.c_uint32]),
+    "xrit_jpeg_header": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
+    "xrit_jpeg_quality_tables": (C.c_int, [C.c_uint32, _vp]),
+    "xrit_jpeg_header_for": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
+    "xrit_jpeg_bound": (C.c_uint64, [C.c_uint32] * 4),
+    "xrit_jpeg_encode_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp, _vp]),
+    "xrit_jpeg_encode": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp]),
+    "xrit_jpeg_encode_resident": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp]),
     "xrit_acquire_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int]),
     "xrit_acquire_destroy": (C.c_int, [_vp]),
     "xrit_acquire_reset": (C.c_int, [_vp]),
@@ -1732,6 +1745,13 @@ class ImageProduct(_Handle):
         _check(lib().xrit_product_process_device(self._h, _p(img), _p(params), v(d_table_in_ptr), v(d_hist_ptr), v(d_lut_ptr), v(d_tone_ptr),
                                                  v(d_small_ptr), v(d_summary_ptr), v(stream)))
 
+    def outputs_device(self):
+        """(d_tone, d_small): where the last process / process_resident left the toned image and the thumbnail in device
+        memory (None for one it did not make), for a stage that goes on with them there (JpegEncoder.encode_resident)."""
+        tone, small = C.c_void_p(), C.c_void_p()
+        _check(lib().xrit_product_outputs_device(self._h, C.byref(tone), C.byref(small)))
+        return tone.value, small.value
+
     def composite(self, a, b, table):
         """a, b: toned 8-bit images of one shape; table: 256 * 256 * 3 bytes -> uint8 (rows, columns, 3)."""
         a, b = np.asarray(a), np.asarray(b)
@@ -1906,6 +1926,112 @@ class ImageProjector(_Handle):
     def reset(self):
         """Waits for the last call; the tables stay."""
         _check(lib().xrit_geo_reset(self._h))
+
+
+# ---- JPEG (DESIGN.md section 25) ---------------------------------------------------------------------------------------
+JPEG_MAX_BLOCKS = 1 << 22
+# xrit_jpeg_result: what an encode leaves for the caller
+JPEG_RESULT_DTYPE = np.dtype([("size", np.uint64), ("status", np.uint32), ("restarts", np.uint32)])
+assert JPEG_RESULT_DTYPE.itemsize == 16
+
+
+def jpeg_bound(components, columns, rows, restart=0):
+    """The largest file any input of that shape can produce; 0 for a shape the stage refuses.  Plain host code."""
+    return int(lib().xrit_jpeg_bound(components, columns, rows, restart))
+
+
+def jpeg_quality_tables(quality):
+    """libjpeg's scaling of the Annex K tables -> uint8 (2, 64), natural order.  Plain host code."""
+    t = np.zeros((2, 64), np.uint8)
+    _check(lib().xrit_jpeg_quality_tables(quality, _p(t)))
+    return t
+
+
+def jpeg_header(tables, restart, components, columns, rows):
+    """SOI .. SOS as the device writes them for these tables ((2, 64), natural order).  Plain host code: no device."""
+    t = np.ascontiguousarray(tables, np.uint8).reshape(-1)
+    if len(t) != 128:
+        raise ValueError("two tables of 64 bytes")
+    out, n = np.zeros(1024, np.uint8), _sz()
+    _check(lib().xrit_jpeg_header_for(_p(t), restart, components, columns, rows, _p(out), len(out), C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+class JpegEncoder(_Handle):
+    """An 8-bit image in device memory -> a complete baseline JFIF file in device memory, the file libjpeg writes for the
+    same pixels: quality 1 .. 100 (libjpeg's scaling of the Annex K tables) or the caller's two tables ((2, 64), natural
+    order, entries 1 .. 255); restart in MCUs (0: none).  One component (H x W) or interleaved RGB (H x W x 3), coded
+    4:4:4.  The handle owns scratch and the parameters; tests/jpeg_spec.py is the specification."""
+    _destroy = "xrit_jpeg_destroy"
+
+    def __init__(self, quality=90, restart=0, tables=None, device=0):
+        super().__init__()
+        _check(lib().xrit_jpeg_create(C.byref(self._h), device))
+        if tables is None:
+            self.set_quality(quality, restart)
+        else:
+            self.set_tables(tables, restart)
+
+    def set_quality(self, quality, restart=0):
+        _check(lib().xrit_jpeg_set_quality(self._h, quality, restart))
+        self.restart = restart
+
+    def set_tables(self, tables, restart=0):
+        t = np.ascontiguousarray(tables, np.uint8).reshape(-1)
+        if len(t) != 128:
+            raise ValueError("two tables of 64 bytes")
+        _check(lib().xrit_jpeg_set_tables(self._h, _p(t), restart))
+        self.restart = restart
+
+    def header(self, components, columns, rows):
+        """The bytes SOI .. SOS the device will write for that shape.  Host only."""
+        out, n = np.zeros(1024, np.uint8), _sz()
+        _check(lib().xrit_jpeg_header(self._h, components, columns, rows, _p(out), len(out), C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def bound(self, components, columns, rows):
+        return jpeg_bound(components, columns, rows, self.restart)
+
+    @staticmethod
+    def _image(pixels_ptr, columns, rows, pitch):
+        image = np.zeros(1, PRODUCT_IMAGE_DTYPE)
+        image[0] = (pixels_ptr or 0, columns, rows, pitch, 8)
+        return image
+
+    def _to_host(self, fn, pixels_ptr, columns, rows, pitch, components, cap):
+        cap = self.bound(components, columns, rows) if cap is None else cap
+        out, result = np.zeros(max(cap, 1), np.uint8), np.zeros(1, JPEG_RESULT_DTYPE)
+        _check(fn(self._h, _p(self._image(pixels_ptr, columns, rows, pitch)), components, _p(out), cap, _p(result)))
+        return out[:int(result[0]["size"])].tobytes()
+
+    def encode(self, image, cap=None):
+        """image: uint8, H x W or H x W x 3, contiguous along its rows (its row stride is the pitch) -> the file's bytes.
+        cap: the room for the file (default: the bound); XritError -5 when the file does not fit."""
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim not in (2, 3) or (image.ndim == 3 and image.shape[2] != 3):
+            raise ValueError("a uint8 image of shape H x W or H x W x 3")
+        rows, columns = image.shape[:2]
+        comps = 1 if image.ndim == 2 else 3
+        if image.strides[0] < 0 or image.strides[1] != comps or (comps == 3 and image.strides[2] != 1):
+            raise ValueError("an image contiguous along its rows")
+        return self._to_host(lib().xrit_jpeg_encode, image.ctypes.data, columns, rows, image.strides[0] if rows > 1 else columns * comps,
+                             comps, cap)
+
+    def encode_resident(self, d_pixels_ptr, columns, rows, pitch, components, cap=None):
+        """As encode, on pixels that lie in device memory: nothing is uploaded, only the file's bytes are downloaded."""
+        return self._to_host(lib().xrit_jpeg_encode_resident, d_pixels_ptr, columns, rows, pitch, components, cap)
+
+    def encode_device(self, d_pixels_ptr, columns, rows, pitch, components, d_out_ptr, cap, d_result_ptr, stream=None):
+        """Device pointers; the file goes to d_out (at most cap bytes), 16 bytes of JPEG_RESULT_DTYPE to d_result.
+        Asynchronous on stream, no host synchronisation: may be queued behind ImageProduct.process_device,
+        composite_device and ImageProjector.project_device."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_jpeg_encode_device(self._h, _p(self._image(d_pixels_ptr, columns, rows, pitch)), components, v(d_out_ptr), cap,
+                                             v(d_result_ptr), v(stream)))
+
+    def reset(self):
+        """Waits for the last call; the parameters stay."""
+        _check(lib().xrit_jpeg_reset(self._h))
 
 
 # ---- carrier acquisition (DESIGN.md section 21) -------------------------------------------------------------------------

@@ -563,6 +563,30 @@ int launch_geo_resample(const GeoTables &t, const xrit_product_image &im, const 
                         uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
 int launch_geo_project(const GeoTables &t, const xrit_geo_nav &nav, const xrit_product_image &im, uint32_t mode, unsigned char *out,
                        uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
+// JPEG stage (jpeg.hip; jpeg_rule.h is the rule per value): one call on blocks = MCUs * comps blocks in n_int restart
+// intervals of ri MCUs (restart 0: one interval of all MCUs); the scratch for that many
+struct JpegPar {
+    const unsigned char *pix;
+    uint32_t columns, rows, pitch, comps;
+    uint32_t bw, mcus, blocks;              // MCUs per row, MCUs, blocks
+    uint32_t ri, n_int;
+    unsigned char q[2][64];                 // the quantisation tables, natural order
+};
+struct JpegHeader {                         // SOI .. SOS, handed to the emit kernel by value
+    uint32_t n;
+    unsigned char b[640];
+};
+struct JpegScratch {
+    unsigned long long *P, *P_aggs;         // [blocks + 1] the bits in front of a block; its scan's aggregates
+    uint32_t *raw;                          // the unstuffed stream, every interval from a byte boundary, as whole groups of 16 bytes
+    int16_t *coef;                          // [blocks][64] quantised coefficients, zigzag order
+    uint32_t *blen;                         // [blocks] a block's code length in bits
+    uint32_t *U, *U_aggs;                   // [n_int + 1] the unstuffed bytes in front of an interval
+    uint32_t *F, *F_aggs;                   // [groups + 1] the 0xFF bytes in front of a group of 16 unstuffed bytes
+};
+size_t jpeg_scratch_carve(void *p, uint32_t blocks, uint32_t n_int, JpegScratch &sc);
+int launch_jpeg(const JpegPar &p, const JpegHeader &h, const JpegScratch &sc, unsigned char *out, size_t cap, xrit_jpeg_result *result,
+                hipStream_t s);
 // carrier acquisition (acquire.hip; acquire_host.h has the sizes): the handle's state is one xrit_acquire_state; the scratch
 // of an estimate of M segments
 struct AcquireScratch {

@@ -27,6 +27,7 @@ constexpr uint64_t MAX_PIXELS = (uint64_t)1 << 31;
 struct xrit_product : StageHandle {
     DevBuf scratch;                                 // the histogram, the tone table, then the out-of-range count
     DevBuf h_in, h_table, h_out;                    // the host-buffer forms'
+    const uint8_t *last_tone = nullptr, *last_small = nullptr;      // where the last host-buffer call left them in h_out
     uint32_t *hist() const { return scratch.as<uint32_t>(); }
     unsigned char *lut() const { return scratch.as<unsigned char>() + HIST_BYTES; }
     unsigned long long *over_count() const { return reinterpret_cast<unsigned long long *>(scratch.as<char>() + HIST_BYTES + LUT_BYTES); }
@@ -108,6 +109,8 @@ static int product_to_host(xrit_product *pr, const xrit_product_image &im, const
     const size_t at_tone = sizeof(xrit_product_summary), at_small = at_tone + tone_bytes;
     XR_TRY(pr->h_out.reserve(at_small + small_bytes));
     uint8_t *d_out = pr->h_out.as<uint8_t>();
+    pr->last_tone = tone_bytes ? d_out + at_tone : nullptr;
+    pr->last_small = small_bytes ? d_out + at_small : nullptr;
     XR_TRY(product_run(pr, im, pp, d_table_in, nullptr, nullptr, tone_bytes ? d_out + at_tone : nullptr, small_bytes ? d_out + at_small : nullptr,
                        reinterpret_cast<xrit_product_summary *>(d_out), s));
     XR_HIP(hipMemcpyAsync(summary, d_out, sizeof *summary, hipMemcpyDeviceToHost, s));
@@ -154,6 +157,14 @@ int xrit_product_process_resident(xrit_product *pr, const xrit_product_image *im
     XR_TRY(pr->adopt_own_stream(s));
     XR_TRY(upload_table(pr, *image, *params, table_in, s));
     return product_to_host(pr, *image, *params, pr->h_table.as<uint8_t>(), hist, lut, tone, small, summary, s);
+}
+
+int xrit_product_outputs_device(xrit_product *pr, const uint8_t **d_tone, const uint8_t **d_small)
+{
+    if (!pr || !d_tone || !d_small) { set_error("null argument"); return XRIT_E_INVALID; }
+    *d_tone = pr->last_tone;
+    *d_small = pr->last_small;
+    return XRIT_OK;
 }
 
 static int check_composite(const xrit_product *pr, const void *a, uint32_t pitch_a, const void *b, uint32_t pitch_b, uint32_t columns,

@@ -100,6 +100,7 @@ struct Options {
     bool products = false;         // --products: with --canvas, every canvas written also as DIR/<name>.view.pgm and .thumb.pgm (xrit_product_*)
     bool product_flags = false;    // --product-tone or --product-factor was given
     xrit_product_params product{XRIT_TONE_EQUALISE, 0, 10000, 8};      // --product-tone linear|equalise|stretch[:LO:HI], --product-factor F
+    int jpeg = 0;                  // --jpeg [Q]: with --products, each .view.pgm and .thumb.pgm also as .jpg of quality Q (xrit_jpeg_*); 0: none
     bool project = false;          // --project: with --canvas, every canvas written also on a latitude / longitude grid, DIR/<name>.geo.pgm (xrit_geo_*)
     bool project_flags = false;    // --project-grid or --project-mode was given
     bool project_grid_given = false;   // --project-grid LON0:LAT0:STEP:COLUMNS:ROWS; otherwise the disc's bounding box at 0.05 degrees
@@ -157,6 +158,9 @@ void usage()
                  "                                 stretch between the percentiles LO and HI per myriad (default 200:9800), value 0 being \"no data\" --\n"
                  "                                 and written as DIR/<name>.view.pgm, and reduced F times (1..64, default 8; pixels without data\n"
                  "                                 left out of the means) as DIR/<name>.thumb.pgm; only these two are downloaded)\n"
+                 "         [--jpeg [Q]]           (with --products: the toned image and the thumbnail are also encoded on the GPU where they lie, as\n"
+                 "                                 baseline JPEG of quality Q (1..100, default 90) with a restart marker per row of blocks, and\n"
+                 "                                 written as DIR/<name>.view.jpg and DIR/<name>.thumb.jpg; only the files' bytes are downloaded)\n"
                  "         [--project [--project-grid LON0:LAT0:STEP:COLUMNS:ROWS] [--project-mode nearest|bilinear]]   (with --canvas: every canvas\n"
                  "                                 that is written is also resampled on the GPU onto a latitude / longitude grid, from the image\n"
                  "                                 navigation record (type 2) of its segment file at line 0, column 0, and written as\n"
@@ -269,6 +273,15 @@ bool parse(int argc, char **argv, Options &o)
             o.product.factor = (uint32_t)f;
             o.product_flags = true;
         }
+        else if (a == "--jpeg") {
+            o.jpeg = 90;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {      // a token that begins with a digit is Q, whole
+                char *end = nullptr;
+                const long q = std::strtol(argv[++i], &end, 10);
+                if (*end != '\0' || q < 1 || q > 100) { std::fprintf(stderr, "--jpeg %s: 1..100\n", argv[i]); return false; }
+                o.jpeg = (int)q;
+            }
+        }
         else if (a == "--project") o.project = true;
         else if (a == "--project-grid") {
             if (!(v = need("--project-grid")) || !parse_project_grid(v, o.project_grid)) return false;
@@ -342,6 +355,10 @@ bool parse(int argc, char **argv, Options &o)
     }
     if ((o.products && !o.canvas) || (o.product_flags && !o.products)) {
         std::fprintf(stderr, "--products needs --canvas; --product-tone and --product-factor need --products\n");
+        return false;
+    }
+    if (o.jpeg && !o.products) {
+        std::fprintf(stderr, "--jpeg needs --products\n");
         return false;
     }
     if ((o.project && !o.canvas) || (o.project_flags && !o.project)) {
@@ -474,6 +491,10 @@ struct FrameDecode {
     xrit_product *pr = nullptr;
     std::vector<uint8_t> pr_tone, pr_small;
     size_t products_written = 0, product_fallbacks = 0;
+    int jpeg = 0;                   // --jpeg's quality, 0: none (set it before open())
+    xrit_jpeg *jp = nullptr;
+    std::vector<uint8_t> jp_file;
+    size_t jpegs_written = 0, jpeg_bytes = 0;
     bool project = false;           // --project (set it, project_grid, project_grid_given and project_mode before open())
     bool project_grid_given = false;
     xrit_geo_grid project_grid{};
@@ -564,6 +585,10 @@ struct FrameDecode {
                 cv_slots.assign(canvas_slots, xrit_canvas_slot{});
                 cv_pixels.resize(canvas_bytes);
                 if (products && xrit_product_create(&pr, device) != XRIT_OK) {
+                    std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
+                    return false;
+                }
+                if (products && jpeg && xrit_jpeg_create(&jp, device) != XRIT_OK) {
                     std::fprintf(stderr, "xritdemod_amd: %s\n", xrit_last_error());
                     return false;
                 }
@@ -938,6 +963,35 @@ struct FrameDecode {
             if (!ok) { std::perror(path.c_str()); return false; }
         }
         ++products_written;
+        if (!jp) return true;
+        // --jpeg: both encoded where the product call left them on the device
+        const uint8_t *d_tone = nullptr, *d_small = nullptr;
+        if (xrit_product_outputs_device(pr, &d_tone, &d_small) != XRIT_OK) return fail("product outputs");
+        return write_jpeg(stem + ".view.jpg", d_tone, summary.tone_columns, summary.tone_rows) &&
+               write_jpeg(stem + ".thumb.jpg", d_small, summary.small_columns, summary.small_rows);
+    }
+    // one 8-bit image in device memory as a JPEG file, a restart marker per row of blocks; a file longer than the pixels
+    // (noise at a high quality) takes a second call with the room the first one asked for
+    bool write_jpeg(const std::string &path, const uint8_t *d_pixels, uint32_t columns, uint32_t rows)
+    {
+        if (!d_pixels || !columns || !rows) return true;
+        if (xrit_jpeg_set_quality(jp, (uint32_t)jpeg, (columns + 7) / 8) != XRIT_OK) return fail("jpeg");
+        const xrit_product_image image{d_pixels, columns, rows, columns, 8};
+        xrit_jpeg_result result{};
+        jp_file.resize((size_t)columns * rows + 4096);
+        int rc = xrit_jpeg_encode_resident(jp, &image, 1, jp_file.data(), jp_file.size(), &result);
+        if (rc == XRIT_E_CAPACITY) {
+            jp_file.resize((size_t)result.size);
+            rc = xrit_jpeg_encode_resident(jp, &image, 1, jp_file.data(), jp_file.size(), &result);
+        }
+        if (rc != XRIT_OK) return fail("jpeg");
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::perror(path.c_str()); return false; }
+        const bool ok = std::fwrite(jp_file.data(), 1, (size_t)result.size, f) == (size_t)result.size;
+        std::fclose(f);
+        if (!ok) { std::perror(path.c_str()); return false; }
+        ++jpegs_written;
+        jpeg_bytes += (size_t)result.size;
         return true;
     }
     void close_packet_files()
@@ -1018,6 +1072,11 @@ struct FrameDecode {
                                  product.factor, product_fallbacks);
                     xrit_product_destroy(pr);
                     pr = nullptr;
+                }
+                if (jp) {
+                    std::fprintf(stderr, "jpeg: %zu files of quality %d, %zu bytes\n", jpegs_written, jpeg, jpeg_bytes);
+                    xrit_jpeg_destroy(jp);
+                    jp = nullptr;
                 }
                 if (geo) {
                     std::fprintf(stderr, "project: %zu canvases projected onto %u x %u (%s), %zu skipped\n", projected, project_grid.columns,
@@ -1396,6 +1455,7 @@ int main(int argc, char **argv)
     decode.canvas_bytes = o.canvas_mib << 20;
     decode.products = o.products;
     decode.product = o.product;
+    decode.jpeg = o.jpeg;
     decode.project = o.project;
     decode.project_grid = o.project_grid;
     decode.project_grid_given = o.project_grid_given;
