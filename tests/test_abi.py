@@ -95,14 +95,18 @@ def test_host_program_builds_and_has_no_cpu_path(xa, tmp_path):
     assert os.path.exists(HOST_BIN), "make -C xritdemod_amd/csrc builds it"
     r = subprocess.run([HOST_BIN], capture_output=True, text=True)
     assert r.returncode == 2 and "usage:" in r.stderr
+    host = os.path.join(ROOT, "xritdemod_amd", "host")
+    pieces = sorted(os.listdir(host))
+    assert "xrit_demod_host.cpp" in pieces
+    for name in pieces:                          # the boundary is the C ABI only, in every piece of the program
+        src = open(os.path.join(host, name)).read()
+        assert "hip/hip_runtime" not in src and "<hip/" not in src, name
     if xa.device_count() > 0:
         pytest.skip("a HIP device is present")
     f = tmp_path / "x.cf32"
     np.zeros(2048, np.complex64).tofile(f)
     r = subprocess.run([HOST_BIN, "--input", str(f), "--sink", "null"], capture_output=True, text=True)
     assert r.returncode == 1 and "no CPU path" in r.stderr
-    src = open(os.path.join(ROOT, "xritdemod_amd", "host", "xrit_demod_host.cpp")).read()
-    assert "hip/hip_runtime" not in src          # the boundary is the C ABI only
 
 
 def test_integration_md_snippets_compile_against_the_header(tmp_path):
