@@ -1469,6 +1469,12 @@ int xrit_jpeg_encode_resident(xrit_jpeg *j, const xrit_product_image *image, uin
  *    times (-1)^k0 places the line inside the bin.  M = min(segments,
  *    floor(floor(n / pre_sum) / 2048) - 1).  float32 through |X|^2, float64 behind
  *    it; no atomics: the same bits from run to run.
+ *    A sample that is not finite, or whose square is not in float32, gives status
+ *    WEAK whenever it lies within the samples the estimate reads, and is never
+ *    applied; k0, ratio and nu are then unspecified but the same from run to run,
+ *    and inc is 0 when nu is NaN.  Silence is WEAK too (ratio NaN, k0, nu and inc
+ *    0).  Samples beyond (M + 1) * 2048 * pre_sum, and beyond the last whole
+ *    pre-sum, are not read.
  *    UNAMBIGUOUS ONLY FOR |f| < sample_rate / (4 * pre_sum).
  *    A strong DC component squares to a line at 0 Hz and would be taken for the
  *    carrier; behaviour under adjacent-channel interference is not known

@@ -1,6 +1,6 @@
 """The cases the carrier acquisition tests share (tests/test_acquire_spec.py on the CPU, tests/test_gpu_acquire.py on the
-device): the synthetic bursts of the estimate, the burst of the end-to-end check, and how its decisions are counted.  Every
-burst and every record of the specification is made once per process."""
+device): the synthetic bursts of the estimate, pure tones with a closed form for the answer, the burst of the end-to-end
+check, and how its decisions are counted.  Every burst and every record of the specification is made once per process."""
 import numpy as np
 
 import acquire_spec as sp
@@ -79,6 +79,79 @@ def spec_record(name, detail=False):
 def noise(n, seed):
     rng = np.random.default_rng(seed)
     return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.1).astype(np.complex64)
+
+
+def longer(name, n):
+    """The case's burst carried on to n samples, in the case's sample type (the generator is counter based: the first
+    samples are the case's own).  For the plain cases only."""
+    c = CASES[name]
+    assert not {"held", "tiled", "high_bytes", "symbol_rate"} & set(c)
+    x = synth.generate(synth.SynthParams(fs_in=c["fs"], carrier_hz=c["carrier_hz"], esn0_db=c["esn0_db"]), n)
+    if c.get("s16"):
+        x = np.clip(np.rint(x.view(np.float32) * 32768.0), -32768, 32767).astype(np.int16)
+    elif c.get("s8"):
+        x = np.clip(np.rint(x.view(np.float32) * 128.0), -128, 127).astype(np.int8)
+    return x
+
+
+# ---- tones: a pure line at a chosen place, with a closed form for the answer ---------------------------------------------------
+_TABLE, _TONE_RATIO = [], {}
+TONE_EDGES = (0, 1, 2047, 2048, 2049, 4095)
+
+
+def tone(k, d16, n=65536, pre_sum=1):
+    """n * pre_sum complex64 samples whose pre-summed square is a pure line at bin k + d16 / 16 of the N-point spectrum:
+    x[j] = exp(i pi (16 k + d16) j / (16 N R)).  For R = 1 the samples are looked up in a float64 table of the 32 N values
+    exp(i pi m / (16 N)) at the integer (j (16 k + d16)) mod 32 N, so no phase is ever rounded; for R > 1 sample m R + r is
+    the table's value for m times exp(i pi (16 k + d16) r / (16 N R)), one float64 product."""
+    if not _TABLE:
+        _TABLE.append(np.exp(1j * np.pi * np.arange(32 * sp.N) / (16 * sp.N)))
+    f = 16 * int(k) + int(d16)
+    x = _TABLE[0][(np.arange(n, dtype=np.int64) * f) % (32 * sp.N)]
+    if pre_sum > 1:
+        x = (x[:, None] * np.exp(1j * np.pi * f * np.arange(pre_sum) / (16 * sp.N * pre_sum))[None, :]).reshape(-1)
+    return x.astype(np.complex64)
+
+
+def tone_as(x, sample_type):
+    """A tone in the given sample type: cf32 as is, int16 scaled to 30000, int8 to 100, rounded (interleaved)."""
+    if sample_type == sp.FLOATIQ:
+        return x
+    scale, dt = (30000.0, np.int16) if sample_type == sp.S16IQ else (100.0, np.int8)
+    return np.rint(x.view(np.float32) * np.float32(scale)).astype(dt)
+
+
+def tone_d16(k):
+    """The schedule that gives every bin an offset of its own: -6 .. 6 sixteenths, so the line's bin is k without doubt."""
+    return (37 * int(k)) % 13 - 6
+
+
+def tone_nu(k, d16, pre_sum=1):
+    """The closed form of the answer: wrap((k + d16 / 16) / N) / (2 R), wrap to [-1/2, 1/2)."""
+    nu2 = (k + d16 / 16.0) / sp.N
+    return (nu2 - np.floor(nu2 + 0.5)) / (2 * pre_sum)
+
+
+def bins_apart(nu_a, nu_b, pre_sum=1, circle=False):
+    """|nu_a - nu_b| in bins of 1 / (2 N R); on the circle the distance modulo N bins (a line on the wrap at bin 2048 may be
+    named from either side)."""
+    d = (float(nu_a) - float(nu_b)) * 2 * sp.N * pre_sum
+    if circle:
+        d -= sp.N * np.rint(d / sp.N)
+    return abs(d)
+
+
+def tone_ratio(d16):
+    """The specification's ratio for a tone of 65 536 samples d16 sixteenths off a bin: that of bin 0, since the spectrum
+    of a shifted tone is the same spectrum shifted (tests/test_acquire_spec.py holds that to 1e-8)."""
+    if d16 not in _TONE_RATIO:
+        _TONE_RATIO[d16] = float(sp.estimate(tone(0, d16), 1.25e6)["ratio"])
+    return _TONE_RATIO[d16]
+
+
+def top_two(P):
+    """The two largest powers of a row, the smaller first."""
+    return np.sort(P)[-2:]
 
 
 # ---- end to end: LRIT at 1.25 Msps, +23 kHz, 8 dB, 600 000 samples -----------------------------------------------------------

@@ -79,8 +79,10 @@ def inc_from_hz(hz, sample_rate):
 
 def estimate(x, sample_rate, pre_sum=1, max_segments=DEFAULT_SEGMENTS, min_ratio=DEFAULT_MIN_RATIO, detail=False):
     """x: complex samples (any complex dtype; taken to float64).  -> a RECORD_DTYPE scalar record (applied 0); with
-    detail also P, the summed power rows."""
-    x = np.asarray(x).astype(np.complex128)
+    detail also P, the summed power rows.  Only the first (M + 1) * 2048 * R samples are read.  Silence and a sample that is
+    not finite among them give a record like any other input: the ratio is NaN, so the status is WEAK, and a nu that is
+    not finite gives inc 0."""
+    x = np.asarray(x, np.complex128)
     R = int(pre_sum)
     rec = np.zeros(1, RECORD_DTYPE)[0]
     M = segments_for(len(x), R, max_segments)
@@ -89,29 +91,30 @@ def estimate(x, sample_rate, pre_sum=1, max_segments=DEFAULT_SEGMENTS, min_ratio
         rec["status"] = TOO_SHORT
         return (rec, None) if detail else rec
     nz = (M + 1) * HOP
-    u = x[:nz * R].reshape(nz, R).sum(axis=1)
-    z = u * u
-    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N) / N)
-    P = np.zeros(N)
-    X = np.empty((M, N), np.complex128)
-    for s in range(M):
-        X[s] = np.fft.fft(z[s * HOP:s * HOP + N] * w)
-        P += np.abs(X[s]) ** 2
-    k0 = int(np.argmax(P))
-    col = X[:, k0]
-    C = np.sum(col[1:] * np.conj(col[:-1]))
-    if k0 & 1:
-        C = -C
-    d = np.arctan2(C.imag, C.real)
-    nu2 = k0 / N + d / (np.pi * N)
-    nu2 -= np.floor(nu2 + 0.5)
-    nu = nu2 / (2 * R)
-    rec["k0"] = k0
-    rec["ratio"] = P[k0] / np.mean(P)
-    rec["nu"] = nu
-    rec["hz"] = nu * sample_rate
-    rec["inc"] = inc_from_nu(nu)
-    rec["status"] = OK if rec["ratio"] >= min_ratio else WEAK
+    with np.errstate(all="ignore"):         # silence (0 / 0) and samples that are not finite give a record, not a warning
+        u = x[:nz * R].reshape(nz, R).sum(axis=1)
+        z = u * u
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N) / N)
+        P = np.zeros(N)
+        X = np.empty((M, N), np.complex128)
+        for s in range(M):
+            X[s] = np.fft.fft(z[s * HOP:s * HOP + N] * w)
+            P += np.abs(X[s]) ** 2
+        k0 = int(np.argmax(P))
+        col = X[:, k0]
+        C = np.sum(col[1:] * np.conj(col[:-1]))
+        if k0 & 1:
+            C = -C
+        d = np.arctan2(C.imag, C.real)
+        nu2 = k0 / N + d / (np.pi * N)
+        nu2 -= np.floor(nu2 + 0.5)
+        nu = nu2 / (2 * R)
+        rec["k0"] = k0
+        rec["ratio"] = P[k0] / np.mean(P)
+        rec["nu"] = nu
+        rec["hz"] = nu * sample_rate
+    rec["inc"] = inc_from_nu(nu) if np.isfinite(nu) else 0          # the device's nu == nu ? ... : 0
+    rec["status"] = OK if rec["ratio"] >= min_ratio else WEAK       # (a ratio that is NaN is WEAK)
     return (rec, P) if detail else rec
 
 
@@ -136,14 +139,22 @@ class Acquirer:
     def __init__(self, sample_rate, pre_sum=1, segments=DEFAULT_SEGMENTS, min_ratio=DEFAULT_MIN_RATIO):
         self.sample_rate, self.pre_sum, self.segments, self.min_ratio = float(sample_rate), pre_sum, segments, min_ratio
         self.acc, self.inc = 0, 0
+        self.estimates, self.applied = 0, 0
 
     def set_frequency(self, hz):
         self.inc = inc_from_hz(hz, self.sample_rate)
 
     def estimate(self, samples, sample_type=FLOATIQ, apply=False):
-        rec = estimate(to_complex(samples, sample_type, np.complex128), self.sample_rate, self.pre_sum, self.segments, self.min_ratio)
+        return self.take(estimate(to_complex(samples, sample_type, np.complex128), self.sample_rate, self.pre_sum, self.segments,
+                                  self.min_ratio), apply)
+
+    def take(self, rec, apply=False):
+        """What an estimate does to the state once its record (made with this object's parameters, applied 0) is known."""
+        rec = rec.copy()
+        self.estimates += 1
         if apply and rec["status"] == OK:
             self.inc = int(rec["inc"])
+            self.applied += 1
             rec["applied"] = 1
         return rec
 

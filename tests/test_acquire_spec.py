@@ -1,4 +1,6 @@
-"""CPU tier: the specification of the carrier acquisition stage (tests/acquire_spec.py) against the synthetic burst, the
+"""CPU tier: the specification of the carrier acquisition stage (tests/acquire_spec.py) against the synthetic burst, against
+the closed form of a pure tone's answer (every 16th bin and the edges within 1e-9 of a bin, the half-way offsets), on input
+that is not a signal (silence, NaN, Inf, overflow: a WEAK record, no warning; a NaN where nothing is read: the same bytes), the
 oracle chain behind it, and the CPU side of the stage's ABI -- the header declares the functions, the ctypes layer binds
 them, the record layouts are the header's field for field, bad arguments are refused before a device is asked for, there is
 no CPU path; the plain host parts (csrc/acquire_host.h) in a stand-alone program under the sanitizers, held against a table
@@ -100,6 +102,106 @@ def test_default_min_ratio_lies_between_noise_and_signal():
     """2.28 over 256 seeds of noise at 31 segments, 34.9 for the weakest signal case at 2 dB."""
     assert 2.28 * 3 < sp.DEFAULT_MIN_RATIO < 34.9 / 3
     assert abs(sp.DEFAULT_MIN_RATIO - (2.28 * 34.9) ** 0.5) < 0.05
+
+
+# ---- the estimate against a closed form: tones --------------------------------------------------------------------------------
+def test_tones_are_what_they_say():
+    """The table look-up is np.exp of the same phase to float64's last bits; the pre-summed tone is a tone; the quantised
+    forms fill their range without clipping."""
+    for k, d16 in ((0, -6), (77, 3), (2048, 0), (4095, 8)):
+        want = np.exp(1j * np.pi * (16 * k + d16) * np.arange(65536) / (16 * sp.N))
+        assert np.abs(ac.tone(k, d16).astype(np.complex128) - want).max() < 1e-7           # complex64's rounding, and a 2e-11 phase
+        x4 = ac.tone(k, d16, 4096, 4).astype(np.complex128)
+        assert len(x4) == 4 * 4096
+        u = x4.reshape(4096, 4).sum(axis=1)
+        z = u * u / (u[0] * u[0])
+        assert np.abs(z - np.exp(2j * np.pi * (k + d16 / 16.0) * np.arange(4096) / sp.N)).max() < 1e-5
+    x = ac.tone(77, 3)
+    s16, s8 = ac.tone_as(x, sp.S16IQ), ac.tone_as(x, sp.S8IQ)
+    assert s16.dtype == np.int16 and s8.dtype == np.int8 and len(s16) == len(s8) == 2 * len(x)
+    assert 29990 <= int(np.abs(s16.astype(np.int64)).max()) <= 30000 and int(np.abs(s8.astype(np.int64)).max()) == 100
+    assert sorted({ac.tone_d16(k) for k in range(sp.N)}) == list(range(-6, 7))
+    assert ac.tone_nu(2048, 0) == -0.25 and ac.tone_nu(2047, 8, 4) == (2047.5 / sp.N) / 8 and ac.tone_nu(4095, 8) == -0.5 / sp.N / 2
+    assert ac.bins_apart(0.25 - 1e-9, -0.25, circle=True) < 1e-5 and ac.bins_apart(0.25 - 1e-9, -0.25) > 4095
+
+
+def test_specification_meets_the_closed_form_on_tones():
+    """Every 16th bin and the edges, each at its own offset of the schedule: the bin, nu within 1e-9 of a bin of
+    wrap((k + d16 / 16) / N) / 2 (measured: 3.0e-11), the ratio within 1e-8 of bin 0's at the same offset (measured: 5.8e-10)."""
+    worst_nu = worst_ratio = 0.0
+    for k in sorted(set(range(0, sp.N, 16)) | set(ac.TONE_EDGES)):
+        d16 = ac.tone_d16(k)
+        rec = sp.estimate(ac.tone(k, d16), 1.25e6)
+        assert rec["status"] == sp.OK and rec["segments"] == 31 and rec["k0"] == k, (k, d16)
+        bins = ac.bins_apart(rec["nu"], ac.tone_nu(k, d16))
+        rel = abs(float(rec["ratio"]) / ac.tone_ratio(d16) - 1.0)
+        worst_nu, worst_ratio = max(worst_nu, bins), max(worst_ratio, rel)
+        assert bins <= 1e-9 and rel <= 1e-8, (k, d16, bins, rel)
+        assert rec["inc"] == sp.inc_from_nu(rec["nu"]) and rec["hz"] == rec["nu"] * 1.25e6
+    print(f"tones: nu at most {worst_nu:.2e} of a bin from the closed form, ratio at most {worst_ratio:.2e} from bin 0's; "
+          f"smallest ratio {min(ac.tone_ratio(d) for d in range(-6, 7)):.0f}")
+    # the line on the wrap: either side names it
+    rec = sp.estimate(ac.tone(2048, 0), 1.25e6)
+    assert rec["status"] == sp.OK and rec["k0"] == 2048 and ac.bins_apart(rec["nu"], ac.tone_nu(2048, 0), circle=True) <= 1e-9
+
+
+def test_specification_places_a_line_half_way_between_two_bins():
+    """The coarse peak only has to be right to a bin: with the line half way the two neighbours' powers agree to 1e-9, either
+    may be named, and nu is the closed form's all the same."""
+    for k in (0, 77, 2047, 4095):
+        for d16 in (-8, 8):
+            rec, P = sp.estimate(ac.tone(k, d16), 1.25e6, detail=True)
+            top = ac.top_two(P)
+            other = (k + (1 if d16 > 0 else -1)) % sp.N
+            assert abs(top[1] / top[0] - 1.0) <= 1e-9 and {int(i) for i in np.argsort(P)[-2:]} == {k, other}, (k, d16)
+            assert rec["status"] == sp.OK and int(rec["k0"]) in (k, other)
+            assert ac.bins_apart(rec["nu"], ac.tone_nu(k, d16), circle=True) <= 1e-9, (k, d16)
+
+
+# ---- input that is not a signal -------------------------------------------------------------------------------------------------
+def same_record(a, b):
+    return a.tobytes() == b.tobytes()
+
+
+def test_silence_and_samples_that_are_not_finite_give_a_weak_record():
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")                      # the specification emits none
+        rec = sp.estimate(np.zeros(65536, np.complex64), 1.25e6)
+        assert rec["status"] == sp.WEAK and rec["segments"] == 31 and rec["k0"] == 0 and rec["nu"] == 0.0 and rec["hz"] == 0.0 and rec["inc"] == 0
+        assert np.isnan(rec["ratio"]) and rec["applied"] == 0
+        clean = ac.samples("c")
+        for bad, at in ((np.nan, 0), (np.nan, 40000), (np.nan, 65535), (np.inf, 12345), (-np.inf, 2048)):
+            x = clean.copy()
+            x[at] = bad
+            rec = sp.estimate(x, 1.25e6)
+            assert rec["status"] == sp.WEAK and rec["inc"] == 0 and rec["segments"] == 31, (bad, at)
+        big = sp.estimate(clean.astype(np.complex128) * 1e200, 1.25e6)              # squares overflow float64
+        assert big["status"] == sp.WEAK and big["inc"] == 0
+    a = sp.Acquirer(1.25e6)
+    a.set_frequency(1234.5)
+    x = clean.copy()
+    x[100] = np.nan
+    rec = a.estimate(x, apply=True)
+    assert rec["applied"] == 0 and a.inc == sp.inc_from_hz(1234.5, 1.25e6) and (a.estimates, a.applied) == (1, 0)
+
+
+def test_samples_that_are_not_read_do_not_count():
+    """The n mod R samples behind the last whole pre-sum, and everything beyond (M + 1) * 2048 * R once `segments` caps M."""
+    fs = 5e6
+    x = ac.tone(300, 5, 65536, 4)
+    want = sp.estimate(x, fs, pre_sum=4)
+    tail = np.concatenate([x, np.full(3, np.nan, np.complex64)])
+    assert want["status"] == sp.OK and same_record(sp.estimate(tail, fs, pre_sum=4), want)
+    tail[4 * 65536 - 1] = np.nan                            # the last sample that is read
+    assert sp.estimate(tail, fs, pre_sum=4)["status"] == sp.WEAK
+    clean = ac.samples("a")                                 # 2^20 samples, 511 segments
+    want = sp.estimate(clean, 1.25e6, max_segments=31)
+    x = clean.copy()
+    x[32 * 2048:] = np.nan
+    assert want["status"] == sp.OK and want["segments"] == 31 and same_record(sp.estimate(x, 1.25e6, max_segments=31), want)
+    x[32 * 2048 - 1] = np.nan
+    assert sp.estimate(x, 1.25e6, max_segments=31)["status"] == sp.WEAK
 
 
 # ---- the mix ---------------------------------------------------------------------------------------------------------------
