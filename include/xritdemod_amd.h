@@ -1441,6 +1441,133 @@ int xrit_jpeg_encode_resident(xrit_jpeg *j, const xrit_product_image *image, uin
                               xrit_jpeg_result *result);
 
 /* ------------------------------------------------------------------------
+ * JPEG decoder: a batch of baseline JPEG streams in device memory -> the
+ * pixels libjpeg gives for them (tests/jpegdec_spec.py
+ * is the specification).  The data field of an LRIT/HRIT image file whose
+ * image structure record has compression flag 2 is such a stream.
+ *
+ *  - input: the streams lie in one byte buffer; each is named by a record
+ *    that begins {uint64 offset; uint32 length}, `stride` bytes apart (a
+ *    multiple of 4, at least 12), as for xrit_rice_decode_device: an
+ *    xrit_file_piece or a record of the caller's.  A record that reaches
+ *    outside the buffer is XRIT_JPEGDEC_DAMAGED.
+ *  - accepted: baseline sequential DCT (SOF0), 8-bit samples; one component,
+ *    or three components all sampled 1 x 1, taken as YCbCr; any DQT with 8-bit
+ *    entries in any of the four slots; any DHT in any of the four slots whose
+ *    DC symbols are 0 .. 11 and whose AC symbols have a size of 0 .. 10; DRI
+ *    of any value with RSTm markers; APPn, COM and other segments with a
+ *    length are skipped; bytes behind EOI are ignored, a missing EOI too.
+ *  - output: the pixels of every image back to back in item order, rows tight
+ *    (columns * components bytes; three components: interleaved RGB through
+ *    libjpeg's fixed-point YCbCr -> RGB), each image padded with zeros to a
+ *    multiple of 4 bytes; one xrit_jpegdec_record per item; one summary.
+ *    An image is written iff offset + padded length <= cap; the summary has
+ *    the true total and overflow = 1 otherwise.  An image with a non-zero
+ *    status that has a geometry (the statuses from 4 on) takes its room and
+ *    its pixel bytes are all zero; the others have length 0 and offset 0.
+ *  - arithmetic: jidctint operation for operation (columns descaled by 11,
+ *    rows by 18, 13-bit constants), samples clip(v + 128, 0, 255), in 32-bit
+ *    two's complement; the DC predictor is kept in 16 bits.
+ *  - the statuses are those of the SERIAL walk: the first thing wrong in the
+ *    order header chain, then per restart interval its bits, then the marker
+ *    behind it.
+ *      0 OK
+ *      1 UNSUPPORTED  a JPEG this stage does not decode: progressive, extended,
+ *                     lossless or hierarchical SOF, arithmetic coding, 12-bit
+ *                     samples, 16-bit quantiser entries, subsampled components,
+ *                     2 or 4 and more components, a scan that does not name
+ *                     every component (several scans)
+ *      2 DAMAGED      the chain SOI .. SOS is broken: no SOI, a segment that
+ *                     runs past `length`, no SOF in front of SOS, dimensions of
+ *                     0, SOS naming a table never defined, a DHT that is no
+ *                     prefix code or has symbols out of range
+ *      3 TOO_LARGE    more than 2^22 blocks of 8 x 8 in the image; or the item
+ *                     brings the call's running total of blocks above
+ *                     max_blocks or of entropy-coded bytes above n_bytes (only
+ *                     overlapping items can): it and every sound item behind it
+ *      4 BAD_CODE     16 bits that begin no code
+ *      5 INDEX        a coefficient index past 63
+ *      6 SHORT        a restart interval out of bits before its MCUs
+ *      7 INTERVALS    fewer or more restart intervals than the geometry asks for
+ *      8 RST_ORDER    an RSTm out of sequence
+ *      9 MARKER       a marker other than RSTm or EOI in the scan
+ *    Damage never changes a neighbouring image.  No byte outside the buffers
+ *    handed over is read or written for any input bytes whatever.
+ *  - the handle owns only scratch and the form: no state between calls, so the
+ *    stage queues in front of xrit_product_*, xrit_geo_* and xrit_jpeg_* on one
+ *    stream; describe an image to them with an xrit_product_image {d_pixels +
+ *    offset, columns, rows, pitch = columns * components, bits = 8}.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_jpegdec xrit_jpegdec;
+#define XRIT_JPEGDEC_OK          0
+#define XRIT_JPEGDEC_UNSUPPORTED 1
+#define XRIT_JPEGDEC_DAMAGED     2
+#define XRIT_JPEGDEC_TOO_LARGE   3
+#define XRIT_JPEGDEC_BAD_CODE    4
+#define XRIT_JPEGDEC_INDEX       5
+#define XRIT_JPEGDEC_SHORT       6
+#define XRIT_JPEGDEC_INTERVALS   7
+#define XRIT_JPEGDEC_RST_ORDER   8
+#define XRIT_JPEGDEC_MARKER      9
+#define XRIT_JPEGDEC_STATUSES    10
+#define XRIT_JPEGDEC_MAX_BLOCKS  (1u << 22)
+#define XRIT_JPEGDEC_DEFAULT_BLOCKS (1u << 16)
+#define XRIT_JPEGDEC_MAX_BYTES   (1u << 28)   /* n_bytes of one call */
+#define XRIT_JPEGDEC_MAX_ITEMS   (1u << 20)
+typedef struct xrit_jpegdec_record {
+    uint64_t offset;                 /* of the image's pixels in the output */
+    uint64_t length;                 /* columns * rows * components, without the padding */
+    uint32_t columns, rows, components;
+    uint32_t restart;                /* the DRI value */
+    uint32_t intervals;              /* restart intervals found in the scan */
+    uint32_t status;
+    uint32_t reserved[6];
+} xrit_jpegdec_record;               /* 64 bytes */
+typedef struct xrit_jpegdec_summary {
+    uint64_t images;                 /* items with status 0 */
+    uint64_t bytes;                  /* pixel bytes of all items with their padding, whether or not they fitted */
+    uint32_t by_status[XRIT_JPEGDEC_STATUSES];
+    uint32_t overflow;               /* 1: an image did not fit below cap */
+    uint32_t reserved;
+} xrit_jpegdec_summary;              /* 64 bytes */
+typedef struct xrit_jpegdec_info {
+    uint32_t columns, rows, components, restart, status;
+    uint32_t scan_offset;            /* the first byte behind SOS */
+    uint32_t blocks, intervals;      /* what the geometry asks for */
+} xrit_jpegdec_info;                 /* 32 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path".  A new handle has form 1 and subsequences of 1024 bits. */
+int xrit_jpegdec_create(xrit_jpegdec **d, int device);
+int xrit_jpegdec_destroy(xrit_jpegdec *d);
+/* waits for the handle's last call; the form stays */
+int xrit_jpegdec_reset(xrit_jpegdec *d);
+/* The entropy decoder's form.  0: one lane per restart interval, the plain serial walk.  1: one wave per interval, the
+ * interval cut into subsequences of subsequence_bits (32 .. 2^20, 0: 1024) that 64 lanes walk from guessed states until
+ * the states are the serial walk's.  Both give the same coefficients bit for bit.  Anything else: XRIT_E_INVALID. */
+int xrit_jpegdec_set_form(xrit_jpegdec *d, uint32_t form, uint32_t subsequence_bits);
+/* Host only, no device is touched: the header chain of one stream in host memory -> its geometry and status (0, 1, 2 or 3),
+ * so that a caller can size the output: an image takes columns * rows * components bytes rounded up to 4. */
+int xrit_jpegdec_header(const uint8_t *data, size_t length, xrit_jpegdec_info *info);
+/* device pointers, asynchronous on `stream` (0: the null stream); no host synchronisation once the scratch has its size for
+ * (n_items, n_bytes, max_blocks).  max_blocks: the blocks of 8 x 8 of all components the call's scratch, grids and scans
+ * are sized for (0: XRIT_JPEGDEC_DEFAULT_BLOCKS = 2^16, a 2048 x 2048 grey image; give the batch's own bound, from
+ * xrit_jpegdec_header, for more).  The scratch costs about 132 bytes per block of max_blocks (128 of them the int16
+ * coefficients: 8.6 MB at the default, 554 MB at 2^22), 3.5 bytes per byte of n_bytes and 5.6 KB per item.  NULL pointers (d_bytes, d_items with n_items 0 and d_pixels with cap 0 excepted), n_bytes above 2^28, n_items
+ * above 2^20, max_blocks above 2^22, a stride below 12 or no multiple of 4, records or a summary that are not 8-byte
+ * aligned: XRIT_E_INVALID, nothing queued, nothing written. */
+int xrit_jpegdec_decode_device(xrit_jpegdec *d, const uint8_t *d_bytes, size_t n_bytes, const void *d_items, size_t stride, size_t n_items,
+                               size_t max_blocks, uint8_t *d_pixels, size_t cap, xrit_jpegdec_record *d_records,
+                               xrit_jpegdec_summary *d_summary, void *stream);
+/* host buffers: the bytes and the records are uploaded, the scratch is sized from the headers (read on the host), the
+ * summary and the records are downloaded, then the pixel bytes up to the end of the last image that fitted.
+ * XRIT_E_CAPACITY when an image did not fit: the records are all there, the pixels of the images that fitted are written,
+ * the room of one that did not is left as it was. */
+int xrit_jpegdec_decode(xrit_jpegdec *d, const uint8_t *bytes, size_t n_bytes, const void *items, size_t stride, size_t n_items, uint8_t *pixels,
+                        size_t cap, xrit_jpegdec_record *records, xrit_jpegdec_summary *summary);
+/* after the handle's last call (waits for it): the most rounds a tile of 64 subsequences took in form 1 (0 in form 0) */
+int xrit_jpegdec_rounds(xrit_jpegdec *d, uint32_t *rounds);
+
+/* ------------------------------------------------------------------------
  * Carrier acquisition: a stage IN FRONT of the chain that finds a large carrier
  * offset and takes it out on the device (DESIGN.md section 21;
  * tests/acquire_spec.py is the specification).  The reference has no such

@@ -29,6 +29,7 @@ from ._capi import (  # noqa: F401
     ImageProjector, GEO_NAV_DTYPE, GEO_GRID_DTYPE, GEO_POINT_DTYPE, GEO_SUMMARY_DTYPE, GEO_KINDS, GEO_MODES, GEO_MAX_DIM, GEO_OFF,
     GEO_EQUIRECT, GEO_MERCATOR, GEO_NEAREST, GEO_BILINEAR, geo_nav, geo_grid_tables, geo_parse_navigation, geo_pixel_to_lonlat,
     JpegEncoder, JPEG_RESULT_DTYPE, JPEG_MAX_BLOCKS, jpeg_bound, jpeg_quality_tables, jpeg_header,
+    JpegDecoder, JPEGDEC_RECORD_DTYPE, JPEGDEC_SUMMARY_DTYPE, JPEGDEC_INFO_DTYPE, JPEGDEC_ITEM_DTYPE, JPEGDEC_MAX_BLOCKS, jpegdec_header,
     CarrierAcquirer, ACQUIRE_PARAMS_DTYPE, ACQUIRE_RECORD_DTYPE, ACQUIRE_STATE_DTYPE, ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK,
     LinkMonitor, MONITOR_BLOCK_DTYPE, MONITOR_SUMMARY_DTYPE, MONITOR_STATE_DTYPE, MONITOR_QUALITY_DTYPE, SYMBOL_F32, SYMBOL_I8,
     MONITOR_NO_SIGNAL, MONITOR_NO_NOISE,

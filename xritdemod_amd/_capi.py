@@ -191,6 +191,14 @@ _SIGNATURES = {
     "xrit_jpeg_encode_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp, _vp]),
     "xrit_jpeg_encode": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp]),
     "xrit_jpeg_encode_resident": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp]),
+    "xrit_jpegdec_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_jpegdec_destroy": (C.c_int, [_vp]),
+    "xrit_jpegdec_reset": (C.c_int, [_vp]),
+    "xrit_jpegdec_set_form": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "xrit_jpegdec_header": (C.c_int, [_vp, _sz, _vp]),
+    "xrit_jpegdec_decode_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "xrit_jpegdec_decode": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "xrit_jpegdec_rounds": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "xrit_acquire_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int]),
     "xrit_acquire_destroy": (C.c_int, [_vp]),
     "xrit_acquire_reset": (C.c_int, [_vp]),
@@ -2032,6 +2040,94 @@ class JpegEncoder(_Handle):
     def reset(self):
         """Waits for the last call; the parameters stay."""
         _check(lib().xrit_jpeg_reset(self._h))
+
+
+# ---- JPEG decoder (DESIGN.md section 27) ---------------------------------------------------------------------------------
+(JPEGDEC_OK, JPEGDEC_UNSUPPORTED, JPEGDEC_DAMAGED, JPEGDEC_TOO_LARGE, JPEGDEC_BAD_CODE, JPEGDEC_INDEX, JPEGDEC_SHORT, JPEGDEC_INTERVALS,
+ JPEGDEC_RST_ORDER, JPEGDEC_MARKER) = range(10)
+JPEGDEC_MAX_BLOCKS = 1 << 22
+# xrit_jpegdec_record, xrit_jpegdec_summary, xrit_jpegdec_info
+JPEGDEC_RECORD_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint64), ("columns", np.uint32), ("rows", np.uint32), ("components", np.uint32),
+                                 ("restart", np.uint32), ("intervals", np.uint32), ("status", np.uint32), ("reserved", np.uint32, 6)])
+JPEGDEC_SUMMARY_DTYPE = np.dtype([("images", np.uint64), ("bytes", np.uint64), ("by_status", np.uint32, 10), ("overflow", np.uint32),
+                                  ("reserved", np.uint32)])
+JPEGDEC_INFO_DTYPE = np.dtype([("columns", np.uint32), ("rows", np.uint32), ("components", np.uint32), ("restart", np.uint32), ("status", np.uint32),
+                               ("scan_offset", np.uint32), ("blocks", np.uint32), ("intervals", np.uint32)])
+# the record that names a stream: it begins {uint64 offset; uint32 length}
+JPEGDEC_ITEM_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint32), ("reserved", np.uint32)])
+assert JPEGDEC_RECORD_DTYPE.itemsize == 64 and JPEGDEC_SUMMARY_DTYPE.itemsize == 64 and JPEGDEC_INFO_DTYPE.itemsize == 32
+
+
+def jpegdec_header(data):
+    """The header chain of one JPEG stream -> a JPEGDEC_INFO_DTYPE record: geometry and status (0 .. 3).  Plain host code."""
+    a = np.frombuffer(bytes(data), np.uint8)
+    info = np.zeros(1, JPEGDEC_INFO_DTYPE)
+    _check(lib().xrit_jpegdec_header(_p(a) if len(a) else None, len(a), _p(info)))
+    return info[0]
+
+
+class JpegDecoder(_Handle):
+    """A batch of baseline JPEG streams -> the pixels libjpeg gives for them, back to back, one JPEGDEC_RECORD_DTYPE per
+    stream and a summary.  One component, or three sampled 1 x 1 (YCbCr -> interleaved RGB).  form 0: a lane per restart
+    interval; form 1: a wave per interval over subsequences of subsequence_bits.  The handle owns scratch and the form;
+    tests/jpegdec_spec.py is the specification."""
+    _destroy = "xrit_jpegdec_destroy"
+
+    def __init__(self, form=1, subsequence_bits=0, device=0):
+        super().__init__()
+        _check(lib().xrit_jpegdec_create(C.byref(self._h), device))
+        self.set_form(form, subsequence_bits)
+
+    def set_form(self, form, subsequence_bits=0):
+        _check(lib().xrit_jpegdec_set_form(self._h, form, subsequence_bits))
+
+    def decode(self, data, items, cap=None):
+        """data: the bytes that hold the streams; items: (offset, length) pairs, or an array whose records begin
+        {uint64 offset; uint32 length}.  -> (pixels uint8, records, summary).  cap: the room for the pixels (default: what
+        the headers ask for); XritError -5 when an image did not fit (the records and the summary are in the error's
+        `records` and `summary`, the prefix that fitted in `pixels`)."""
+        a = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        if isinstance(items, np.ndarray) and items.dtype.fields:
+            rec = np.ascontiguousarray(items)
+        else:
+            rec = np.zeros(len(items), JPEGDEC_ITEM_DTYPE)
+            for i, (offset, length) in enumerate(items):
+                rec[i] = (offset, length, 0)
+        if cap is None:
+            cap = 0
+            for r in rec:
+                off, n = int(r["offset"]), int(r["length"])
+                if off <= len(a) and n <= len(a) - off:
+                    info = jpegdec_header(a[off:off + n])
+                    if info["status"] == 0:
+                        cap += (int(info["columns"]) * int(info["rows"]) * int(info["components"]) + 3) & ~3
+        pixels, records, summary = np.zeros(max(cap, 1), np.uint8), np.zeros(len(rec), JPEGDEC_RECORD_DTYPE), np.zeros(1, JPEGDEC_SUMMARY_DTYPE)
+        rc = lib().xrit_jpegdec_decode(self._h, _p(a) if len(a) else None, len(a), _p(rec) if len(rec) else None, rec.dtype.itemsize, len(rec),
+                                       _p(pixels) if cap else None, cap, _p(records) if len(rec) else None, _p(summary))
+        if rc == -5:
+            err = XritError(rc, lib().xrit_last_error().decode("utf-8", "replace"))
+            err.pixels, err.records, err.summary = pixels[:cap], records, summary[0]
+            raise err
+        _check(rc)
+        return pixels[:min(cap, int(summary[0]["bytes"]))], records, summary[0]
+
+    def decode_device(self, d_bytes_ptr, n_bytes, d_items_ptr, stride, n_items, d_pixels_ptr, cap, d_records_ptr, d_summary_ptr, max_blocks=0,
+                      stream=None):
+        """Device pointers; asynchronous on stream, no host synchronisation once the scratch has its size: may be queued in
+        front of ImageProduct, ImageProjector and JpegEncoder calls that read the pixels in place."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_jpegdec_decode_device(self._h, v(d_bytes_ptr), n_bytes, v(d_items_ptr), stride, n_items, max_blocks, v(d_pixels_ptr), cap,
+                                                v(d_records_ptr), v(d_summary_ptr), v(stream)))
+
+    def rounds(self):
+        """The most rounds a tile of 64 subsequences took in the last call (form 1; waits for the call)."""
+        n = C.c_uint32()
+        _check(lib().xrit_jpegdec_rounds(self._h, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """Waits for the last call; the form stays."""
+        _check(lib().xrit_jpegdec_reset(self._h))
 
 
 # ---- carrier acquisition (DESIGN.md section 21) -------------------------------------------------------------------------

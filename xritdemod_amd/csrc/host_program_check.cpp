@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "../host/jpeg_files.h"
 #include "../host/outputs.h"
 #include "../host/sinks.h"
 #include "../host/source.h"
@@ -305,6 +306,28 @@ static int check_queue(const std::string &dir)
     return 0;
 }
 
+// jpeg_files.h: the option, where the data field begins, PNM
+static int check_jpeg_files(const std::string &dir)
+{
+    FilesJpegOption o;
+    CHECK(!o.flag("--files") && !o.flag("--files-jpegs") && !o.on && o.refused(false) == nullptr);
+    CHECK(o.flag("--files-jpeg") && o.on && o.refused(true) == nullptr);
+    CHECK(std::string(o.refused(false)) == "--files-jpeg needs --files DIR\n");
+    size_t n = 7;
+    CHECK(data_field(16, 2, 16, &n) == 16 && n == 0);                  // headers only
+    CHECK(data_field(25, 2, 1000, &n) == 25 && n == 975);
+    CHECK(data_field(25, 1, 1000, &n) == 0 && n == 0 && data_field(25, 0, 1000, &n) == 0 && n == 0);     // the chain was not walked
+    CHECK(data_field(1001, 2, 1000, &n) == 0 && n == 0 && data_field(15, 2, 1000, &n) == 0 && n == 0);
+    CHECK(pnm_header(1, 9, 7) == "P5\n9 7\n255\n" && pnm_header(3, 65535, 1) == "P6\n65535 1\n255\n");
+    CHECK(std::string(pnm_suffix(1)) == ".pgm" && std::string(pnm_suffix(3)) == ".ppm");
+    const uint8_t px[12] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12};
+    CHECK(write_pnm(dir + "/a.pgm", px, 1, 3, 2) && slurp(dir + "/a.pgm") == std::string("P5\n3 2\n255\n\x01\x02\x03\x04\x05\x06", 17));
+    CHECK(write_pnm(dir + "/a.ppm", px, 3, 2, 2) && slurp(dir + "/a.ppm") == "P6\n2 2\n255\n" + std::string(reinterpret_cast<const char *>(px), 12));
+    Quiet quiet(dir + "/stderr_pnm.txt");
+    CHECK(!write_pnm(dir + "/none/a.pgm", px, 1, 3, 2));
+    return 0;
+}
+
 int main()
 {
     char pattern[] = "/tmp/host_program_check.XXXXXX";
@@ -312,7 +335,7 @@ int main()
     CHECK(made != nullptr);
     const std::string dir = made;
     const int rc = check_pgm(dir) || check_names() || check_journal(dir) || check_packet_files(dir) || check_fifo(dir) ||
-                   check_read_ahead() || check_queue(dir);
+                   check_read_ahead() || check_queue(dir) || check_jpeg_files(dir);
     fs::remove_all(dir);
     if (rc == 0) std::printf("host_program_check: ok\n");
     return rc;

@@ -587,6 +587,43 @@ struct JpegScratch {
 size_t jpeg_scratch_carve(void *p, uint32_t blocks, uint32_t n_int, JpegScratch &sc);
 int launch_jpeg(const JpegPar &p, const JpegHeader &h, const JpegScratch &sc, unsigned char *out, size_t cap, xrit_jpeg_result *result,
                 hipStream_t s);
+// JPEG decoder stage (jpegdec.hip; jpegdec_rule.h is the rule per value): one call on n_items streams in `bytes`; the scratch
+// for that many items, max_scan bytes of entropy-coded data and max_blocks blocks
+struct JpegDecPar {
+    const unsigned char *bytes;
+    unsigned long long n_bytes;
+    const unsigned char *items;             // {uint64 offset; uint32 length} every `stride` bytes
+    unsigned long long stride;
+    uint32_t n_items, max_blocks, max_scan;
+    uint32_t form, S;                       // 0: a lane per restart interval; 1: a wave per interval, subsequences of S bits
+    unsigned char *pixels;
+    unsigned long long cap;
+    xrit_jpegdec_record *records;
+    xrit_jpegdec_summary *summary;
+};
+struct JpegDecItem;
+struct JpegDecHuff;
+struct JpegDecSum;
+struct JpegDecScratch {
+    JpegDecItem *item;                      // [n_items] what the header kernel found, the final status
+    uint32_t *bbase, *mbase, *ibase, *sbase;        // [n_items + 1] blocks, MCUs, intervals (one more each), scan bytes in front of an item
+    uint32_t *kbase, *rbase;                // [n_items + 1] unstuffed bytes, RSTm markers in front of an item
+    unsigned long long *obase;              // [n_items + 1] pixel bytes in front of an item
+    unsigned long long *tot;                // [8] those sums over the items the call takes
+    JpegDecSum *item_aggs;
+    JpegDecHuff *huff;                      // [n_items][6] per component its DC and AC table
+    unsigned char *q;                       // [n_items][3][64] per component its quantiser table, natural order
+    unsigned char *un;                      // [max_scan] the unstuffed scan bytes of all items
+    uint32_t *rst_pos;                      // [max_scan / 2 + 1] per RSTm the unstuffed bytes in front of it
+    unsigned char *rst_m;                   // its m
+    unsigned long long *un_aggs;
+    int16_t *coef;                          // [max_blocks][64] zigzag order
+    uint32_t *ifault;                       // [max_blocks + n_items] per interval its fault
+    uint4 *dc_aggs;
+    uint32_t *rounds;                       // the most rounds a tile of form 1 took
+};
+size_t jpegdec_scratch_carve(void *p, uint32_t n_items, uint32_t max_scan, uint32_t max_blocks, JpegDecScratch &sc);
+int launch_jpegdec(const JpegDecPar &p, const JpegDecScratch &sc, hipStream_t s);
 // carrier acquisition (acquire.hip; acquire_host.h has the sizes): the handle's state is one xrit_acquire_state; the scratch
 // of an estimate of M segments
 struct AcquireScratch {

@@ -8,9 +8,11 @@
 #include <string>
 
 #include "../../include/xritdemod_amd.h"
+#include "jpeg_files.h"
 #include "source.h"
 
 struct Options {
+    FilesJpegOption files_jpeg;    // --files-jpeg: with --files, image files with compression flag 2 decoded to DIR/STEM.pgm / .ppm (xrit_jpegdec_*)
     std::string mode = "lrit";
     std::string input;
     std::string format = "cf32";
@@ -91,6 +93,9 @@ inline void usage()
                  "         [--files-decompress]   (with --files: image files whose headers say Rice compression -- one coded line per packet behind a\n"
                  "                                 header-only first packet -- are also decoded on the GPU to ..._{serial}.img: lines x columns raw\n"
                  "                                 samples, uint8 or little-endian uint16; a line that faults is written as decoded and counted)\n"
+                 "         [--files-jpeg]         (with --files: an image file whose headers say compression 2 carries a baseline JPEG stream in its\n"
+                 "                                 data field; when it ends it is decoded on the GPU to ..._{serial}.pgm, or .ppm for three\n"
+                 "                                 components; a stream that does not decode writes nothing and gets a line on stderr)\n"
                  "         [--canvas [--canvas-slots N] [--canvas-mib M]]   (with --files-decompress: GOES sends an image as several segment files;\n"
                  "                                 their lines are placed into full images on the GPU by the segment identification record\n"
                  "                                 (type 128) and every image that is complete is written to DIR/<annotation text>.pgm (binary PGM,\n"
@@ -245,7 +250,7 @@ inline bool parse(int argc, char **argv, Options &o)
         }
         for (const SwitchFlag &f : SWITCH_FLAGS)
             if (a == f.name) known = o.*f.field = true;
-        if (known) continue;
+        if (known || o.files_jpeg.flag(a)) continue;
         if (a == "--product-tone") { if (!(v = need()) || !parse_tone(v, o.product)) return false; o.product_flags = true; }
         else if (a == "--product-factor") {
             if (!(v = need())) return false;
@@ -295,6 +300,7 @@ inline bool parse(int argc, char **argv, Options &o)
         return refuse("--stream-sync needs --decode, --channels, --decoder-stats, --packets or --files\n");
     if (o.files_decompress && o.files.empty())
         return refuse("--files-decompress needs --files DIR\n");
+    if (const char *why = o.files_jpeg.refused(!o.files.empty())) return refuse("%s", why);
     if (o.canvas && (!o.files_decompress || o.canvas_slots < 1 || o.canvas_slots > XRIT_CANVAS_MAX_SLOTS || o.canvas_mib < 1 || o.canvas_mib > 4096))
         return refuse("--canvas needs --files DIR --files-decompress; --canvas-slots 1..%d, --canvas-mib 1..4096\n", XRIT_CANVAS_MAX_SLOTS);
     if ((o.products && !o.canvas) || (o.product_flags && !o.products))

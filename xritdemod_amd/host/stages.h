@@ -395,6 +395,45 @@ struct Jpeg {
     void report() const { std::fprintf(stderr, "jpeg: %zu files of quality %d, %zu bytes\n", written, quality, bytes); }
 };
 
+// --files-jpeg: the data field of a finished STEM.lrit whose headers say compression 2, decoded to STEM.pgm / STEM.ppm
+struct JpegFiles {
+    Handle<xrit_jpegdec, xrit_jpegdec_destroy> jd;
+    std::vector<uint8_t> file, pixels;
+    size_t written = 0, refused = 0;
+
+    bool write(const std::string &stem, const xrit_file_record &r)
+    {
+        FILE *f = std::fopen((stem + ".lrit").c_str(), "rb");
+        if (!f) { std::perror((stem + ".lrit").c_str()); return false; }
+        file.resize((size_t)(r.file_offset + r.length));
+        const bool whole = std::fread(file.data(), 1, file.size(), f) == file.size();
+        std::fclose(f);
+        if (!whole) { std::perror((stem + ".lrit").c_str()); return false; }
+        size_t n = 0;
+        const size_t at = data_field(r.header_length, r.header_state, file.size(), &n);
+        xrit_jpegdec_info info{};
+        info.status = XRIT_JPEGDEC_DAMAGED;
+        if (n && xrit_jpegdec_header(file.data() + at, n, &info) != XRIT_OK) return fail("files-jpeg");
+        xrit_jpegdec_record rec{};
+        rec.status = info.status;
+        if (info.status == XRIT_JPEGDEC_OK) {
+            struct { uint64_t offset; uint32_t length, pad; } item{0, (uint32_t)n, 0};
+            xrit_jpegdec_summary summary{};
+            pixels.resize(((size_t)info.columns * info.rows * info.components + 3) & ~(size_t)3);
+            if (xrit_jpegdec_decode(jd, file.data() + at, n, &item, sizeof item, 1, pixels.data(), pixels.size(), &rec, &summary) != XRIT_OK)
+                return fail("files-jpeg");
+        }
+        if (rec.status != XRIT_JPEGDEC_OK) {
+            ++refused;
+            std::fprintf(stderr, "files-jpeg: %s.lrit: status %u, nothing written\n", stem.c_str(), rec.status);
+            return true;
+        }
+        ++written;
+        return write_pnm(stem + pnm_suffix(rec.components), pixels.data(), rec.components, rec.columns, rec.rows);
+    }
+    void report() const { std::fprintf(stderr, "files-jpeg: %zu images written, %zu streams refused\n", written, refused); }
+};
+
 // --products: a slot's pixels toned and reduced where they lie; the two products are what is downloaded
 struct Products {
     Handle<xrit_product, xrit_product_destroy> pr;
@@ -521,6 +560,7 @@ struct DecodeChain {
     Products products;
     Jpeg jpeg;
     Projection projection;
+    JpegFiles jpeg_files;
 
     bool active() const { return decoder.dec || lock.lk; }
 
@@ -550,6 +590,7 @@ struct DecodeChain {
         if (xrit_files_create(&files.fa.p, device) != XRIT_OK) return library_error();
         if (!make_dir(o.files, "--files")) return false;
         files.dir = o.files;
+        if (o.files_jpeg.on && xrit_jpegdec_create(&jpeg_files.jd.p, device) != XRIT_OK) return library_error();
         decompress = o.files_decompress;
         if (!decompress) return true;
         if (xrit_images_create(&images.im.p, device) != XRIT_OK) return library_error();
@@ -604,6 +645,9 @@ struct DecodeChain {
             if (!journal_record(file_stem(files.dir, r.vcid, r.apid, r.key_serial), r.flags, r.n_pieces ? &body : nullptr, rice, lines.data(),
                                 lines.size()))
                 return false;
+            if (jpeg_files.jd && r.compression == 2 && (r.flags & XRIT_FILE_ENDS) && !(r.flags & XRIT_FILE_ABORTED) &&
+                !jpeg_files.write(file_stem(files.dir, r.vcid, r.apid, r.key_serial), r))
+                return false;
         }
         return true;
     }
@@ -641,6 +685,7 @@ struct DecodeChain {
         if (demux.dm) demux.report();
         if (files.fa) files.report();
         if (files.fa && decompress) images.report();
+        if (jpeg_files.jd) jpeg_files.report();
         if (canvas.cv) {
             size_t partial = 0;
             for (unsigned s = 0; s < canvas.n_slots; ++s)
