@@ -84,8 +84,9 @@ def test_loop_sincosf_is_the_cpu_chains(xa, oracle_mod):
 
 # ------------------------------------------------------------------------------------------------ stages
 @pytest.mark.parametrize("D,kind", [(1, "rrc"), (5, "lp5"), (32, "lp32"), (2, "rrc"), (3, "lp5"), (4, "short"), (16, "lp16"),
-                                    (6, "lp5"), (1, "short"), (7, "one")])
+                                    (6, "lp5"), (1, "short"), (7, "one"), (17, "lp16"), (25, "lp32"), (19, "short"), (33, "one")])
 def test_fir_exact_order_is_the_oracle_bit_for_bit(xa, oracle_mod, D, kind):
+    """(odd decimations from 17 up: one output per lane, nothing for a window walk to share -- fir_exact_kernel unskewed)"""
     o = oracle_mod
     taps = {"rrc": o.rrc_taps(1, 1.25e6, 293883, 0.5, 63), "lp5": o.lowpass_taps(1, 6.25e6, 625e3, 100e3),
             "lp32": o.lowpass_taps(1, 40e6, 625e3, 100e3), "short": np.array([0.5, -0.25, 0.125], np.float32),
@@ -196,20 +197,36 @@ CASES = {"C1": ("lrit", 1.25e6, 1, {}), "C2": ("lrit", 6.25e6, 5, {}),
 def test_chain_front_exact_2_every_stage_is_the_oracle(xa, oracle_mod, case):
     """keep_stages: decimator, AGC, matched filter and Costas outputs word for word; with the clock recovery relayed to
     closure (cfg.clock_exact = 1) the soft symbols too -- over several calls of a stream (state carried in every stage)."""
-    mode, fs, D, kw = CASES[case]
-    n = 400_000 * D
+    chain_stages_are_the_oracle(xa, oracle_mod, case, CASES[case], 400_000, front_exact=2, soft=True)
+
+
+def chain_stages_are_the_oracle(xa, oracle_mod, case, what, n_dec, front_exact, soft):
+    mode, fs, D, kw = what
+    n = n_dec * D
     x = synth_signal(n, fs_in=fs, **kw)
-    dem = xa.Demodulator(xa.Demodulator.config(mode, fs, D, front_exact=2, clock_exact=1))
+    dem = xa.Demodulator(xa.Demodulator.config(mode, fs, D, front_exact=front_exact, clock_exact=1))
     dem.keep_stages(True)
     od = oracle_mod.Demod(oracle_mod.config(mode, fs, D))
-    cuts = [0, 150_000 * D, 150_001 * D + (3 if D > 1 else 0), n]
+    cuts = [0, n_dec * 3 // 8 * D, (n_dec * 3 // 8 + 1) * D + (3 if D > 1 else 0), n]
     for a, b in zip(cuts[:-1], cuts[1:]):
+        if front_exact == 0:
+            assert dem.front_exact_for(b - a), (case, "a call of this size should take the exact twin", b - a)
         got, want = dem.process(x[a:b]), od.process(x[a:b])
         names = ["decimator", "agc", "rrc", "costas"] if D > 1 else ["agc", "rrc", "costas"]
         for nm in names:
             g, w = dem.stage(nm), od.stage(nm)
             assert same_words(g, w), (case, nm, a, b, first_diff(g, w), rms(g - w) if g.shape == w.shape else None)
-        assert same_words(got, want), (case, "soft symbols", a, b, first_diff(got, want))
+        if soft:
+            assert same_words(got, want), (case, "soft symbols", a, b, first_diff(got, want))
+
+
+@pytest.mark.parametrize("front_exact", [0, 2])
+def test_chain_at_decimation_17_every_stage_is_the_oracle(xa, oracle_mod, front_exact):
+    """LRIT at 21.25 Msps, decimation 17, a burst of 40 000 symbols (171 000 samples behind the decimator): an odd decimation
+    from 17 up, where the exact order takes fir_exact_kernel unskewed.  Asked for (cfg.front_exact = 2) and as a chain finds it
+    by default (cfg.front_exact = 0: calls below a million symbols go through the exact twin) the decimator, AGC, matched
+    filter and Costas outputs are the oracle's word for word."""
+    chain_stages_are_the_oracle(xa, oracle_mod, "LRIT/17", ("lrit", 21.25e6, 17, {}), 171_000, front_exact=front_exact, soft=False)
 
 
 @pytest.mark.parametrize("case", ["C1", "C2", "C3", "C5"])

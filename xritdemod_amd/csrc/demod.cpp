@@ -348,7 +348,7 @@ static int front_end(xrit_demod *d, const void *in, size_t n, int type, int set,
     const bool agc_fused = !ex && D > 1 && length > 0 && d->dec.agc_supported();
     if (D > 1) {
         AgcEpilogue epi{};
-        if (agc_fused) XR_TRY(d->agc.fused_begin(length, d->dec.RC, s, &epi));
+        if (agc_fused) XR_TRY(d->agc.fused_begin(length, d->dec.plan.RC, s, &epi));
         XR_TRY(d->dec.run(in, type, A, length, s, prof, nullptr, 0, agc_fused ? &epi : nullptr, nullptr, ex));          // :138
         cur = A;
     } else if (type != XRIT_SAMPLE_FLOATIQ) {
@@ -361,7 +361,7 @@ static int front_end(xrit_demod *d, const void *in, size_t n, int type, int set,
     XR_TRY(keep_stage(d, 0, cur, length, s));
     // ... and when nobody asks for the AGC output itself, the matched filter applies the gains while it fills its
     // window: the AGC then costs the stream no sweep of its own at all
-    const bool agc_in_rrc = agc_fused && !d->keep_stages && d->rrc.agc_fill_supported(d->dec.RC);
+    const bool agc_in_rrc = agc_fused && !d->keep_stages && d->rrc.agc_fill_supported(d->dec.plan.RC);
     // no decimator (C1, C3), or one whose kernel has no such epilogue (the polyphase one, C5): the run maps come
     // from one read-only sweep, the rest is the same
     const bool agc_in_rrc_d1 = !ex && !agc_fused && length > 0 && !d->keep_stages && d->rrc.agc_fill_supported(3);
@@ -371,9 +371,9 @@ static int front_end(xrit_demod *d, const void *in, size_t n, int type, int set,
         XR_TRY(d->bufC[set].reserve((length + 8) * sizeof(float2)));
         Cfb = d->bufC[set].as<float2>();
         if (agc_in_rrc_d1) XR_TRY(d->agc.fused_reduce(cur, length, 3, s, prof));
-        XR_TRY(d->agc.fused_scan(cur, Cfb, length, agc_in_rrc ? d->dec.RC : 3, s, prof, &fill));    // :143
+        XR_TRY(d->agc.fused_scan(cur, Cfb, length, agc_in_rrc ? d->dec.plan.RC : 3, s, prof, &fill));    // :143
     }
-    else if (agc_fused) XR_TRY(d->agc.fused_finish(cur, B, length, d->dec.RC, s, prof));
+    else if (agc_fused) XR_TRY(d->agc.fused_finish(cur, B, length, d->dec.plan.RC, s, prof));
     else XR_TRY(d->agc.run(cur, B, length, s, prof, ex));
     XR_TRY(keep_stage(d, 1, B, length, s));
     // the RRC epilogue leaves the per-chain statistic of the Costas guess, the Costas final pass the

@@ -738,6 +738,16 @@ fir_exact_kernel(const void *__restrict__ in, const float2 *__restrict__ hist, f
     }
 }
 
+// ---- the stage: a plan (fir_plan.h) made once, the tap image it names, the history, and one checked dispatch ---------------
+static_assert(AGC_RUN_MAX_PER_LANE >= 5, "a window walk gives a lane up to five outputs, and the AGC epilogue a run per wave");
+
+static int fir_upload(DevBuf &to, const std::vector<float> &image)
+{
+    XR_TRY(to.reserve(image.size() * sizeof(float)));
+    XR_HIP(hipMemcpy(to.p, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
+    return XRIT_OK;
+}
+
 int FirStage::init(const float *taps, int ntaps, int decim)
 {
     taps_host.assign(taps, taps + ntaps);
@@ -752,116 +762,21 @@ int FirStage::init(const float *taps, int ntaps, int decim)
     }
 
     // diagnostic switches are read once, here: never on the launch path (a host that calls setenv races with getenv)
-    no_static_dec = getenv("XRIT_NO_STATIC_DEC") != nullptr;
-    no_static_mf = getenv("XRIT_NO_STATIC_MF") != nullptr;
+    FirKnobs knobs;
+    knobs.no_static_dec = getenv("XRIT_NO_STATIC_DEC") != nullptr;
+    knobs.no_static_mf = getenv("XRIT_NO_STATIC_MF") != nullptr;
 #ifdef XRIT_EXPERIMENTS
-    mfma_dec = getenv("XRIT_MFMA_DEC") != nullptr;
+    knobs.mfma_dec = getenv("XRIT_MFMA_DEC") != nullptr;
+    if (getenv("XRIT_DEC_THREADS")) knobs.dec_threads = atoi(getenv("XRIT_DEC_THREADS"));
 #endif
-    T = ntaps;
-    D = decim < 1 ? 1 : decim;
-    // measured at C2: five outputs per lane halve the decimator's occupancy (52 KiB window) and lose 45 %
-    if (D == 1) RC = 5;
-    else RC = 3;
-    // (cfg.front_exact = 2 at large decimations: one output per lane -- a window of 64 KiB then holds 128 outputs, four workgroups
-    // per CU; with three per lane it held 192 on ONE wave per workgroup and two waves per CU: 4.0 ms per C5 burst)
-    if (exact && D >= 16) RC = 1;
-    // large decimations whose phases map onto lanes take the polyphase kernel
-    poly = (D == 16 || D == 32 || D == 64) && (T + D - 1) / D <= POLY_NQ;
-    if (exact) {
-        // (cfg.front_exact = 2: fir_exact_kernel; the reversed taps, a tile of at most 64 KiB)
-        poly = false;
-        std::vector<float> r((size_t)T);
-        for (int i = 0; i < T; ++i) r[(size_t)i] = taps[T - 1 - i];
-        XR_TRY(rt.reserve(r.size() * sizeof(float)));
-        XR_HIP(hipMemcpy(rt.p, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
-        ex_pad = (D % 2) == 0;
-        ex_threads = 256;
-        ex_opt = D == 1 ? 4 : 2;
-        for (;;) {
-            const long long ob = (long long)ex_threads * ex_opt;
-            const long long tl = (ob - 1) * D + T;
-            const long long padded = ex_pad ? tl + tl / D + 2 : tl;
-            if (padded * 8 <= 64 * 1024 || (ex_threads == 64 && ex_opt == 1)) {
-                ex_tile_len = (int)tl;
-                ex_lds = (size_t)padded * 8;
-                break;
-            }
-            if (ex_opt > 1) --ex_opt; else ex_threads /= 2;
-        }
-        if (ex_lds > 160 * 1024) { set_error("FIR window of %d taps x decimation %d does not fit LDS", T, D); return XRIT_E_INVALID; }
+    plan = fir_plan(ntaps, decim, exact, knobs);
+    if (!plan.error.empty()) { set_error("%s", plan.error.c_str()); return XRIT_E_INVALID; }
+    XR_TRY(fir_upload(g, fir_tap_image(plan, taps, plan.taps)));
+    if (plan.key.mf) XR_TRY(fir_upload(mfb, fir_tap_image(plan, taps, FIR_TAPS_TOEPLITZ)));
+    for (DevBuf &h : hist) {
+        XR_TRY(h.reserve((size_t)(plan.T > 1 ? plan.T - 1 : 1) * sizeof(float2)));
+        XR_HIP(hipMemset(h.p, 0, h.bytes));
     }
-    if (poly) {
-        threads = XRIT_POLY_THREADS;
-        RC = 1;
-        pad = false;
-        const int OB = (threads / D) * POLY_PR;
-        tile_len = (POLY_NQ + OB - 1) * D + 2;
-        lds_bytes = (size_t)tile_len * sizeof(float2);
-        std::vector<float> hq((size_t)D * POLY_NQ, 0.0f);
-        for (int ph = 0; ph < D; ++ph)
-            for (int q = 0; q < POLY_NQ; ++q)
-                if (q * D + ph < T) hq[(size_t)ph * POLY_NQ + q] = taps[q * D + ph];
-        XR_TRY(g.reserve(hq.size() * sizeof(float)));
-        XR_HIP(hipMemcpy(g.p, hq.data(), hq.size() * sizeof(float), hipMemcpyHostToDevice));
-        XR_TRY(hist[0].reserve((size_t)(T > 1 ? T - 1 : 1) * sizeof(float2)));
-        XR_TRY(hist[1].reserve((size_t)(T > 1 ? T - 1 : 1) * sizeof(float2)));
-        XR_HIP(hipMemset(hist[0].p, 0, hist[0].bytes));
-        XR_HIP(hipMemset(hist[1].p, 0, hist[1].bytes));
-        cur = 0;
-        return XRIT_OK;
-    }
-    pad = ((RC * D) % 2) == 0;
-    W = T + (RC - 1) * D;
-    Wpad = (W + 3) & ~3;
-    std::vector<float> rows((size_t)RC * Wpad, 0.0f);
-    for (int c = 0; c < RC; ++c)
-        for (int i = 0; i < W; ++i) {
-            int k = T - 1 + c * D - i;
-            if (k >= 0 && k < T) rows[(size_t)c * Wpad + i] = taps[k];
-        }
-    XR_TRY(g.reserve(rows.size() * sizeof(float)));
-    XR_HIP(hipMemcpy(g.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (mfma_dec && T == 151 && D == 5) {
-        // the Toeplitz operand of the matrix-pipe experiment: step q, lane l -> H[4 q + (l >> 4)][l & 15] = g[s - 5 j]
-        const int KS = (15 * 5 + 151 + 3) / 4;
-        std::vector<float> hb((size_t)KS * 64, 0.0f);
-        for (int q = 0; q < KS; ++q)
-            for (int l = 0; l < 64; ++l) {
-                const int sp = 4 * q + (l >> 4) - 5 * (l & 15);
-                if (sp >= 0 && sp < T) hb[(size_t)q * 64 + l] = rows[(size_t)sp];
-            }
-        XR_TRY(mfb.reserve(hb.size() * sizeof(float)));
-        XR_HIP(hipMemcpy(mfb.p, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    // block size: keep the LDS window under 64 KiB
-    threads = 256;
-    // (XRIT_DEC_THREADS, read here, when the stage is created: the decimator's workgroup size for A/B runs -- smaller
-    // workgroups hold smaller windows, and more of them fit next to the relay's walkers)
-#ifdef XRIT_EXPERIMENTS
-    if (D > 1 && getenv("XRIT_DEC_THREADS")) {
-        const int t = atoi(getenv("XRIT_DEC_THREADS"));
-        if (t == 64 || t == 128 || t == 192 || t == 256) threads = t;
-    }
-#endif
-    for (;;) {
-        long long ob = (long long)threads * RC;
-        long long tl = (ob - 1) * D + T + (Wpad - W) + 8;
-        long long padded = pad ? tl + tl / D + 8 : tl;
-        if (padded * 8 <= 64 * 1024 || threads == 64) {
-            tile_len = (int)tl;
-            lds_bytes = (size_t)padded * 8;
-            break;
-        }
-        threads = threads == 192 ? 128 : threads / 2;
-    }
-    if (lds_bytes > 160 * 1024) {
-        set_error("FIR window of %d taps x decimation %d does not fit LDS", T, D);
-        return XRIT_E_INVALID;
-    }
-    XR_TRY(hist[0].reserve((size_t)(T > 1 ? T - 1 : 1) * sizeof(float2)));
-    XR_TRY(hist[1].reserve((size_t)(T > 1 ? T - 1 : 1) * sizeof(float2)));
-    XR_HIP(hipMemset(hist[0].p, 0, hist[0].bytes));
-    XR_HIP(hipMemset(hist[1].p, 0, hist[1].bytes));
     cur = 0;
     return XRIT_OK;
 }
@@ -876,106 +791,92 @@ int FirStage::reset(hipStream_t s)
     return XRIT_OK;
 }
 
-bool FirStage::agc_supported() const
-{
-    return !exact && !poly && !pad && threads % 64 == 0 && RC <= AGC_RUN_MAX_PER_LANE;      // one run per wave: 64 * RC outputs
-}
-
-bool FirStage::stat_supported(int statL) const
-{
-    // runs must not straddle blocks (the sums are taken from the block's outputs staged in LDS)
-    if (exact) return statL == 8;
-    if (poly) return false;
-    return statL > 0 && !pad && threads % 64 == 0 && (threads * RC) % statL == 0;
-}
-
 int FirStage::set_exact(bool on)
 {
     if (on == exact) return XRIT_OK;
     if (taps_host.empty()) { set_error("FIR: set_exact before init"); return XRIT_E_INVALID; }
     exact = on;
     const std::vector<float> t = taps_host;
-    return init(t.data(), (int)t.size(), D);
+    return init(t.data(), (int)t.size(), plan.D);
 }
 
 void FirStage::release()
 {
     if (twin) { twin->release(); delete twin; twin = nullptr; }
-    rt.release();
     g.release();
     mfb.release();
     hist[0].release();
     hist[1].release();
 }
 
-template <int RC, bool PAD>
-static int fir_launch_t(const FirStage &f, const void *in, int type, float2 *out, size_t n_out, size_t n_in,
-                        hipStream_t s, float2 *stat, int statL, const AgcEpilogue &agc)
+// What a launch passes, whatever the form; each kernel signature takes its part of it in fir_go.
+struct FirLaunch {
+    const FirPlan &p;
+    unsigned blocks;
+    size_t lds_bytes;
+    hipStream_t s;
+    const void *in;
+    const float2 *hist;
+    float2 *out;
+    const float *taps, *mfb;
+    long long n_out, n_in;
+    float2 *stat;
+    int stat_word;           // statL | (prio << 16)
+    AgcEpilogue agc;
+    AgcFill fill;
+    float2 *hist_new;
+};
+
+template <int FORM, int RC, bool PAD, int APL, int TS, int DS, bool MF, int TYPE>
+static void fir_go(const FirLaunch &a)
 {
-    const AgcFill af{};
-    unsigned blocks = div_up(n_out, (size_t)f.threads * RC);
-    const float2 *h = f.hist[f.cur].as<float2>();
-    const float *g = f.g.as<float>();
-#define XR_FIR_GO(TY)                                                                                          \
-    hipLaunchKernelGGL((fir_decim_kernel<RC, PAD, TY>), dim3(blocks), dim3(f.threads), f.lds_bytes, s, in, h,  \
-                       out, g, f.T, f.D, f.Wpad, (long long)n_out, (long long)n_in, f.tile_len, stat, statL | (f.prio << 16), agc, af, \
-                       f.T > 1 ? f.hist[f.cur ^ 1].as<float2>() : (float2 *)nullptr)
-#ifdef XRIT_EXPERIMENTS
-    if (RC == 3 && !PAD && f.T == 151 && f.D == 5 && type == XRIT_SAMPLE_FLOATIQ && f.mfma_dec && f.threads == 256)
-        hipLaunchKernelGGL((fir_decim_kernel<RC, PAD, XRIT_SAMPLE_FLOATIQ, 0, (RC == 3 && !PAD) ? 151 : 0, 5, (RC == 3 && !PAD)>), dim3(blocks),
-                           dim3(f.threads), f.lds_bytes + (f.tile_len / 80 + 1) * 20 * 8, s, in, h, out, g, f.T, f.D, f.Wpad, (long long)n_out, (long long)n_in,
-                           f.tile_len, stat, statL | (f.prio << 16), agc, af, f.T > 1 ? f.hist[f.cur ^ 1].as<float2>() : (float2 *)nullptr,
-                           f.mfb.as<float>());
+    const FirPlan &p = a.p;
+    if constexpr (FORM == FIR_WALK || FORM == FIR_WALK_EXACT)
+        hipLaunchKernelGGL((fir_decim_kernel<RC, PAD, TYPE, APL, TS, DS, MF, FORM == FIR_WALK_EXACT>), dim3(a.blocks), dim3(p.threads),
+                           a.lds_bytes, a.s, a.in, a.hist, a.out, a.taps, p.T, p.D, p.Wpad, a.n_out, a.n_in, p.tile_len, a.stat,
+                           a.stat_word, a.agc, a.fill, a.hist_new, a.mfb);
+    else if constexpr (FORM == FIR_EXACT)
+        hipLaunchKernelGGL((fir_exact_kernel<TYPE, PAD>), dim3(a.blocks), dim3(p.threads), a.lds_bytes, a.s, a.in, a.hist, a.out,
+                           a.taps, p.T, p.D, a.n_out, a.n_in, p.tile_len, p.RC, a.stat, a.hist_new);
     else
-#endif
-    if (RC == 3 && !PAD && f.T == 151 && f.D == 5 && type == XRIT_SAMPLE_FLOATIQ && !f.no_static_dec)
-        hipLaunchKernelGGL((fir_decim_kernel<RC, PAD, XRIT_SAMPLE_FLOATIQ, 0, (RC == 3 && !PAD) ? 151 : 0, 5>), dim3(blocks),
-                           dim3(f.threads), f.lds_bytes, s, in, h, out, g, f.T, f.D, f.Wpad, (long long)n_out, (long long)n_in,
-                           f.tile_len, stat, statL | (f.prio << 16), agc, af, f.T > 1 ? f.hist[f.cur ^ 1].as<float2>() : (float2 *)nullptr);
-    else if (RC == 5 && !PAD && f.T == 63 && f.D == 1 && type == XRIT_SAMPLE_FLOATIQ && !f.no_static_mf)
-        hipLaunchKernelGGL((fir_decim_kernel<RC, PAD, XRIT_SAMPLE_FLOATIQ, 0, (RC == 5 && !PAD) ? 63 : 0>), dim3(blocks),
-                           dim3(f.threads), f.lds_bytes, s, in, h, out, g, f.T, f.D, f.Wpad, (long long)n_out, (long long)n_in,
-                           f.tile_len, stat, statL | (f.prio << 16), agc, af, f.T > 1 ? f.hist[f.cur ^ 1].as<float2>() : (float2 *)nullptr);
-    else if (type == XRIT_SAMPLE_FLOATIQ) XR_FIR_GO(XRIT_SAMPLE_FLOATIQ);
-    else if (type == XRIT_SAMPLE_S16IQ) XR_FIR_GO(XRIT_SAMPLE_S16IQ);
-    else XR_FIR_GO(XRIT_SAMPLE_S8IQ);
-#undef XR_FIR_GO
-    XR_HIP(hipGetLastError());
-    return XRIT_OK;
+        hipLaunchKernelGGL((fir_poly_kernel<DS, FirPlan::POLY_PR, FirPlan::POLY_NQ, TYPE>), dim3(a.blocks), dim3(p.threads),
+                           a.lds_bytes, a.s, a.in, a.hist, a.out, a.taps, p.T, a.n_out, a.n_in, p.tile_len, a.hist_new);
 }
 
-bool FirStage::agc_fill_supported(int per_lane) const
+// the one switch over the sample type: go(FirType<type>)
+template <int TYPE> struct FirType { static constexpr int value = TYPE; };
+template <int TYPES, class Go>
+static int fir_by_type(int type, Go go)
 {
-    // the window must be covered by three rounds of the block's waves, one run each
-    const long long runs = (tile_len + (long long)64 * per_lane - 1) / (64 * per_lane) + 1;
-    return !exact && D == 1 && !pad && threads % 64 == 0 && per_lane == 3 && RC == 5 && runs <= 3 * (threads / 64);
-}
-
-// matched filter with the AGC applied in its window fill; `in` is the fallback stream (AgcFill)
-static int fir_launch_agc_fill(FirStage &f, const float2 *in, float2 *out, size_t n, hipStream_t s, Profiler *prof,
-                               float2 *stat, int statL, const AgcFill &af)
-{
-    const AgcEpilogue none{nullptr, nullptr, 0.f, 0.f, 0.f};
-    const unsigned blocks = div_up(n, (size_t)f.threads * 5);
-    {
-        ProfScope ps(prof, "fir_rrc", s);
-        if (f.T == 63 && !f.no_static_mf)
-            hipLaunchKernelGGL((fir_decim_kernel<5, false, XRIT_SAMPLE_FLOATIQ, 3, 63>), dim3(blocks), dim3(f.threads), f.lds_bytes, s,
-                               in, f.hist[f.cur].as<float2>(), out, f.g.as<float>(), f.T, f.D, f.Wpad, (long long)n,
-                               (long long)n, f.tile_len, stat, statL | (f.prio << 16), none, af, f.hist[f.cur ^ 1].as<float2>());
-        else
-        hipLaunchKernelGGL((fir_decim_kernel<5, false, XRIT_SAMPLE_FLOATIQ, 3>), dim3(blocks), dim3(f.threads), f.lds_bytes, s,
-                           in, f.hist[f.cur].as<float2>(), out, f.g.as<float>(), f.T, f.D, f.Wpad, (long long)n,
-                           (long long)n, f.tile_len, stat, statL | (f.prio << 16), none, af, f.hist[f.cur ^ 1].as<float2>());
+    if (type == XRIT_SAMPLE_FLOATIQ) go(FirType<XRIT_SAMPLE_FLOATIQ>{});
+    else if constexpr (TYPES == FIR_ANY_TYPE) {
+        if (type == XRIT_SAMPLE_S16IQ) go(FirType<XRIT_SAMPLE_S16IQ>{});
+        else if (type == XRIT_SAMPLE_S8IQ) go(FirType<XRIT_SAMPLE_S8IQ>{});
+        else { set_error("FIR: no kernel for sample type %d", type); return XRIT_E_INVALID; }
     }
+    else { set_error("FIR: this kernel form takes cf32 samples only, not type %d", type); return XRIT_E_INVALID; }
     XR_HIP(hipGetLastError());
-    f.cur ^= 1;
     return XRIT_OK;
+}
+
+// The launch of a key: a row of fir_plan.h's instance list, or an error -- nothing takes "the rest".
+static int fir_dispatch(const FirKey &key, int type, const FirLaunch &a)
+{
+#define XR_FIR_LAUNCH(FORM, RC, PAD, APL, TS, DS, MF, TYPES)    \
+    if (key == FirKey{FORM, RC, PAD, APL, TS, DS, MF})          \
+        return fir_by_type<TYPES>(type, [&a](auto ty) { fir_go<FORM, RC, PAD, APL, TS, DS, MF, decltype(ty)::value>(a); });
+    XR_FIR_INSTANCES(XR_FIR_LAUNCH)
+#undef XR_FIR_LAUNCH
+    set_error("FIR: no kernel instance of form %d for %d outputs per lane, PAD %d, APL %d, TS %d, DS %d, MF %d", key.form, key.rc,
+              (int)key.pad, key.apl, key.ts, key.ds, (int)key.mf);
+    return XRIT_E_INVALID;
 }
 
 int FirStage::run(const void *in, int type, float2 *out, size_t n_out, hipStream_t s, Profiler *prof, float2 *stat,
                   int statL, const AgcEpilogue *agc_in, const AgcFill *fill, bool use_exact)
 {
+    const FirPlan &p = plan;
+    const int T = p.T;
     if (twin && T > 1 && use_exact != last_twin) {
         // the call changes sides: the T - 1 samples of history go along
         FirStage &from = last_twin ? *twin : *this, &to = last_twin ? *this : *twin;
@@ -986,117 +887,33 @@ int FirStage::run(const void *in, int type, float2 *out, size_t n_out, hipStream
         twin->prio = prio;
         return twin->run(in, type, out, n_out, s, prof, stat, statL, agc_in, fill, false);
     }
-    if (fill) {
-        if (!agc_fill_supported(fill->per_lane) || type != XRIT_SAMPLE_FLOATIQ || T < 2) {
-            set_error("FIR: this filter cannot apply the AGC in its window fill");
-            return XRIT_E_INVALID;
-        }
-        if (stat && !stat_supported(statL)) stat = nullptr;
-        if (n_out == 0) return XRIT_OK;
-        return fir_launch_agc_fill(*this, reinterpret_cast<const float2 *>(in), out, n_out, s, prof, stat, statL, *fill);
+    // matched filter with the AGC applied in its window fill: `in` is then the fallback stream (AgcFill)
+    if (fill && (!agc_fill_supported(fill->per_lane) || type != XRIT_SAMPLE_FLOATIQ || T < 2)) {
+        set_error("FIR: this filter cannot apply the AGC in its window fill");
+        return XRIT_E_INVALID;
     }
     if (stat && !stat_supported(statL)) stat = nullptr;
-    if (exact) {
-        if (agc_in) { set_error("FIR: the exact-order kernel has no AGC epilogue"); return XRIT_E_INVALID; }
-        const size_t n_in = n_out * (size_t)D;
-        if (n_out > 0) {
-            ProfScope ps(prof, D > 1 ? "fir_decim" : "fir_rrc", s);
-            const unsigned blocks = div_up(n_out, (size_t)ex_threads * ex_opt);
-            const float2 *h = hist[cur].as<float2>();
-            float2 *hn = T > 1 ? hist[cur ^ 1].as<float2>() : (float2 *)nullptr;
-#define XR_EX_GO(TY, PD)                                                                                               \
-    hipLaunchKernelGGL((fir_exact_kernel<TY, PD>), dim3(blocks), dim3(ex_threads), ex_lds, s, in, h, out, rt.as<float>(), T, D, \
-                       (long long)n_out, (long long)n_in, ex_tile_len, ex_opt, stat, hn)
-#define XR_EX_TY(PD)                                                          \
-    do {                                                                      \
-        if (type == XRIT_SAMPLE_FLOATIQ) XR_EX_GO(XRIT_SAMPLE_FLOATIQ, PD);   \
-        else if (type == XRIT_SAMPLE_S16IQ) XR_EX_GO(XRIT_SAMPLE_S16IQ, PD);  \
-        else XR_EX_GO(XRIT_SAMPLE_S8IQ, PD);                                  \
-    } while (0)
-            if (!pad && threads % 64 == 0) {
-                // (windows that need no skew: the window walk shared by a lane's RC outputs, fir_decim_kernel<..., EX>)
-                const AgcEpilogue none{nullptr, nullptr, 0.f, 0.f, 0.f};
-                const AgcFill af{};
-                const unsigned blk = div_up(n_out, (size_t)threads * RC);
-#define XR_EXS_GO(RCV, TY)                                                                                                     \
-    hipLaunchKernelGGL((fir_decim_kernel<RCV, false, TY, 0, 0, 1, false, true>), dim3(blk), dim3(threads), lds_bytes, s, in, h, out, \
-                       g.as<float>(), T, D, Wpad, (long long)n_out, (long long)n_in, tile_len, stat, statL | (prio << 16), none, af, hn)
-#define XR_EXS_TY(RCV)                                                          \
-    do {                                                                        \
-        if (type == XRIT_SAMPLE_FLOATIQ) XR_EXS_GO(RCV, XRIT_SAMPLE_FLOATIQ);   \
-        else if (type == XRIT_SAMPLE_S16IQ) XR_EXS_GO(RCV, XRIT_SAMPLE_S16IQ);  \
-        else XR_EXS_GO(RCV, XRIT_SAMPLE_S8IQ);                                  \
-    } while (0)
-                if (RC == 5) XR_EXS_TY(5);
-                else XR_EXS_TY(3);
-#undef XR_EXS_TY
-#undef XR_EXS_GO
-            }
-            else if (pad && D % 4 == 0 && threads % 64 == 0 && (RC == 3 || RC == 1)) {
-                // (skewed windows with D a multiple of 4 -- 16, 32, 64: the shared walk too)
-                const AgcEpilogue none{nullptr, nullptr, 0.f, 0.f, 0.f};
-                const AgcFill af{};
-                const unsigned blk = div_up(n_out, (size_t)threads * RC);
-#define XR_EXP_GO(RCV, TY)                                                                                                     \
-    hipLaunchKernelGGL((fir_decim_kernel<RCV, true, TY, 0, 0, 1, false, true>), dim3(blk), dim3(threads), lds_bytes, s, in, h, out, \
-                       g.as<float>(), T, D, Wpad, (long long)n_out, (long long)n_in, tile_len, (float2 *)nullptr, 0, none, af, hn)
-#define XR_EXP_TY(RCV)                                                          \
-    do {                                                                        \
-        if (type == XRIT_SAMPLE_FLOATIQ) XR_EXP_GO(RCV, XRIT_SAMPLE_FLOATIQ);   \
-        else if (type == XRIT_SAMPLE_S16IQ) XR_EXP_GO(RCV, XRIT_SAMPLE_S16IQ);  \
-        else XR_EXP_GO(RCV, XRIT_SAMPLE_S8IQ);                                  \
-    } while (0)
-                if (RC == 1) XR_EXP_TY(1);
-                else XR_EXP_TY(3);
-#undef XR_EXP_TY
-#undef XR_EXP_GO
-            }
-            else if (ex_pad) XR_EX_TY(true);
-            else XR_EX_TY(false);
-#undef XR_EX_TY
-#undef XR_EX_GO
-            XR_HIP(hipGetLastError());
-        }
-        if (T > 1 && n_in > 0) cur ^= 1;
-        return XRIT_OK;
+    if (!fill && agc_in && exact) { set_error("FIR: the exact-order kernel has no AGC epilogue"); return XRIT_E_INVALID; }
+    if (!fill && agc_in && !agc_supported()) {
+        set_error("FIR: this block shape cannot produce the AGC epilogue");
+        return XRIT_E_INVALID;
     }
-    AgcEpilogue agc{nullptr, nullptr, 0.f, 0.f, 0.f};
-    if (agc_in) {
-        if (!agc_supported()) {
-            set_error("FIR: this block shape cannot produce the AGC epilogue");
-            return XRIT_E_INVALID;
-        }
-        agc = *agc_in;
+    if (n_out == 0) return XRIT_OK;
+
+    const FirKey key = fir_key(p, type == XRIT_SAMPLE_FLOATIQ, fill != nullptr);
+    unsigned blocks = div_up(n_out, fir_block_outputs(p));
+    if (key.form == FIR_POLY) blocks = (blocks + 7u) & ~7u;          // XCD-contiguous tile ranges
+    // (the skewed exact walk leaves no sums and has never run at a raised priority)
+    const int stat_word = key.form == FIR_WALK_EXACT && key.pad ? 0 : statL | (prio << 16);
+    const AgcEpilogue none{nullptr, nullptr, 0.f, 0.f, 0.f};
+    const FirLaunch a{p, blocks, fir_lds_bytes(p, key), s, in, hist[cur].as<float2>(), out, g.as<float>(), key.mf ? mfb.as<float>() : nullptr,
+                      (long long)n_out, (long long)(n_out * (size_t)p.D), stat, stat_word, agc_in && !fill ? *agc_in : none,
+                      fill ? *fill : AgcFill{}, T > 1 ? hist[cur ^ 1].as<float2>() : (float2 *)nullptr};
+    {
+        ProfScope ps(prof, p.D > 1 ? "fir_decim" : "fir_rrc", s);
+        XR_TRY(fir_dispatch(key, type, a));
     }
-    size_t n_in = n_out * (size_t)D;
-    if (n_out > 0 && poly) {
-        ProfScope ps(prof, "fir_decim", s);
-        const int OB = (threads / D) * POLY_PR;
-        const unsigned blocks = (div_up(n_out, (size_t)OB) + 7u) & ~7u;          // XCD-contiguous tile ranges
-        const float2 *h = hist[cur].as<float2>();
-#define XR_POLY_GO(DPV, TY)                                                                                      \
-    hipLaunchKernelGGL((fir_poly_kernel<DPV, POLY_PR, POLY_NQ, TY>), dim3(blocks), dim3(threads), lds_bytes, s, in, h,  \
-                       out, g.as<float>(), T, (long long)n_out, (long long)n_in, tile_len,                               \
-                       T > 1 ? hist[cur ^ 1].as<float2>() : (float2 *)nullptr)
-#define XR_POLY_TY(DPV)                                                         \
-    do {                                                                        \
-        if (type == XRIT_SAMPLE_FLOATIQ) XR_POLY_GO(DPV, XRIT_SAMPLE_FLOATIQ);  \
-        else if (type == XRIT_SAMPLE_S16IQ) XR_POLY_GO(DPV, XRIT_SAMPLE_S16IQ); \
-        else XR_POLY_GO(DPV, XRIT_SAMPLE_S8IQ);                                 \
-    } while (0)
-        if (D == 16) XR_POLY_TY(16);
-        else if (D == 32) XR_POLY_TY(32);
-        else XR_POLY_TY(64);
-#undef XR_POLY_TY
-#undef XR_POLY_GO
-        XR_HIP(hipGetLastError());
-    } else if (n_out > 0) {
-        ProfScope ps(prof, D > 1 ? "fir_decim" : "fir_rrc", s);
-        if (RC == 5 && !pad) XR_TRY((fir_launch_t<5, false>(*this, in, type, out, n_out, n_in, s, stat, statL, agc)));
-        else if (RC == 3 && !pad) XR_TRY((fir_launch_t<3, false>(*this, in, type, out, n_out, n_in, s, stat, statL, agc)));
-        else XR_TRY((fir_launch_t<3, true>(*this, in, type, out, n_out, n_in, s, stat, statL, agc)));
-    }
-    if (T > 1 && n_in > 0) cur ^= 1;      // the filter kernel's last workgroup has left the new history
+    if (T > 1) cur ^= 1;      // the filter kernel's last workgroup has left the new history
     return XRIT_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "lock_host.h"
 #include "clock_jobs.h"
 #include "clock_plan.h"
+#include "fir_plan.h"
 #include "loop_core.h"
 #include "taps.h"
 
@@ -15,25 +16,14 @@ namespace xrit {
 
 // ---- FirFilter (demodulator.cpp:446,450; Work at :138,:148) ---------------
 struct FirStage {
-    int T = 0, D = 1, RC = 3, W = 0, Wpad = 0, threads = 256, tile_len = 0, cur = 0;
-    bool pad = false;
-    bool mfma_dec = false;      // XRIT_MFMA_DEC=1: the C2 decimator on the matrix pipe (experiment, fir.hip)
-    bool no_static_dec = false, no_static_mf = false;   // XRIT_NO_STATIC_DEC / XRIT_NO_STATIC_MF, read once in init (A/B runs)
+    FirPlan plan;        // fir_plan.h: kernel form, template key, geometry and tap layout, made once in init
+    int cur = 0;
     int prio = 0;        // 1: this launch's waves at a raised issue priority (fir_decim_kernel; set by the chain per front end)
-    bool poly = false;   // polyphase kernel (lanes = phases) for decimation 16 / 32 / 64
-    // cfg.front_exact = 2: summed in the CPU chain's order, no FMA (fir_exact_kernel); set before init or through set_exact()
-    bool exact = false, ex_pad = false;
-    int ex_threads = 256, ex_opt = 2, ex_tile_len = 0;
-    size_t ex_lds = 0;
-    DevBuf rt;           // the taps reversed (exact kernel)
+    // cfg.front_exact = 2: summed in the CPU chain's order, no FMA (the plan's exact forms); set before init or through set_exact()
+    bool exact = false;
     std::vector<float> taps_host;
     int set_exact(bool on);
-#ifndef XRIT_POLY_PR
-#define XRIT_POLY_PR 16
-#endif
-    static constexpr int POLY_PR = XRIT_POLY_PR, POLY_NQ = 32;     // outputs per lane group, taps per phase (T <= 32 * D)
-    size_t lds_bytes = 0;
-    DevBuf g;        // RC x Wpad window taps (polyphase: D x POLY_NQ phase taps)
+    DevBuf g;        // the tap image the plan names (rows, phases or the taps reversed)
     DevBuf mfb;      // matrix-pipe experiment: the Toeplitz tap operand, one float per (step, lane)
     DevBuf hist[2];  // T-1 samples of history (ping-pong)
     int init(const float *taps, int ntaps, int decim);
@@ -54,9 +44,9 @@ struct FirStage {
     FirStage() = default;
     FirStage(const FirStage &) = delete;
     FirStage &operator=(const FirStage &) = delete;
-    bool agc_fill_supported(int per_lane) const;
-    bool stat_supported(int statL) const;
-    bool agc_supported() const;
+    bool agc_fill_supported(int per_lane) const { return fir_agc_fill_supported(plan, per_lane); }
+    bool stat_supported(int statL) const { return fir_stat_supported(plan, statL); }
+    bool agc_supported() const { return fir_agc_supported(plan); }
 };
 
 // What the decimator's epilogue needs to leave the AGC's first sweep behind (AgcStage::fused_begin fills it).

@@ -173,7 +173,7 @@ int xrit_fir_work(xrit_fir *f, const float *in, float *out, size_t n_out)
 {
     if (!f || (n_out && (!in || !out))) { set_error("null argument"); return XRIT_E_INVALID; }
     XR_HIP(hipSetDevice(f->device));
-    size_t n_in = n_out * (size_t)f->st.D;
+    size_t n_in = n_out * (size_t)f->st.plan.D;
     XR_TRY(f->in.reserve((n_in + 8) * sizeof(float2)));
     XR_TRY(f->out.reserve((n_out + 8) * sizeof(float2)));
     if (n_in) XR_HIP(hipMemcpyAsync(f->in.p, in, n_in * sizeof(float2), hipMemcpyHostToDevice, f->stream));
