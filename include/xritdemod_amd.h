@@ -1347,6 +1347,147 @@ int xrit_geo_parse_navigation(const uint8_t *header_bytes, size_t n, xrit_geo_na
 int xrit_geo_pixel_to_lonlat(const xrit_geo_nav *nav, double column, double line, double *lon_deg, double *lat_deg);
 
 /* ------------------------------------------------------------------------
+ * Map overlay: coastlines, borders and a latitude / longitude graticule drawn
+ * into an image where it lies in device memory -- a toned view, a projected
+ * image -- so that a cloud field can be placed by eye (DESIGN.md section 28;
+ * tests/overlay_spec.py is the specification, csrc/overlay_rule.h the rules the
+ * kernels and the host check are built from).  Polylines become a mask of one
+ * byte per pixel, the mask is blended into the image.  Integer arithmetic from
+ * the vertices on: the device equals the specification byte for byte, whatever
+ * the order in which the segments are taken.
+ *
+ *  - vertices: an array of xrit_geo_point, qx, qy in 1/256 pixel of the target
+ *    image, pixel centres at multiples of 256.  Segment i joins vertex i and
+ *    i + 1 iff neither is a break.  A break is {INT32_MIN, INT32_MIN}; a vertex
+ *    with |qx| or |qy| at or above 2^29 counts as one.  That keeps every product
+ *    below in 64 bits, and this test stands in front of every index.
+ *  - vertex map, scan geometry (xrit_overlay_map_device): per vertex a quad of
+ *    doubles {A, B, C, S} as "Image projection" defines them for a row and a column;
+ *    the point is that section's map entry, computed by the same function.  Off
+ *    the disc, or a quad holding NaN: a break.  xrit_overlay_quads makes the quads
+ *    of longitudes and latitudes on the host; xrit_overlay_grid_points gives the
+ *    positions on an xrit_geo_grid directly.
+ *  - the mask: rows x mask_pitch bytes, bit k of a byte: layer k (0 .. 7) drew
+ *    here.  mask_pitch >= columns and a multiple of 4, d_mask 4-byte aligned;
+ *    columns, rows 1 .. 16384.  Bits are set with 32-bit atomic OR, so a call adds
+ *    to what is there, and calls on different layers may run in any order.
+ *  - a segment with ends (x0, y0), (x1, y1), in exact integers:
+ *      1. max_jump != 0 and |x1-x0| > max_jump or |y1-y0| > max_jump: not drawn,
+ *         counted in `jumps` (the line across the picture where a grid wraps).
+ *      2. Both end pixels ((x+128)>>8, (y+128)>>8) are stamped.
+ *      3. The major axis is x iff |dx| >= |dy|; a the major, b the minor
+ *         coordinate, the ends ordered so that a0 <= a1.
+ *      4. a0 == a1: nothing more.
+ *      5. For every integer m with a0 <= 256 m <= a1:
+ *         minor = b0 + floor((2 (256 m - a0)(b1 - b0) + (a1 - a0)) / (2 (a1 - a0))),
+ *         and pixel (m, (minor+128)>>8) (major, minor) is stamped.
+ *      6. Before anything is walked the range of m is cut to
+ *         -floor(w/2) .. dim - 1 + floor((w-1)/2), dim being the image's size along
+ *         the major axis: the m whose stamp can reach the image along that axis.  A
+ *         segment costs at most dim + w + 1 steps whatever its coordinates.
+ *      7. A stamp of width w (1 .. 8) at (px, py) sets the pixels with offsets
+ *         -floor((w-1)/2) .. floor(w/2) in both directions that lie inside the image.
+ *  - the draw's summary: vertices = n; segments: pairs with both ends present;
+ *    hidden: pairs with a break (segments + hidden = n - 1); jumps; drawn =
+ *    segments - jumps; outside: drawn, but no stamp touched the image; steps: for
+ *    every drawn segment 2 (the end stamps, wherever they fall) plus the number
+ *    of m left after the cut of rule 6 (0 for a0 == a1).
+ *  - two forms of the draw (xrit_overlay_set_form), the same mask and summary bit
+ *    for bit: 0, a lane per segment walks its steps; 1 (a new handle's), the steps
+ *    of all segments are counted and prefix-summed, and a lane takes one step.
+ *  - blend: per pixel, k the highest set bit of the mask byte.  No bit: the
+ *    output is the source (grey replicated for 1 -> 3 components).  Otherwise per
+ *    channel out = (src * (255 - alpha_k) + c_k * alpha_k + 127) / 255, integer
+ *    division, c = r, g, b of styles[k]; a one-component output uses
+ *    c = (77 r + 150 g + 29 b + 128) >> 8.  The image is an xrit_product_image with
+ *    bits == 8 and components_in (1 or 3, interleaved) bytes per pixel,
+ *    pitch >= columns * components_in; components_out is 1 or 3, three in needs
+ *    three out; out_pitch >= columns * components_out; mask_pitch >= columns; no
+ *    alignment is asked for.  In place (d_out == image->d_pixels) is allowed when
+ *    components and pitches are equal: every pixel is read and written by one
+ *    lane.  Bytes of an output row behind columns * components_out are not written.
+ *  - the handle owns scratch (8 bytes per vertex for form 1, the host-buffer
+ *    forms' staging) and the form: no state between calls.  Calls on one handle
+ *    share the scratch: keep them in order.  Once the scratch has its size no
+ *    call synchronises with the host.
+ * ------------------------------------------------------------------------ */
+typedef struct xrit_overlay xrit_overlay;
+#define XRIT_OVERLAY_MAX_DIM       16384
+#define XRIT_OVERLAY_MAX_WIDTH     8
+#define XRIT_OVERLAY_LAYERS        8
+#define XRIT_OVERLAY_MAX_VERTICES  (1u << 26)
+typedef struct xrit_overlay_style {
+    uint8_t r, g, b, alpha;
+} xrit_overlay_style;                /* 4 bytes */
+typedef struct xrit_overlay_draw_summary {
+    uint64_t vertices, segments, hidden, jumps, outside, drawn, steps;
+    uint32_t layer, width;
+} xrit_overlay_draw_summary;         /* 64 bytes */
+typedef struct xrit_overlay_blend_summary {
+    uint64_t pixels;                 /* rows * columns */
+    uint64_t covered;                /* pixels with a mask bit */
+    uint64_t by_layer[8];            /* of those, by their top layer: they add up to covered */
+    uint32_t columns, rows, components_in, components_out;
+} xrit_overlay_blend_summary;        /* 96 bytes */
+
+/* No device: XRIT_E_NO_DEVICE, "no CPU path".  A new handle has form 1. */
+int xrit_overlay_create(xrit_overlay **ov, int device);
+int xrit_overlay_destroy(xrit_overlay *ov);
+/* waits for the handle's last call; there is no state to clear */
+int xrit_overlay_reset(xrit_overlay *ov);
+/* form 0 or 1; anything else XRIT_E_INVALID, nothing changed */
+int xrit_overlay_set_form(xrit_overlay *ov, uint32_t form);
+/* The _device calls are asynchronous on `stream` (0: the null stream).  A NULL pointer (n == 0 allows NULL vertices),
+ * n above 2^26, layer > 7, width 0 or above 8, columns or rows outside 1 .. 16384, a pitch too small, mask_pitch or
+ * d_mask not a multiple of 4 (draw), d_quads, d_points or a summary not 8-byte aligned, an image outside the bounds above:
+ * XRIT_E_INVALID, nothing queued, nothing written. */
+/* n quads {A, B, C, S} -> n points */
+int xrit_overlay_map_device(xrit_overlay *ov, const xrit_geo_nav *nav, const double *d_quads, size_t n, xrit_geo_point *d_points, void *stream);
+/* clear != 0: rows * mask_pitch bytes of the mask are zeroed first */
+int xrit_overlay_draw_device(xrit_overlay *ov, const xrit_geo_point *d_points, size_t n, uint32_t layer, uint32_t width, uint32_t max_jump,
+                             uint8_t *d_mask, uint32_t columns, uint32_t rows, uint32_t mask_pitch, uint32_t clear,
+                             xrit_overlay_draw_summary *d_summary, void *stream);
+/* styles: XRIT_OVERLAY_LAYERS entries in host memory, copied into the launch */
+int xrit_overlay_blend_device(xrit_overlay *ov, const xrit_product_image *image, uint32_t components_in, const uint8_t *d_mask,
+                              uint32_t mask_pitch, const xrit_overlay_style *styles, uint8_t *d_out, uint32_t out_pitch,
+                              uint32_t components_out, xrit_overlay_blend_summary *d_summary, void *stream);
+/* host buffers (one upload, one download; run on the handle's own stream and wait): every pointer is host memory.  The
+ * draw uploads the mask unless clear != 0. */
+int xrit_overlay_map(xrit_overlay *ov, const xrit_geo_nav *nav, const double *quads, size_t n, xrit_geo_point *points);
+int xrit_overlay_draw(xrit_overlay *ov, const xrit_geo_point *points, size_t n, uint32_t layer, uint32_t width, uint32_t max_jump,
+                      uint8_t *mask, uint32_t columns, uint32_t rows, uint32_t mask_pitch, uint32_t clear, xrit_overlay_draw_summary *summary);
+int xrit_overlay_blend(xrit_overlay *ov, const xrit_product_image *image, uint32_t components_in, const uint8_t *mask, uint32_t mask_pitch,
+                       const xrit_overlay_style *styles, uint8_t *out, uint32_t out_pitch, uint32_t components_out,
+                       xrit_overlay_blend_summary *summary);
+/* the image and the mask in device memory where they lie (a toned view behind xrit_product_outputs_device, a mask drawn by
+ * xrit_overlay_draw_device), out and summary host memory */
+int xrit_overlay_blend_resident(xrit_overlay *ov, const xrit_product_image *image, uint32_t components_in, const uint8_t *d_mask,
+                                uint32_t mask_pitch, const xrit_overlay_style *styles, uint8_t *out, uint32_t out_pitch,
+                                uint32_t components_out, xrit_overlay_blend_summary *summary);
+/* Where the handle's last xrit_overlay_draw left the mask in device memory (rows x mask_pitch bytes as that call was
+ * given them; NULL before any such call): for xrit_overlay_blend_resident behind it.  It stays until the handle's next
+ * xrit_overlay_draw.  Nothing is queued and nothing waited for. */
+int xrit_overlay_mask_device(xrit_overlay *ov, const uint8_t **d_mask);
+/* Host helpers: plain C++ on the C library, never touch a device.  In longitude / latitude arrays a vertex with NaN in
+ * either coordinate is a break. */
+/* the quads of n vertices, by the formulas of xrit_geo_grid_tables per vertex; NaN in either coordinate: a NaN quad */
+int xrit_overlay_quads(const double *lon_deg, const double *lat_deg, size_t n, double sub_lon_deg, double *quads);
+/* the positions on a grid in 1/256 pixel: column (d / step_lon) with d = lon - lon0 brought into [-180, 180), row
+ * (lat0 - lat) / step_lat, for XRIT_GEO_MERCATOR (lat0 - asinh(tan(lat))) / step_lat; q = floor(256 v + 0.5).  NaN, or a
+ * position not below 2^29 in magnitude: a break. */
+int xrit_overlay_grid_points(const xrit_geo_grid *grid, const double *lon_deg, const double *lat_deg, size_t n, xrit_geo_point *points);
+/* a segment longer than max_step_deg in either coordinate is split into k = ceil(max(|dlon|, |dlat|) / max_step_deg)
+ * equal parts in lon / lat (vertex j of them: p0 + (p1 - p0) * j / k); breaks are kept.  *n_out: the vertices this makes;
+ * XRIT_E_CAPACITY (and the true *n_out, the first cap written) when cap is too small; more than 2^26: XRIT_E_INVALID. */
+int xrit_overlay_densify(const double *lon_deg, const double *lat_deg, size_t n, double max_step_deg, double *out_lon, double *out_lat,
+                         size_t cap, size_t *n_out);
+/* meridians at -180 + i * step_deg below 180, from latitude -90 to 90, then parallels at -90 + i * step_deg strictly
+ * between the poles, from longitude -180 to 180, each with a vertex every vertex_step_deg (the last one on the end) and a
+ * break behind it.  step_deg 0.1 .. 90, vertex_step_deg 0.001 .. step_deg; steps that make more than 2^26 vertices:
+ * XRIT_E_INVALID, decided from the steps before anything is written.  *n_out and XRIT_E_CAPACITY as above. */
+int xrit_overlay_graticule(double step_deg, double vertex_step_deg, double *lon_deg, double *lat_deg, size_t cap, size_t *n_out);
+
+/* ------------------------------------------------------------------------
  * JPEG: an 8-bit image in device memory -- the product stage's toned image,
  * its thumbnail, its composite, a projected image -- becomes a complete
  * baseline JFIF file in device memory, so that only the file's bytes cross to

@@ -28,6 +28,9 @@ from ._capi import (  # noqa: F401
     TONE_LINEAR, TONE_TABLE, TONE_EQUALISE, TONE_STRETCH,
     ImageProjector, GEO_NAV_DTYPE, GEO_GRID_DTYPE, GEO_POINT_DTYPE, GEO_SUMMARY_DTYPE, GEO_KINDS, GEO_MODES, GEO_MAX_DIM, GEO_OFF,
     GEO_EQUIRECT, GEO_MERCATOR, GEO_NEAREST, GEO_BILINEAR, geo_nav, geo_grid_tables, geo_parse_navigation, geo_pixel_to_lonlat,
+    MapOverlay, OVERLAY_STYLE_DTYPE, OVERLAY_DRAW_SUMMARY_DTYPE, OVERLAY_BLEND_SUMMARY_DTYPE, OVERLAY_BREAK, OVERLAY_LIMIT, OVERLAY_MAX_DIM,
+    OVERLAY_MAX_WIDTH, OVERLAY_LAYERS, OVERLAY_MAX_VERTICES, overlay_styles, overlay_quads, overlay_grid_points, overlay_densify,
+    overlay_graticule,
     JpegEncoder, JPEG_RESULT_DTYPE, JPEG_MAX_BLOCKS, jpeg_bound, jpeg_quality_tables, jpeg_header,
     JpegDecoder, JPEGDEC_RECORD_DTYPE, JPEGDEC_SUMMARY_DTYPE, JPEGDEC_INFO_DTYPE, JPEGDEC_ITEM_DTYPE, JPEGDEC_MAX_BLOCKS, jpegdec_header,
     CarrierAcquirer, ACQUIRE_PARAMS_DTYPE, ACQUIRE_RECORD_DTYPE, ACQUIRE_STATE_DTYPE, ACQUIRE_OK, ACQUIRE_TOO_SHORT, ACQUIRE_WEAK,

@@ -179,6 +179,22 @@ _SIGNATURES = {
     "xrit_geo_project_resident": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "xrit_geo_parse_navigation": (C.c_int, [_vp, C.c_size_t, _vp]),
     "xrit_geo_pixel_to_lonlat": (C.c_int, [_vp, C.c_double, C.c_double, _vp, _vp]),
+    "xrit_overlay_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "xrit_overlay_destroy": (C.c_int, [_vp]),
+    "xrit_overlay_reset": (C.c_int, [_vp]),
+    "xrit_overlay_set_form": (C.c_int, [_vp, C.c_uint32]),
+    "xrit_overlay_map_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "xrit_overlay_draw_device": (C.c_int, [_vp, _vp, _sz] + [C.c_uint32] * 3 + [_vp] + [C.c_uint32] * 4 + [_vp, _vp]),
+    "xrit_overlay_blend_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "xrit_overlay_map": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "xrit_overlay_draw": (C.c_int, [_vp, _vp, _sz] + [C.c_uint32] * 3 + [_vp] + [C.c_uint32] * 4 + [_vp]),
+    "xrit_overlay_blend": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "xrit_overlay_blend_resident": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "xrit_overlay_mask_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "xrit_overlay_quads": (C.c_int, [_vp, _vp, _sz, C.c_double, _vp]),
+    "xrit_overlay_grid_points": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "xrit_overlay_densify": (C.c_int, [_vp, _vp, _sz, C.c_double, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "xrit_overlay_graticule": (C.c_int, [C.c_double, C.c_double, _vp, _vp, _sz, C.POINTER(_sz)]),
     "xrit_jpeg_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "xrit_jpeg_destroy": (C.c_int, [_vp]),
     "xrit_jpeg_reset": (C.c_int, [_vp]),
@@ -1934,6 +1950,182 @@ class ImageProjector(_Handle):
     def reset(self):
         """Waits for the last call; the tables stay."""
         _check(lib().xrit_geo_reset(self._h))
+
+
+# ---- map overlay (DESIGN.md section 28) ----------------------------------------------------------------------------------
+OVERLAY_BREAK = -(1 << 31)
+OVERLAY_LIMIT = 1 << 29
+OVERLAY_MAX_DIM = 16384
+OVERLAY_MAX_WIDTH = 8
+OVERLAY_LAYERS = 8
+OVERLAY_MAX_VERTICES = 1 << 26
+# xrit_overlay_style, xrit_overlay_draw_summary, xrit_overlay_blend_summary
+OVERLAY_STYLE_DTYPE = np.dtype([("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("alpha", np.uint8)])
+assert OVERLAY_STYLE_DTYPE.itemsize == 4
+OVERLAY_DRAW_SUMMARY_DTYPE = np.dtype([(k, np.uint64) for k in ("vertices", "segments", "hidden", "jumps", "outside", "drawn", "steps")] +
+                                      [(k, np.uint32) for k in ("layer", "width")])
+assert OVERLAY_DRAW_SUMMARY_DTYPE.itemsize == 64
+OVERLAY_BLEND_SUMMARY_DTYPE = np.dtype([("pixels", np.uint64), ("covered", np.uint64), ("by_layer", np.uint64, (8,))] +
+                                       [(k, np.uint32) for k in ("columns", "rows", "components_in", "components_out")])
+assert OVERLAY_BLEND_SUMMARY_DTYPE.itemsize == 96
+
+
+def overlay_styles(styles):
+    """8 x (r, g, b, alpha) -> an OVERLAY_STYLE_DTYPE array of 8."""
+    if isinstance(styles, np.ndarray) and styles.dtype == OVERLAY_STYLE_DTYPE and styles.shape == (OVERLAY_LAYERS,):
+        return np.ascontiguousarray(styles)
+    a = np.asarray(styles, np.int64).reshape(OVERLAY_LAYERS, 4)
+    if (a < 0).any() or (a > 255).any():
+        raise ValueError("r, g, b and alpha are bytes")
+    return np.ascontiguousarray(a.astype(np.uint8)).view(OVERLAY_STYLE_DTYPE).reshape(OVERLAY_LAYERS)
+
+
+def _overlay_points_arg(points):
+    if isinstance(points, np.ndarray) and points.dtype == GEO_POINT_DTYPE:
+        return np.ascontiguousarray(points.reshape(-1))
+    a = np.ascontiguousarray(np.asarray(points, np.int64).reshape(-1, 2).astype(np.int32))
+    return a.view(GEO_POINT_DTYPE).reshape(-1)
+
+
+def _lonlat(lon_deg, lat_deg):
+    lon, lat = np.ascontiguousarray(lon_deg, np.float64).reshape(-1), np.ascontiguousarray(lat_deg, np.float64).reshape(-1)
+    if len(lon) != len(lat):
+        raise ValueError("a latitude per longitude")
+    return lon, lat
+
+
+def overlay_quads(lon_deg, lat_deg, sub_lon_deg):
+    """The quads {A, B, C, S} of vertices given in degrees, made on the host (no device): (n, 4) float64; NaN: a NaN quad."""
+    lon, lat = _lonlat(lon_deg, lat_deg)
+    quads = np.zeros((len(lon), 4))
+    _check(lib().xrit_overlay_quads(_p(lon), _p(lat), len(lon), float(sub_lon_deg), _p(quads)))
+    return quads
+
+
+def overlay_grid_points(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg, lon_deg, lat_deg):
+    """The positions on a grid in 1/256 pixel (no device): GEO_POINT_DTYPE; NaN or out of range: a break."""
+    lon, lat = _lonlat(lon_deg, lat_deg)
+    grid = _geo_grid_arg(kind, columns, rows, lon0_deg, lat0_deg, step_lon_deg, step_lat_deg)
+    points = np.zeros(len(lon), GEO_POINT_DTYPE)
+    _check(lib().xrit_overlay_grid_points(_p(grid), _p(lon), _p(lat), len(lon), _p(points)))
+    return points
+
+
+def _overlay_sized(call):
+    """A host helper with a capacity: asked for the count first, then for the vertices."""
+    n = C.c_size_t()
+    rc = call(None, None, 0, n)
+    if rc not in (0, -5):
+        _check(rc)
+    lon, lat = np.zeros(n.value), np.zeros(n.value)
+    _check(call(_p(lon), _p(lat), n.value, n))
+    return lon, lat
+
+
+def overlay_densify(lon_deg, lat_deg, max_step_deg):
+    """Segments longer than max_step_deg in either coordinate split into equal parts; NaN vertices are breaks and stay."""
+    lon, lat = _lonlat(lon_deg, lat_deg)
+    return _overlay_sized(lambda a, b, cap, n: lib().xrit_overlay_densify(_p(lon), _p(lat), len(lon), float(max_step_deg), a, b, cap, C.byref(n)))
+
+
+def overlay_graticule(step_deg, vertex_step_deg):
+    """Meridians and parallels every step_deg with a vertex every vertex_step_deg, a NaN break behind each line."""
+    return _overlay_sized(lambda a, b, cap, n: lib().xrit_overlay_graticule(float(step_deg), float(vertex_step_deg), a, b, cap, C.byref(n)))
+
+
+class MapOverlay(_Handle):
+    """Polylines (coastlines, borders, a graticule) drawn into a mask of one byte per pixel, bit k for layer k, and the
+    mask blended into an 8-bit image, on the device.  form 0: a lane per segment; form 1: a lane per step.  The handle
+    owns scratch and the form; tests/overlay_spec.py is the specification."""
+    _destroy = "xrit_overlay_destroy"
+
+    def __init__(self, form=1, device=0):
+        super().__init__()
+        _check(lib().xrit_overlay_create(C.byref(self._h), device))
+        self.set_form(form)
+
+    def set_form(self, form):
+        _check(lib().xrit_overlay_set_form(self._h, form))
+
+    @staticmethod
+    def _image(pixels_ptr, columns, rows, pitch):
+        image = np.zeros(1, PRODUCT_IMAGE_DTYPE)
+        image[0] = (pixels_ptr or 0, columns, rows, pitch, 8)
+        return image
+
+    def map_device(self, nav, d_quads_ptr, n, d_points_ptr, stream=None):
+        """n quads of four float64 -> n GEO_POINT_DTYPE entries, both in device memory.  Asynchronous on stream."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_overlay_map_device(self._h, _p(_geo_nav_arg(nav)), v(d_quads_ptr), n, v(d_points_ptr), v(stream)))
+
+    def draw_device(self, d_points_ptr, n, layer, width, max_jump, d_mask_ptr, columns, rows, mask_pitch, clear, d_summary_ptr, stream=None):
+        """Asynchronous on stream; ORs into the mask unless clear."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_overlay_draw_device(self._h, v(d_points_ptr), n, layer, width, max_jump, v(d_mask_ptr), columns, rows, mask_pitch,
+                                              1 if clear else 0, v(d_summary_ptr), v(stream)))
+
+    def blend_device(self, d_pixels_ptr, columns, rows, pitch, components_in, d_mask_ptr, mask_pitch, styles, d_out_ptr, out_pitch,
+                     components_out, d_summary_ptr, stream=None):
+        """Asynchronous on stream; d_out_ptr may be d_pixels_ptr when components and pitches are equal."""
+        v = lambda x: C.c_void_p(x) if x else None
+        _check(lib().xrit_overlay_blend_device(self._h, _p(self._image(d_pixels_ptr, columns, rows, pitch)), components_in, v(d_mask_ptr),
+                                               mask_pitch, _p(overlay_styles(styles)) if styles is not None else None, v(d_out_ptr), out_pitch,
+                                               components_out, v(d_summary_ptr), v(stream)))
+
+    def map(self, nav, quads):
+        """quads: (n, 4) float64 -> n GEO_POINT_DTYPE entries."""
+        q = np.ascontiguousarray(quads, np.float64).reshape(-1, 4)
+        points = np.zeros(len(q), GEO_POINT_DTYPE)
+        _check(lib().xrit_overlay_map(self._h, _p(_geo_nav_arg(nav)), _p(q), len(q), _p(points)))
+        return points
+
+    def draw(self, points, layer, width, mask, max_jump=0, clear=False):
+        """points: GEO_POINT_DTYPE or (n, 2) integers; mask: 2-D uint8, C-contiguous, its row length a multiple of 4 and at
+        least `columns` -- drawn into in place.  columns: mask.shape[1] -> the OVERLAY_DRAW_SUMMARY_DTYPE record."""
+        return self.draw_into(points, layer, width, mask, mask.shape[1], max_jump, clear)
+
+    def draw_into(self, points, layer, width, mask, columns, max_jump=0, clear=False):
+        """As draw, for a mask whose rows are longer than the image's `columns`."""
+        if not (isinstance(mask, np.ndarray) and mask.dtype == np.uint8 and mask.ndim == 2 and mask.flags.c_contiguous and mask.flags.writeable):
+            raise ValueError("a writeable C-contiguous 2-D uint8 mask")
+        pts = _overlay_points_arg(points)
+        summary = np.zeros(1, OVERLAY_DRAW_SUMMARY_DTYPE)
+        _check(lib().xrit_overlay_draw(self._h, _p(pts) if len(pts) else None, len(pts), layer, width, max_jump, _p(mask), columns, mask.shape[0],
+                                       mask.shape[1], 1 if clear else 0, _p(summary)))
+        return summary[0]
+
+    def _blend_to_host(self, fn, pixels_ptr, columns, rows, pitch, components_in, mask_ptr, mask_pitch, styles, components_out):
+        out = np.zeros((rows, columns) if components_out == 1 else (rows, columns, 3), np.uint8)
+        summary = np.zeros(1, OVERLAY_BLEND_SUMMARY_DTYPE)
+        _check(fn(self._h, _p(self._image(pixels_ptr, columns, rows, pitch)), components_in, C.c_void_p(mask_ptr), mask_pitch,
+                  _p(overlay_styles(styles)), _p(out), columns * components_out, components_out, _p(summary)))
+        return out, summary[0]
+
+    def blend(self, image, mask, styles, components_out=3):
+        """image: (rows, columns) or (rows, columns, 3) uint8; mask: (rows, columns) uint8 -> (the blended image, an
+        OVERLAY_BLEND_SUMMARY_DTYPE record)."""
+        image, mask = np.ascontiguousarray(image, np.uint8), np.ascontiguousarray(mask, np.uint8)
+        if image.ndim not in (2, 3) or (image.ndim == 3 and image.shape[2] != 3) or mask.shape != image.shape[:2]:
+            raise ValueError("an image of one or three interleaved components and a mask of its size")
+        rows, columns = mask.shape
+        cin = 1 if image.ndim == 2 else 3
+        return self._blend_to_host(lib().xrit_overlay_blend, image.ctypes.data, columns, rows, columns * cin, cin, mask.ctypes.data, columns,
+                                   styles, components_out)
+
+    def blend_resident(self, d_pixels_ptr, columns, rows, pitch, components_in, d_mask_ptr, mask_pitch, styles, components_out=3):
+        """As blend, on an image and a mask that lie in device memory."""
+        return self._blend_to_host(lib().xrit_overlay_blend_resident, d_pixels_ptr, columns, rows, pitch, components_in, d_mask_ptr, mask_pitch,
+                                   styles, components_out)
+
+    def mask_device(self):
+        """Where the last draw / draw_into left the mask in device memory (an int, for blend_resident), None before any."""
+        p = C.c_void_p()
+        _check(lib().xrit_overlay_mask_device(self._h, C.byref(p)))
+        return p.value
+
+    def reset(self):
+        """Waits for the last call; there is no state."""
+        _check(lib().xrit_overlay_reset(self._h))
 
 
 # ---- JPEG (DESIGN.md section 25) ---------------------------------------------------------------------------------------

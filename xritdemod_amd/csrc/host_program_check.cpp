@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../host/jpeg_files.h"
+#include "../host/overlay_files.h"
 #include "../host/outputs.h"
 #include "../host/sinks.h"
 #include "../host/source.h"
@@ -328,6 +329,40 @@ static int check_jpeg_files(const std::string &dir)
     return 0;
 }
 
+// overlay_files.h: the options, the polyline text
+static int check_overlay_files()
+{
+    OverlayOptions o;
+    std::string why;
+    CHECK(o.flag("--overlays", "x", &why) == 0 && o.flag("--files", nullptr, &why) == 0 && !o.on() && o.refused(false) == nullptr);
+    CHECK(o.flag("--overlay", nullptr, &why) == -1 && why == "--overlay needs a value\n");
+    CHECK(o.flag("--overlay", "--graticule", &why) == -1 && why == "--overlay needs a value\n" && o.flag("--graticule", "--products", &why) == -1);
+    CHECK(o.flag("--overlay", "", &why) == -1 && why == "--overlay needs a file name\n" && !o.on());
+    CHECK(o.flag("--overlay-width", "3", &why) == 1 && o.width == 3 && std::string(o.refused(true)) == "--overlay-width needs --overlay or --graticule\n");
+    CHECK(o.flag("--overlay", "coast.txt", &why) == 1 && o.file == "coast.txt" && o.on() && o.refused(true) == nullptr);
+    CHECK(std::string(o.refused(false)) == "--overlay / --graticule need --products\n");
+    for (const char *bad : {"0", "9", "-1", "3x", "", "1.5"}) CHECK(o.flag("--overlay-width", bad, &why) == -1 && why.find(": 1..8\n") != std::string::npos);
+    CHECK(o.width == 3);
+    for (const char *bad : {"0", "0.05", "91", "ten", "10d", "nan", ""}) CHECK(o.flag("--graticule", bad, &why) == -1 && why.find(": 0.1..90 degrees\n") != std::string::npos);
+    CHECK(o.graticule == 0.0 && o.flag("--graticule", "7.5", &why) == 1 && o.graticule == 7.5);
+    OverlayOptions g;
+    CHECK(g.flag("--graticule", "90", &why) == 1 && g.on() && g.file.empty() && g.refused(true) == nullptr && g.width == 1);
+
+    std::vector<double> lon, lat;
+    CHECK(parse_polylines("", lon, lat) == 0 && lon.empty());
+    CHECK(parse_polylines("> first\n-75.5 10\n  -74\t11.25  \r\n\n# note\n1e1 -2.5e0\n>\n3 4", lon, lat) == 0);
+    CHECK(lon.size() == 8 && lat.size() == 8);
+    CHECK(std::isnan(lon[0]) && std::isnan(lat[0]) && lon[1] == -75.5 && lat[1] == 10.0 && lon[2] == -74.0 && lat[2] == 11.25);
+    CHECK(std::isnan(lon[3]) && std::isnan(lon[4]) && lon[5] == 10.0 && lat[5] == -2.5 && std::isnan(lat[6]) && lon[7] == 3.0 && lat[7] == 4.0);
+    CHECK(parse_polylines("1 2\n", lon, lat) == 0 && lon.size() == 1);            // nothing behind the last newline
+    CHECK(parse_polylines("1 2\n\n", lon, lat) == 0 && lon.size() == 2 && std::isnan(lon[1]));
+    CHECK(parse_polylines("1 2\n3\n", lon, lat) == 2 && parse_polylines("1 2 3", lon, lat) == 1 && parse_polylines("1,2", lon, lat) == 1);
+    CHECK(parse_polylines("1 2\n>\nlon lat\n", lon, lat) == 3 && parse_polylines("1 nan", lon, lat) == 1 && parse_polylines("inf 2", lon, lat) == 1);
+    CHECK(parse_polylines("1 2x", lon, lat) == 1 && parse_polylines("\n\n\n4 5 # east", lon, lat) == 4);
+    CHECK(OVERLAY_COAST_RGBA[3] == 255 && OVERLAY_GRATICULE_RGBA[2] == 255 && OVERLAY_DENSIFY_DEG == 0.05);
+    return 0;
+}
+
 int main()
 {
     char pattern[] = "/tmp/host_program_check.XXXXXX";
@@ -335,7 +370,7 @@ int main()
     CHECK(made != nullptr);
     const std::string dir = made;
     const int rc = check_pgm(dir) || check_names() || check_journal(dir) || check_packet_files(dir) || check_fifo(dir) ||
-                   check_read_ahead() || check_queue(dir) || check_jpeg_files(dir);
+                   check_read_ahead() || check_queue(dir) || check_jpeg_files(dir) || check_overlay_files();
     fs::remove_all(dir);
     if (rc == 0) std::printf("host_program_check: ok\n");
     return rc;

@@ -553,6 +553,30 @@ int launch_geo_resample(const GeoTables &t, const xrit_product_image &im, const 
                         uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
 int launch_geo_project(const GeoTables &t, const xrit_geo_nav &nav, const xrit_product_image &im, uint32_t mode, unsigned char *out,
                        uint32_t out_pitch, xrit_geo_summary *summary, hipStream_t s);
+// map overlay stage (overlay.hip; overlay_rule.h is the rule per value): the vertex map, the draw of n vertices into a
+// mask in either form (form 1 needs the scratch for that many), the blend.  launch_overlay_draw zeroes the summary (and
+// with clear the mask) first, launch_overlay_blend its summary.
+struct OverlayDraw {
+    const xrit_geo_point *points;
+    uint32_t n, layer, width, max_jump;
+    unsigned char *mask;
+    uint32_t columns, rows, pitch;
+};
+struct OverlayScratch {
+    unsigned long long *prefix;             // [n] a pair's steps, then the steps in front of it; the last element: all of them
+    unsigned long long *aggs;               // the scan's aggregates
+};
+size_t overlay_scratch_carve(void *p, size_t n, OverlayScratch &sc);
+struct OverlayBlend {
+    const unsigned char *pixels, *mask;
+    unsigned char *out;
+    uint32_t columns, rows, pitch, mask_pitch, out_pitch, cin, cout;
+    uint32_t styles[8];                     // r | g << 8 | b << 16 | alpha << 24
+};
+int launch_overlay_map(const xrit_geo_nav &nav, const double *quads, size_t n, xrit_geo_point *points, hipStream_t s);
+int launch_overlay_draw(const OverlayDraw &d, uint32_t form, uint32_t clear, const OverlayScratch &sc, xrit_overlay_draw_summary *summary,
+                        hipStream_t s);
+int launch_overlay_blend(const OverlayBlend &b, xrit_overlay_blend_summary *summary, hipStream_t s);
 // JPEG stage (jpeg.hip; jpeg_rule.h is the rule per value): one call on blocks = MCUs * comps blocks in n_int restart
 // intervals of ri MCUs (restart 0: one interval of all MCUs); the scratch for that many
 struct JpegPar {

@@ -9,10 +9,12 @@
 
 #include "../../include/xritdemod_amd.h"
 #include "jpeg_files.h"
+#include "overlay_files.h"
 #include "source.h"
 
 struct Options {
     FilesJpegOption files_jpeg;    // --files-jpeg: with --files, image files with compression flag 2 decoded to DIR/STEM.pgm / .ppm (xrit_jpegdec_*)
+    OverlayOptions overlay;        // --overlay FILE, --graticule DEG, --overlay-width W: with --products, every toned view also with a map drawn in (xrit_overlay_*)
     std::string mode = "lrit";
     std::string input;
     std::string format = "cf32";
@@ -118,6 +120,13 @@ inline void usage()
                  "                                 degrees); bilinear (default; pixels without data left out of the means) or nearest.  A canvas\n"
                  "                                 without such a record is skipped with a line on stderr.  With --products the projected image\n"
                  "                                 is toned too: DIR/<name>.geo.view.pgm)\n"
+                 "         [--overlay FILE] [--graticule DEG] [--overlay-width W]   (with --products: every DIR/<name>.view.pgm is also written\n"
+                 "                                 with a map drawn into it on the GPU, as DIR/<name>.view.map.ppm -- the polylines of FILE\n"
+                 "                                 (GMT multi-segment text: one `lon lat` pair per line in degrees, a line that is blank or begins\n"
+                 "                                 > or # ends a polyline) in opaque yellow (255, 255, 0), and meridians and parallels every DEG\n"
+                 "                                 degrees (0.1..90) in cyan (0, 255, 255) at 160 / 255, both with a vertex every 0.05 degrees, W\n"
+                 "                                 pixels wide (1..8, default 1); placed by the image navigation record, a canvas without one is\n"
+                 "                                 skipped with a line on stderr.  With --project also DIR/<name>.geo.view.map.ppm)\n"
                  "         [--tune HZ]   (a carrier offset of HZ is taken out on the GPU in front of the chain; cf32, s16 or s8 input, one GPU)\n"
                  "         [--acquire [--acquire-presum R]]   (the carrier offset is estimated on the first input of at least 65536 * R samples --\n"
                  "                                 further blocks are read ahead if a block is shorter --, printed to stderr with the strength of\n"
@@ -251,6 +260,10 @@ inline bool parse(int argc, char **argv, Options &o)
         for (const SwitchFlag &f : SWITCH_FLAGS)
             if (a == f.name) known = o.*f.field = true;
         if (known || o.files_jpeg.flag(a)) continue;
+        std::string why;
+        const int overlay = o.overlay.flag(a, i + 1 < argc ? argv[i + 1] : nullptr, &why);
+        if (overlay < 0) return refuse("%s", why.c_str());
+        if (overlay > 0) { ++i; continue; }
         if (a == "--product-tone") { if (!(v = need()) || !parse_tone(v, o.product)) return false; o.product_flags = true; }
         else if (a == "--product-factor") {
             if (!(v = need())) return false;
@@ -307,6 +320,7 @@ inline bool parse(int argc, char **argv, Options &o)
         return refuse("--products needs --canvas; --product-tone and --product-factor need --products\n");
     if (o.jpeg && !o.products)
         return refuse("--jpeg needs --products\n");
+    if (const char *why = o.overlay.refused(o.products)) return refuse("%s", why);
     if ((o.project && !o.canvas) || (o.project_flags && !o.project))
         return refuse("--project needs --canvas; --project-grid and --project-mode need --project\n");
     if ((o.tune || o.acquire) && (o.gpus > 1 || o.format == "u8" || o.acquire_presum < 1 || o.acquire_presum > 64))

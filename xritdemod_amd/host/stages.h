@@ -482,6 +482,7 @@ struct Projection {
     uint32_t mode = XRIT_GEO_BILINEAR;
     std::vector<uint8_t> out, tone;
     size_t projected = 0, skipped = 0;
+    bool wrote_view = false;        // the last write() left the projected image's toned view in `tone`
 
     // a canvas's navigation is that of its segment file at line 0, column 0 -- the record in that file's first piece
     void note_navigation(const Files &f, const Canvas &c)
@@ -499,6 +500,7 @@ struct Projection {
     }
     bool write(const Canvas &c, unsigned s, const xrit_canvas_slot &info, const std::string &stem, Products &products)
     {
+        wrote_view = false;
         if (!info.max_column || !info.max_row) return true;
         const SlotNav &n = nav[s];
         if (n.state != 1) {
@@ -534,13 +536,134 @@ struct Projection {
         xrit_product_summary toned{};
         if (xrit_product_process(products.pr, &flat, &products.params, nullptr, nullptr, nullptr, tone.data(), nullptr, &toned) != XRIT_OK)
             return fail("products of the projection");
-        return write_pgm(stem + ".geo.view.pgm", tone.data(), columns, rows, columns, 8);
+        wrote_view = write_pgm(stem + ".geo.view.pgm", tone.data(), columns, rows, columns, 8);
+        return wrote_view;
     }
     void report() const
     {
         std::fprintf(stderr, "project: %zu canvases projected onto %u x %u (%s), %zu skipped\n", projected, grid.columns, grid.rows,
                      mode == XRIT_GEO_NEAREST ? "nearest" : "bilinear", skipped);
     }
+};
+
+// --overlay / --graticule: coastlines (layer 0) and graticule (layer 1) drawn into a mask and blended into a toned view
+// where the product stage left it on the device; the vertices are placed by the canvas's navigation record (the scan
+// geometry) or on the projection's grid.  The vertex lists are fixed for the run, so each of the two kinds of view has a
+// handle of its own that keeps its mask on the device (xrit_overlay_mask_device): it is drawn again only when the
+// geometry or the size of the view changes.
+struct MapOverlay {
+    struct Kind {
+        Handle<xrit_overlay, xrit_overlay_destroy> ov;
+        std::string key;            // the geometry and size the mask on the device was drawn for; empty: none
+        uint32_t pitch = 0;
+    };
+    Kind kinds[2];                  // 0: the scan geometry, 1: the grid
+    std::vector<double> lon[2], lat[2];             // per layer, densified; NaN: a break
+    unsigned width = 1;
+    xrit_overlay_style styles[XRIT_OVERLAY_LAYERS] = {};
+    std::vector<double> quads;
+    std::vector<xrit_geo_point> points;
+    std::vector<uint8_t> mask, out;
+    size_t written = 0, skipped = 0, drawn = 0;
+
+    bool on() const { return (bool)kinds[0].ov; }
+    bool open(int device)
+    {
+        return xrit_overlay_create(&kinds[0].ov.p, device) == XRIT_OK && xrit_overlay_create(&kinds[1].ov.p, device) == XRIT_OK;
+    }
+    bool load(const OverlayOptions &o)
+    {
+        width = o.width;
+        for (auto &s : styles) s = xrit_overlay_style{255, 255, 255, 255};
+        styles[0] = xrit_overlay_style{OVERLAY_COAST_RGBA[0], OVERLAY_COAST_RGBA[1], OVERLAY_COAST_RGBA[2], OVERLAY_COAST_RGBA[3]};
+        styles[1] = xrit_overlay_style{OVERLAY_GRATICULE_RGBA[0], OVERLAY_GRATICULE_RGBA[1], OVERLAY_GRATICULE_RGBA[2], OVERLAY_GRATICULE_RGBA[3]};
+        std::vector<double> raw_lon, raw_lat;
+        if (!o.file.empty()) {
+            std::vector<unsigned char> text;
+            FILE *f = std::fopen(o.file.c_str(), "rb");
+            if (!f) { std::perror(o.file.c_str()); return false; }
+            unsigned char buf[65536];
+            for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.insert(text.end(), buf, buf + n);
+            std::fclose(f);
+            const size_t bad = parse_polylines(std::string(text.begin(), text.end()), raw_lon, raw_lat);
+            if (bad) { std::fprintf(stderr, "--overlay %s: line %zu is not `lon lat`\n", o.file.c_str(), bad); return false; }
+            if (!densify(raw_lon, raw_lat, 0)) return false;
+        }
+        if (o.graticule > 0.0) {
+            size_t n = 0;
+            const double vertex = o.graticule < 1.0 ? o.graticule : 1.0;
+            if (xrit_overlay_graticule(o.graticule, vertex, nullptr, nullptr, 0, &n) != XRIT_E_CAPACITY) return fail("graticule");
+            raw_lon.resize(n);
+            raw_lat.resize(n);
+            if (xrit_overlay_graticule(o.graticule, vertex, raw_lon.data(), raw_lat.data(), n, &n) != XRIT_OK) return fail("graticule");
+            if (!densify(raw_lon, raw_lat, 1)) return false;
+        }
+        return true;
+    }
+    bool densify(const std::vector<double> &a, const std::vector<double> &b, int layer)
+    {
+        size_t n = 0;
+        const int rc = xrit_overlay_densify(a.data(), b.data(), a.size(), OVERLAY_DENSIFY_DEG, nullptr, nullptr, 0, &n);
+        if (rc != XRIT_OK && rc != XRIT_E_CAPACITY) return fail("overlay vertices");
+        lon[layer].resize(n);
+        lat[layer].resize(n);
+        return !n || xrit_overlay_densify(a.data(), b.data(), a.size(), OVERLAY_DENSIFY_DEG, lon[layer].data(), lat[layer].data(), n, &n) == XRIT_OK ||
+               fail("overlay vertices");
+    }
+    // both layers into the kind's mask of a columns x rows image -- nav: through the scan geometry; grid: on that grid, with
+    // max_jump half its width
+    bool draw(Kind &k, uint32_t columns, uint32_t rows, const xrit_geo_nav *nav, const xrit_geo_grid *grid)
+    {
+        k.key.clear();
+        k.pitch = (columns + 3) & ~3u;
+        mask.assign((size_t)k.pitch * rows, 0);
+        for (int layer = 0; layer < 2; ++layer) {
+            const size_t n = lon[layer].size();
+            points.resize(n);
+            if (nav) {
+                quads.resize(4 * n);
+                if (xrit_overlay_quads(lon[layer].data(), lat[layer].data(), n, nav->sub_lon_deg, quads.data()) != XRIT_OK ||
+                    xrit_overlay_map(k.ov, nav, quads.data(), n, points.data()) != XRIT_OK)
+                    return fail("overlay map");
+            } else if (xrit_overlay_grid_points(grid, lon[layer].data(), lat[layer].data(), n, points.data()) != XRIT_OK) {
+                return fail("overlay grid points");
+            }
+            // (a layer without vertices is drawn too: the last draw is the one that leaves the mask on the device)
+            xrit_overlay_draw_summary sum{};
+            if (xrit_overlay_draw(k.ov, points.data(), n, (uint32_t)layer, width, nav ? 0u : columns * 128u, mask.data(), columns, rows, k.pitch, 0,
+                                  &sum) != XRIT_OK)
+                return fail("overlay draw");
+        }
+        ++drawn;
+        return true;
+    }
+    // d_view: a toned view (8 bits, tight) in device memory; path: it with the map, as binary PPM
+    bool write(const std::string &path, const uint8_t *d_view, uint32_t columns, uint32_t rows, const xrit_geo_nav *nav, const xrit_geo_grid *grid)
+    {
+        Kind &k = kinds[nav ? 0 : 1];
+        char text[256];
+        if (nav)
+            std::snprintf(text, sizeof text, "%u %u %d %d %d %d %d %.17g", columns, rows, nav->cfac, nav->lfac, nav->coff, nav->loff, nav->origin,
+                          nav->sub_lon_deg);
+        else
+            std::snprintf(text, sizeof text, "%u %u %u %.17g %.17g %.17g %.17g", columns, rows, grid->kind, grid->lon0_deg, grid->lat0_deg,
+                          grid->step_lon_deg, grid->step_lat_deg);
+        if (k.key != text) {
+            if (!draw(k, columns, rows, nav, grid)) return false;
+            k.key = text;
+        }
+        const uint8_t *d_mask = nullptr;
+        if (xrit_overlay_mask_device(k.ov, &d_mask) != XRIT_OK || !d_mask) return fail("overlay mask");
+        const xrit_product_image image{d_view, columns, rows, columns, 8};
+        out.resize((size_t)columns * rows * 3);
+        xrit_overlay_blend_summary blended{};
+        if (xrit_overlay_blend_resident(k.ov, &image, 1, d_mask, k.pitch, styles, out.data(), columns * 3, 3, &blended) != XRIT_OK)
+            return fail("overlay blend");
+        if (!write_pnm(path, out.data(), 3, columns, rows)) return false;
+        ++written;
+        return true;
+    }
+    void report() const { std::fprintf(stderr, "overlay: %zu views written with the map (%zu masks drawn), %zu skipped\n", written, drawn, skipped); }
 };
 
 // ---- the sequence ------------------------------------------------------------------------------------------------------
@@ -560,6 +683,7 @@ struct DecodeChain {
     Products products;
     Jpeg jpeg;
     Projection projection;
+    MapOverlay overlay;
     JpegFiles jpeg_files;
 
     bool active() const { return decoder.dec || lock.lk; }
@@ -608,7 +732,8 @@ struct DecodeChain {
         projection.mode = o.project_mode;
         if (o.project && xrit_geo_create(&projection.geo.p, device) != XRIT_OK) return library_error();
         projection.nav.assign(canvas.n_slots, Projection::SlotNav{});
-        return true;
+        if (o.overlay.on() && !overlay.open(device)) return library_error();
+        return !overlay.on() || overlay.load(o.overlay);
     }
     // a call's quantised symbols: the frames found in them, decoded, and through every stage behind
     bool add(const int8_t *sym, size_t n)
@@ -655,13 +780,13 @@ struct DecodeChain {
     bool place_lines()
     {
         if (!canvas.process(files, images)) return false;
-        if (projection.geo) projection.note_navigation(files, canvas);
+        if (projection.geo || overlay.on()) projection.note_navigation(files, canvas);
         for (unsigned s = 0; canvas.summary.completed && s < canvas.n_slots; ++s) {
             if (!canvas.slots[s].in_use || !canvas.slots[s].complete) continue;
             if (!write_canvas(s, false)) return false;
             if (xrit_canvas_release(canvas.cv, s) != XRIT_OK) return fail("canvas release");
             canvas.slots[s] = xrit_canvas_slot{};
-            if (projection.geo) projection.nav[s] = Projection::SlotNav{};
+            projection.nav[s] = Projection::SlotNav{};
         }
         return true;
     }
@@ -674,7 +799,27 @@ struct DecodeChain {
                                  (partial ? ".partial" : "");
         if (!write_pgm(stem + ".pgm", canvas.pixels.data(), info.max_column, info.max_row, info.pitch, info.bits)) return false;
         ++canvas.written;
-        return (!products.pr || products.write(canvas, s, info, stem, jpeg)) && (!projection.geo || projection.write(canvas, s, info, stem, products));
+        if (products.pr && !products.write(canvas, s, info, stem, jpeg)) return false;
+        if (overlay.on() && info.max_column && info.max_row) {          // the toned view lies where the product call left it
+            const Projection::SlotNav &n = projection.nav[s];
+            if (n.state == 1) {
+                if (!overlay.write(stem + ".view.map.ppm", product_view(), info.max_column, info.max_row, &n.nav, nullptr)) return false;
+            } else {
+                std::fprintf(stderr, "overlay: %s: no image navigation record of a file at line 0, column 0, no map drawn\n", stem.c_str());
+                ++overlay.skipped;
+            }
+        }
+        if (projection.geo && !projection.write(canvas, s, info, stem, products)) return false;
+        if (overlay.on() && projection.geo && projection.wrote_view)
+            return overlay.write(stem + ".geo.view.map.ppm", product_view(), projection.grid.columns, projection.grid.rows, nullptr, &projection.grid);
+        return true;
+    }
+    // the toned image of the product handle's last host-buffer or resident call, on the device
+    const uint8_t *product_view()
+    {
+        const uint8_t *d_tone = nullptr, *d_small = nullptr;
+        if (xrit_product_outputs_device(products.pr, &d_tone, &d_small) != XRIT_OK) fail("product outputs");
+        return d_tone;
     }
     // the end of the run: what is incomplete becomes .partial.pgm, and every open stage's line on stderr
     void close()
@@ -694,6 +839,7 @@ struct DecodeChain {
             if (products.pr) products.report();
             if (jpeg.jp) jpeg.report();
             if (projection.geo) projection.report();
+            if (overlay.on()) overlay.report();
         }
         if (packets.pk) packets.report();
     }
